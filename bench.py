@@ -1,16 +1,18 @@
 #!/usr/bin/env python3
 """Headline benchmark: realtime factor of PCM -> tokens for base.en on 30 s chunks (BASELINE.json).
 
-  python bench.py --gpus N --steps K --warmup W        (N > 1: launched by torch.distributed.run)
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]   (N > 1: launched by torch.distributed.run)
 
 A step = one complete transcription of one 30 s chunk of synthetic 16 kHz PCM through the boundary the Godot
 host binds — whisper_full(ctx, params, const float * pcm, n) with HOST samples, i.e. the 1.92 MB H2D copy is inside
 the timed region — with the host's parameter set (src/speech_to_text.cpp:403-413: greedy, max_tokens 16,
 single_segment, token timestamps): log-mel -> conv -> 6 encoder blocks -> cross K/V -> prompt + <=17 KV-cached
-decoder steps with the reference's logit filters and sampling.  Secondary figures in the same line: the same with the
-PCM already resident in HBM, the uncapped (max_tokens = 0) transcription, 8 / 16 chunks per call in lock-step,
+decoder steps with the reference's logit filters and sampling.  A plain run sets up, warms up, times the K steps and
+prints the line.  With --full, secondary figures in the same line: the same with the PCM already resident in HBM, the
+uncapped (max_tokens = 0) transcription, 8 / 16 chunks per call in lock-step, the streaming node, the host DSP,
 BASELINE configs[4] (large-v3 q5_1, beam 5), the roofline of the kernel with the largest share of GPU time, of the
 whole decode step and of the encoder, and the reference's CPU path on this box's cores.
+--dump-outputs DIR writes what the last timed step returned to its caller (token data, segments, text) as .npy files.
 Rank r transcribes its own chunks (independent units, no collective in the hot loop: SURVEY §8(e));
 the only collective is the RCCL broadcast of the ggml model image before timing starts.
 Prints ONE JSON line on rank 0.
@@ -54,9 +56,16 @@ def main():
                          "figures, no CPU baseline, no configs[4]")
     ap.add_argument("--chunks", type=int, default=1,
                     help="chunks per GPU per step: 1 = BASELINE configs[1] (headline); 8 = configs[3]'s per-GPU share, lock-step")
+    ap.add_argument("--full", action="store_true",
+                    help="the secondary figures too (device PCM, uncapped, 8 / 16 chunks, streaming node, host DSP, rooflines, CPU baseline, "
+                         "configs[4]); without it the run times the headline steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to its caller as DIR/<name>.npy (float64)")
     args = ap.parse_args()
     if args.profile:
         args.no_cpu_baseline = True; args.no_config4 = True; args.stream_seconds = 0.0
+    # --profile: the headline loop + the per-kernel chains of --full (no secondary figures)
+    full = args.full or args.profile
     IT = 20 if args.profile else 200                 # launches per micro-benchmark chain
 
     import torch
@@ -157,6 +166,8 @@ def main():
         dist.barrier()
     dt = time.perf_counter() - t0
     lib.wmi_get_timings(ctx, t6, n5)
+    if args.dump_outputs:
+        dump_outputs(lib, ctx, args.chunks, args.dump_outputs, "" if world == 1 else f"rank{rank}_")
     if args.chunks > 1:
         lib.wmi_batch_select(ctx, 0)
     n_tokens = sum(lib.whisper_full_n_tokens(ctx, s) for s in range(lib.whisper_full_n_segments(ctx)))
@@ -164,16 +175,16 @@ def main():
     # spread of the headline: the timed steps themselves, and — when K is small — a 200-step sample of the same loop
     spread = {"steps": int(args.steps), "median_ms": round(1e3 * float(np.median(per_step)), 4), "min_ms": round(1e3 * float(per_step.min()), 4),
               "max_ms": round(1e3 * float(per_step.max()), 4), "max_at_step": int(per_step.argmax())}
-    if args.steps < 200 and world == 1 and not args.profile:
+    if args.full and args.steps < 200 and world == 1 and not args.profile:
         extra = np.empty(200)
         for i in range(200):
             ts = time.perf_counter(); step(i); extra[i] = time.perf_counter() - ts
         spread["sample_200"] = {"mean_ms": round(1e3 * float(extra.mean()), 4), "median_ms": round(1e3 * float(np.median(extra)), 4),
                                 "min_ms": round(1e3 * float(extra.min()), 4), "p95_ms": round(1e3 * float(np.percentile(extra, 95)), 4)}
 
-    # ---- secondary figures in the same run (N = 1, headline configuration only)
+    # ---- secondary figures in the same run (--full; N = 1, headline configuration only)
     dev_pcm = None; uncapped = None
-    if args.chunks == 1 and world == 1 and not args.device_pcm and not args.profile:
+    if args.full and args.chunks == 1 and world == 1 and not args.device_pcm and not args.profile:
         reps = max(20, min(300, args.steps // 5))
         for i in range(3):
             t = pcm_dev[i % n_distinct]; assert lib.wmi_full_device_pcm(ctx, params, C.c_void_p(t.data_ptr()), t.numel(), None) == 0
@@ -198,7 +209,7 @@ def main():
         uncapped = {"workload": "same chunk with max_tokens = 0 (no cap on the decoded tokens), whisper_full with host PCM",
                     "value": round(CHUNK_S / tu, 1), "unit": "x realtime", "ms_per_step": round(tu * 1e3, 3), "tokens": int(ntok0)}
     batch8 = None
-    if args.chunks == 1 and not args.profile:
+    if args.full and args.chunks == 1 and not args.profile:
         # BASELINE configs[3]: 8 chunks per GPU in lock-step — at N > 1 every rank runs its own 8 (64 chunks on 8 GPUs), the figure
         # is all ranks' audio over the slowest rank's time
         nb, reps = 8, max(3, args.steps // 8)
@@ -230,10 +241,10 @@ def main():
                   "encoder_tflops": round(nb * ENC_GFLOP / (acc[1] / reps / 1e3), 1)}
 
     stream = None
-    if args.stream_seconds > 0 and world == 1:
+    if args.full and args.stream_seconds > 0 and world == 1:
         stream = stream_config(lib, args.stream_seconds)
     host_dsp = None
-    if world == 1 and not args.profile and args.chunks == 1:
+    if args.full and world == 1 and not args.profile and args.chunks == 1:
         host_dsp = host_dsp_config(lib, ctx, cpu=not args.no_cpu_baseline)
 
     tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
@@ -294,7 +305,7 @@ def main():
         # chain of dependent kernels; each kind is timed in its own back-to-back chain (which = 20 + WMI_STEP_MASK, no host in
         # the loop), its algorithmic bytes are the weights + cache rows it has to read once.
         try:
-          if args.chunks > 1:
+          if full and args.chunks > 1:
             # lock-step configuration (configs[3] per-GPU share): the whole decode step of `chunks` rows in its own chain
             step(0)
             hp_S = lib.whisper_model_n_audio_state(ctx); T = lib.whisper_model_n_audio_ctx(ctx); NV = lib.whisper_n_vocab(ctx)
@@ -305,7 +316,7 @@ def main():
                                "bound": "hbm", "achieved": round(step_bytes / (us_step * 1e-6) / 1e9, 1), "peak": 8000.0, "unit": "GB/s",
                                "frac": round(step_bytes / (us_step * 1e-6) / 1e9 / 8000.0, 4), "traffic": None, "algorithmic_bytes": int(step_bytes), "avg_us": round(us_step, 2),
                                "note": "the probe replays the step with its embedding launch; inside a call every step after a window's first is chained on the device (no embedding launch), see decode_ms_per_token"}
-          else:
+          elif full:
             step(0)                                          # the step record / caches of a headline transcription (17 cells)
             hp_S = lib.whisper_model_n_audio_state(ctx); T = lib.whisper_model_n_audio_ctx(ctx); NV = lib.whisper_n_vocab(ctx)
             Lt = lib.whisper_model_n_text_layer(ctx)
@@ -471,7 +482,7 @@ def main():
             except Exception as e:  # pragma: no cover
                 out["encoder_gemm_mfma_utilisation_batch16_error"] = repr(e)
         # ---- CPU baseline on this box's host cores (bounded sample), rank 0 / N=1 only
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(model_bytes, pcm_host[0])
             # SURVEY §8(d) asks for the host's wider settings too: n_threads = hardware concurrency, and an intermediate count
             # (whisper.cpp's spin-barrier thread pool does not scale to hundreds of threads on a 1500 x 512 problem)
@@ -484,7 +495,7 @@ def main():
     # ---- BASELINE configs[4]: large-v3 q5_1, beam_size = 5 — each GPU's share of "batch = 8 on 8 GPUs" is one chunk; at N > 1 rank 0
     # synthesises the model, the others receive header image + arena by the same two broadcasts as base.en (all ranks take part)
     c4 = None
-    if args.chunks == 1 and not args.no_config4 and not args.profile:
+    if args.full and args.chunks == 1 and not args.no_config4 and not args.profile:
         lib.whisper_free(ctx); node.ctx = None; ctx = None              # release base.en before the 1.2 GB model
         try:
             c4 = config4(lib, cpu=(not args.no_cpu_baseline) and world == 1, rank=rank, world=world, dist=dist, local_rank=local_rank, dev=dev)
@@ -500,6 +511,28 @@ def main():
     node.ctx = None
     if world > 1:
         dist.destroy_process_group()
+
+
+def dump_outputs(lib, ctx, chunks: int, out_dir: str, prefix: str = "") -> None:
+    """What the caller of the timed call reads back after it (W/whisper.h:557-620), per chunk, as float64 .npy files:
+    <chunk>tokens [n][9] = id tid p plog pt ptsum t0 t1 vlen of every token in segment order (tests/golden_util.tokens_array),
+    <chunk>segments [n][3] = t0 t1 n_tokens, <chunk>text = the UTF-8 bytes of the segments' text.  A few KB per chunk."""
+    os.makedirs(out_dir, exist_ok=True)
+    for c in range(chunks):
+        if chunks > 1:
+            assert lib.wmi_batch_select(ctx, c) >= 0
+        name = prefix + (f"chunk{c}_" if chunks > 1 else "")
+        toks, segs, text = [], [], b""
+        for s in range(lib.whisper_full_n_segments(ctx)):
+            nt = lib.whisper_full_n_tokens(ctx, s)
+            segs.append([lib.whisper_full_get_segment_t0(ctx, s), lib.whisper_full_get_segment_t1(ctx, s), nt])
+            text += lib.whisper_full_get_segment_text(ctx, s) or b""
+            for j in range(nt):
+                t = lib.whisper_full_get_token_data(ctx, s, j)
+                toks.append([t.id, t.tid, t.p, t.plog, t.pt, t.ptsum, t.t0, t.t1, t.vlen])
+        np.save(os.path.join(out_dir, name + "tokens.npy"), np.asarray(toks, np.float64).reshape(-1, 9))
+        np.save(os.path.join(out_dir, name + "segments.npy"), np.asarray(segs, np.float64).reshape(-1, 3))
+        np.save(os.path.join(out_dir, name + "text.npy"), np.frombuffer(text, np.uint8).astype(np.float64))
 
 
 def config4(lib, cpu: bool = True, rank: int = 0, world: int = 1, dist=None, local_rank: int = 0, dev=None) -> dict:

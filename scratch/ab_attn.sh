@@ -2,7 +2,7 @@
 # attention output stores: wide (LDS-transposed 16-byte) vs narrow (8-byte) — bench fields attn_layer_us / attn_layer_batch8_us / encode_ms
 for v in wide narrow wide narrow; do
   if [ $v = narrow ]; then export WMI_ATTN_NARROW_STORES=1; else unset WMI_ATTN_NARROW_STORES; fi
-  python bench.py --steps 200 --no-config4 --no-cpu-baseline --stream-seconds 0 > /tmp/ab_$v.json 2>/tmp/ab_$v.err
+  python bench.py --full --steps 200 --no-config4 --no-cpu-baseline --stream-seconds 0 > /tmp/ab_$v.json 2>/tmp/ab_$v.err
   python - "$v" <<'PY'
 import json,sys
 v=sys.argv[1]

@@ -3,7 +3,7 @@
 VAR=$1; VAL=$2; REPS=${3:-2}
 for rep in $(seq $REPS); do for v in default knob; do
   if [ $v = knob ]; then export $VAR=$VAL; else unset $VAR; fi
-  python bench.py --steps 200 --no-config4 --no-cpu-baseline --stream-seconds 0 > /tmp/ab_$v.json 2>/tmp/ab_$v.err
+  python bench.py --full --steps 200 --no-config4 --no-cpu-baseline --stream-seconds 0 > /tmp/ab_$v.json 2>/tmp/ab_$v.err
   python - "$v" "$VAR=$VAL" <<'PY'
 import json,sys
 v=sys.argv[1]

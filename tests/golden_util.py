@@ -75,6 +75,65 @@ def param_variants(node):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ recorded reference results
+# The CPU tests that hold the product or the oracle to the compiled reference bit for bit compare against what the reference
+# returned for the same seeded inputs, stored in tests/golden/reference_records.json: SHA-256 digests of its output arrays and
+# the few scalars the tests use.  `WMI_RECORD_REFERENCE=1 python -m pytest tests -m "not gpu"` where oracle/_ref/ is built
+# (make -C oracle ref) computes every value with the compiled reference instead, asserts against it and rewrites the record.
+import hashlib  # noqa: E402
+import json  # noqa: E402
+import os  # noqa: E402
+
+REF_RECORDS = GOLDEN / "reference_records.json"
+RECORDING = os.environ.get("WMI_RECORD_REFERENCE") == "1"
+_records = None
+
+
+def digest(*arrays) -> str:
+    """SHA-256 over the exact bytes of the arrays (dtype, shape and contents)."""
+    h = hashlib.sha256()
+    for a in arrays:
+        a = np.ascontiguousarray(a)
+        h.update(f"{a.dtype.str}{a.shape}".encode()); h.update(a.tobytes())
+    return h.hexdigest()
+
+
+def ref_value(key: str, compute):
+    """The compiled reference's result under `key`: compute() with the reference while recording, else the stored value."""
+    global _records
+    if _records is None:
+        _records = json.loads(REF_RECORDS.read_text()) if REF_RECORDS.exists() else {}
+    if RECORDING:
+        v = compute()
+        _records[key] = v
+        REF_RECORDS.write_text(json.dumps(_records, indent=0, sort_keys=True) + "\n")
+        return v
+    assert key in _records, f"{key} not recorded: run the tests with WMI_RECORD_REFERENCE=1 where oracle/_ref/ is built"
+    return _records[key]
+
+
+def recording_ref_lib():
+    """The compiled reference (recording runs only), logs silenced."""
+    import ctypes as C
+    from oracle import reflib
+    assert RECORDING and reflib.available(), "recording needs oracle/_ref/libwhisper_ref.so (make -C oracle ref)"
+    lib = reflib.lib()
+    if not hasattr(lib, "_cb"):
+        cb = abi.ggml_log_callback(lambda lvl, txt, ud: None)
+        lib.whisper_log_set(C.cast(cb, C.c_void_p), None); lib._cb = cb
+    return lib
+
+
+def stage_digests(side, pcm, actx, sot):
+    """mel, the encoder's outputs and two decoder calls of one side (sc.RefSide / port.PortSide), as digests"""
+    out = {"mel": digest(side.mel(pcm)[0])}
+    for k, v in side.encode(0, actx).items():
+        out[f"encode/{k}"] = digest(v)
+    out["decode_sot"] = digest(side.decode([sot], 0))
+    out["decode_3"] = digest(side.decode([1000, 2000, 3000], 1))
+    return out
+
+
 STREAM_INTERVAL = 0.7
 
 

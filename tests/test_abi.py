@@ -56,18 +56,30 @@ def test_default_params_match_reference_defaults():
     assert lib.whisper_context_default_params().use_gpu is True
 
 
-def test_reference_defaults_agree(ref_lib):
+def _default_fields(p):
+    """whisper_full_params as plain values (JSON-able); n_threads (hardware-dependent) left out"""
+    out = {}
+    for name, _ in abi.whisper_full_params._fields_:
+        if name in ("n_threads", "greedy", "beam_search"):
+            continue
+        v = getattr(p, name)
+        if name == "prompt_tokens":              # ctypes pointer objects: compare NULL-ness
+            v = bool(v)
+        out[name] = v.decode("latin-1") if isinstance(v, bytes) else v
+    out["greedy/best_of"] = p.greedy.best_of; out["beam_search/beam_size"] = p.beam_search.beam_size
+    out["beam_search/patience"] = p.beam_search.patience
+    return out
+
+
+def test_reference_defaults_agree():
+    import golden_util as gu
     lib = runtime.load_library()
     for strat in (0, 1):
-        a = lib.whisper_full_default_params(strat); b = ref_lib.whisper_full_default_params(strat)
-        for name, _ in abi.whisper_full_params._fields_:
-            if name in ("n_threads", "greedy", "beam_search"):
-                continue
-            va, vb = getattr(a, name), getattr(b, name)
-            if name == "prompt_tokens":              # ctypes pointer objects: compare NULL-ness
-                va, vb = bool(va), bool(vb)
-            assert va == vb, name
-        assert (a.greedy.best_of, a.beam_search.beam_size, a.beam_search.patience) == (b.greedy.best_of, b.beam_search.beam_size, b.beam_search.patience)
+        a = _default_fields(lib.whisper_full_default_params(strat))
+        b = gu.ref_value(f"abi/full_default_params/{strat}", lambda: _default_fields(gu.recording_ref_lib().whisper_full_default_params(strat)))
+        assert sorted(a) == sorted(b)
+        for name in a:
+            assert a[name] == b[name], name
 
 
 def test_free_is_null_safe_and_log_callback_installs():

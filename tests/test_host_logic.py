@@ -1,6 +1,6 @@
 """Host-side decision logic of the product (tokenizer, logit filters, sampling)
-on a host-only context — no GPU needed — against the reference's goldens and, where present, live against
-the compiled reference fed identical logits."""
+on a host-only context — no GPU needed — against the reference's goldens and against
+the compiled reference fed identical logits (its recorded results, tests/golden/reference_records.json)."""
 import ctypes as C
 
 import numpy as np
@@ -9,7 +9,6 @@ import pytest
 import golden_util as gu
 import stage_compare as sc
 from godot_whisper_amd import abi, host, runtime
-from oracle import reflib
 
 G = np.load(gu.GOLDEN / "hotpath.npz")
 
@@ -116,11 +115,29 @@ def test_host_only_context_has_no_compute_path(lib):
         lib.whisper_free(ctx)
 
 
-@pytest.mark.skipif(not reflib.available(), reason="compiled reference absent")
-def test_filters_live_against_reference(lib, ref_lib):
+def _ref_node(model):
+    """SpeechToText over the compiled reference (recording runs, tests/golden_util.ref_value)"""
+    rnode = host.SpeechToText(gu.recording_ref_lib()); rnode.set_language_model(model)
+    return rnode
+
+
+def _process(L, c, nd, fill, raw, hist, temp):
+    """wmi_process_logits / ref_process_logits on one raw row: (logits, log-probabilities, probabilities)"""
+    fn = L.wmi_process_logits if hasattr(L, "wmi_process_logits") else L.ref_process_logits
+    p = nd.full_params("", 0); keep = fill(p)
+    nv = raw.size
+    lo, lp, pr = (np.empty(nv, np.float32) for _ in range(3))
+    fn(c, p, sc._fptr(raw), hist.ctypes.data_as(C.POINTER(C.c_int32)), hist.size, 0, 3000, C.c_float(temp),
+       sc._fptr(lo), sc._fptr(lp), sc._fptr(pr))
+    del keep
+    return lo, lp, pr
+
+
+def test_filters_live_against_reference(lib):
+    """the logit filters and soft-max bit-identical to the compiled reference's on equal raw logits (recorded digests)"""
     model, _, _ = gu.case_inputs("en30")
     ctx = host_ctx(lib, "en30")
-    rnode = host.SpeechToText(ref_lib); rnode.set_language_model(model)
+    rnode = None
     node = host.SpeechToText(lib); node.ctx = ctx
     try:
         nv = lib.whisper_n_vocab(ctx)
@@ -128,30 +145,30 @@ def test_filters_live_against_reference(lib, ref_lib):
         for trial in range(6):
             raw = (rng.standard_normal(nv) * 5.0).astype(np.float32)
             hist = rng.integers(0, 50000, size=trial).astype(np.int32)
-            outs = []
-            for L, c, fn in ((lib, ctx, lib.wmi_process_logits), (ref_lib, rnode.ctx, ref_lib.ref_process_logits)):
-                nd = node if L is lib else rnode
-                p = nd.full_params("", 0); p.suppress_non_speech_tokens = bool(trial % 2)
-                lo, lp, pr = (np.empty(nv, np.float32) for _ in range(3))
-                fn(c, p, sc._fptr(raw), hist.ctypes.data_as(C.POINTER(C.c_int32)), hist.size, 0, 3000, C.c_float(0.2 * trial),
-                   sc._fptr(lo), sc._fptr(lp), sc._fptr(pr))
-                outs.append((lo.copy(), lp.copy(), pr.copy()))
-            for a, b in zip(outs[0], outs[1]):
-                assert np.array_equal(a, b)
+            def fill(p):
+                p.suppress_non_speech_tokens = bool(trial % 2)
+            got = _process(lib, ctx, node, fill, raw, hist, 0.2 * trial)
+            def ref():
+                nonlocal rnode
+                rnode = rnode or _ref_node(model)
+                return [gu.digest(a) for a in _process(rnode.lib, rnode.ctx, rnode, fill, raw, hist, 0.2 * trial)]
+            want = gu.ref_value(f"host_logic/filters/{trial}", ref)
+            assert [gu.digest(a) for a in got] == want
     finally:
-        node.ctx = None; lib.whisper_free(ctx); rnode.close()
+        node.ctx = None; lib.whisper_free(ctx)
+        if rnode:
+            rnode.close()
 
 
 # ------------------------------------------------------------------------------------------------ grammar-constrained decoding
-@pytest.mark.skipif(not reflib.available(), reason="compiled reference absent")
 @pytest.mark.parametrize("which", ["colours", "negated", "unicode"])
-def test_grammar_penalties_live_against_reference(lib, ref_lib, which):
+def test_grammar_penalties_live_against_reference(lib, which):
     """whisper_full_params.grammar_rules (W/whisper.cpp:3876-4290): after the same token history both libraries must
     penalise exactly the same tokens — logits, log-probabilities and probabilities bit-identical on equal raw logits."""
     model, _, _ = gu.case_inputs("en30" if which != "unicode" else "ml11")
     name = "en30" if which != "unicode" else "ml11"
     ctx = host_ctx(lib, name)
-    rnode = host.SpeechToText(ref_lib); rnode.set_language_model(model)
+    rnode = None
     node = host.SpeechToText(lib); node.ctx = ctx
     rules = {"colours": gu.colour_list_grammar, "negated": gu.negated_class_grammar, "unicode": gu.unicode_grammar}[which]()
     texts = {"colours": ["", " red", " red,", " red, 12", " red, 120, gre", " blue.", " purple", " red, green, blue, 7"],
@@ -174,22 +191,22 @@ def test_grammar_penalties_live_against_reference(lib, ref_lib, which):
             hist = np.asarray(hist, np.int32)
             raw = (rng.standard_normal(nv) * 3.0).astype(np.float32)
             raw[beg:] -= 30.0                                                    # keep the timestamp mass below the text tokens
-            outs = []
-            for L, c, fn in ((lib, ctx, lib.wmi_process_logits), (ref_lib, rnode.ctx, ref_lib.ref_process_logits)):
-                nd = node if L is lib else rnode
-                p = nd.full_params("", 0)
+            def fill(p):
                 ptrs, n_rules, keep = abi.make_grammar(rules)
                 p.grammar_rules = C.cast(ptrs, C.c_void_p); p.n_grammar_rules = n_rules; p.i_start_rule = 0; p.grammar_penalty = 50.0 + k
-                lo, lp, pr = (np.empty(nv, np.float32) for _ in range(3))
-                fn(c, p, sc._fptr(raw), hist.ctypes.data_as(C.POINTER(C.c_int32)), hist.size, 0, 3000, C.c_float(0.0),
-                   sc._fptr(lo), sc._fptr(lp), sc._fptr(pr))
-                outs.append((lo.copy(), lp.copy(), pr.copy()))
-                del keep
-            for a, b in zip(outs[0], outs[1]):
-                assert np.array_equal(a, b), (which, text)
-            n_penalised.append(int(np.sum(np.isfinite(outs[0][0]) & (outs[0][0] < raw - 1.0))))
+                return keep
+            got = _process(lib, ctx, node, fill, raw, hist, 0.0)
+            def ref():
+                nonlocal rnode
+                rnode = rnode or _ref_node(model)
+                return [gu.digest(a) for a in _process(rnode.lib, rnode.ctx, rnode, fill, raw, hist, 0.0)]
+            want = gu.ref_value(f"host_logic/grammar/{which}/{k}", ref)
+            assert [gu.digest(a) for a in got] == want, (which, text)
+            n_penalised.append(int(np.sum(np.isfinite(got[0]) & (got[0] < raw - 1.0))))
         # constrained states penalise most of the vocabulary (the negated class: the tokens holding a banned character); histories
         # the grammar cannot parse leave no stack, and then nothing is penalised (:4227)
         assert max(n_penalised) > (5000 if which == "negated" else 40000) and min(n_penalised) == 0, n_penalised
     finally:
-        node.ctx = None; lib.whisper_free(ctx); rnode.close()
+        node.ctx = None; lib.whisper_free(ctx)
+        if rnode:
+            rnode.close()

@@ -1,6 +1,7 @@
 """CPU-side pins of oracle/host_dsp.c and of the product's host-side resampling plan.
 
-* VAD + high-pass filter: bit-exact against the reference's own compiled W/examples/common.cpp (oracle/_ref/libcommon_ref.so).
+* VAD + high-pass filter: bit-exact against the reference's own compiled W/examples/common.cpp (oracle/_ref/libcommon_ref.so;
+  its recorded results, tests/golden/reference_records.json).
 * SINC resampler: libsamplerate cannot be compiled here (src_sinc.c:36 includes a missing blob), so the restatement is held to
   the reference's own TEST PROGRAMS restated on top of it — thirdparty/libsamplerate/tests/termination_test.c (init_term_test,
   simple_test) and snr_bw_test.c (snr_test with calc_snr.c's peak analysis) for the two converters whose tables are in the tree —
@@ -15,6 +16,8 @@ import struct
 
 import numpy as np
 import pytest
+
+import golden_util as gu
 
 ROOT = pathlib.Path(__file__).resolve().parent.parent
 DATA = ROOT / "godot-whisper_amd" / "csrc" / "data"
@@ -59,11 +62,10 @@ def src_simple(dsp, x, ratio, converter, out_frames):
 
 # ------------------------------------------------------------------------------------------------ VAD against the compiled reference
 
-@pytest.fixture(scope="module")
 def common_ref():
+    """the reference's compiled high_pass_filter / vad_simple (recording runs, tests/golden_util.ref_value)"""
     so = ROOT / "oracle" / "_ref" / "libcommon_ref.so"
-    if not so.exists():
-        pytest.skip("oracle/_ref/libcommon_ref.so not built (make -C oracle ref needs /root/reference)")
+    assert gu.RECORDING and so.exists(), "recording needs oracle/_ref/libcommon_ref.so (make -C oracle ref)"
     lib = C.CDLL(str(so))
     lib.ref_high_pass_filter.restype = None
     lib.ref_high_pass_filter.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float]
@@ -80,29 +82,35 @@ def _speechy(rng, n, loud_tail):
 
 
 @pytest.mark.parametrize("cutoff", [100.0, 200.0, 1234.5])
-def test_high_pass_filter_is_the_compiled_reference_bit_for_bit(dsp, common_ref, cutoff):
+def test_high_pass_filter_is_the_compiled_reference_bit_for_bit(dsp, cutoff):
     rng = np.random.default_rng(7)
     x = _speechy(rng, 48000, 1.0)
-    a, b = x.copy(), x.copy()
+    a = x.copy()
     dsp.oracle_high_pass_filter(a.ctypes.data, a.size, cutoff, 16000.0)
-    common_ref.ref_high_pass_filter(b.ctypes.data, b.size, cutoff, 16000.0)
-    assert a.tobytes() == b.tobytes()
+    def ref():
+        b = x.copy()
+        common_ref().ref_high_pass_filter(b.ctypes.data, b.size, cutoff, 16000.0)
+        return gu.digest(b)
+    assert gu.digest(a) == gu.ref_value(f"host_dsp/high_pass/{cutoff}", ref)
 
 
 @pytest.mark.parametrize("tail,thold,freq", [(1.0, 2.0, 200.0), (0.05, 2.0, 200.0), (0.05, 0.6, 100.0), (3.0, 2.0, 0.0), (0.3, 1.0, 200.0)])
-def test_vad_decision_and_filtered_samples_equal_the_compiled_reference(dsp, common_ref, tail, thold, freq):
+def test_vad_decision_and_filtered_samples_equal_the_compiled_reference(dsp, tail, thold, freq):
     rng = np.random.default_rng(11)
     x = _speechy(rng, 48000, tail)
-    a, b = x.copy(), x.copy()
+    a = x.copy()
     en = np.zeros(2, np.float32)
     got = dsp.oracle_vad_simple(a.ctypes.data, a.size, 16000, 500, thold, freq, 1, en.ctypes.data)     # upstream decision
-    want = common_ref.ref_vad_simple(b.ctypes.data, b.size, 16000, 500, thold, freq)
-    assert a.tobytes() == b.tobytes()
+    def ref():
+        b = x.copy()
+        return [int(common_ref().ref_vad_simple(b.ctypes.data, b.size, 16000, 500, thold, freq)), gu.digest(b)]
+    want, want_samples = gu.ref_value(f"host_dsp/vad/{tail}/{thold}/{freq}", ref)
+    assert gu.digest(a) == want_samples
     assert got == want
     # the host's form differs only by its "both energies below 1e-4" clause (src/speech_to_text.cpp:99): loud input -> never "silent"
     c = x.copy()
     host = dsp.oracle_vad_simple(c.ctypes.data, c.size, 16000, 500, thold, freq, 0, en.ctypes.data)
-    assert c.tobytes() == b.tobytes()
+    assert gu.digest(c) == want_samples
     assert host == (1 if (en[0] < 1e-4 and en[1] < 1e-4 and not en[1] > np.float32(thold) * en[0]) else 0)
 
 

@@ -1,17 +1,18 @@
 """Pin the oracle's restatement of the reference's block-quantised arithmetic (oracle/port_quants.c) before it checks
 anything: bit for bit against the reference's own exported functions (quantize_row_q8_0/1, ggml_vec_dot_*,
-dequantize_row_*: W/ggml-quants.c) and, for whole models, against the compiled reference's encoder / decoder outputs.
-Runs where the compiled reference exists (the build container; on the GPU box the prebuilt library travels along)."""
+dequantize_row_*: W/ggml-quants.c) and, for whole models, against the compiled reference's encoder / decoder outputs —
+its recorded results (tests/golden/reference_records.json) on the same seeded inputs."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
+import golden_util as gu
 import stage_compare as sc
 from godot_whisper_amd import synth
-from oracle import port, reflib
+from oracle import port
 
-pytestmark = pytest.mark.skipif(not (port.available() and reflib.available()), reason="needs oracle/libwhisper_port.so and the compiled reference")
+pytestmark = pytest.mark.skipif(not port.available(), reason="needs oracle/libwhisper_port.so (python __graft_entry__.py build)")
 
 QT = {"q4_0": (2, 18, "q8_0"), "q4_1": (3, 20, "q8_1"), "q5_0": (6, 22, "q8_0"), "q5_1": (7, 24, "q8_1"), "q8_0": (8, 34, "q8_0")}
 
@@ -34,12 +35,30 @@ def _ref_quantize(ref, x, kind):
     return b[:, 2:].copy().view(np.int8).reshape(-1), b[:, 0:2].copy().view(np.float16).astype(np.float32).reshape(-1), None, buf
 
 
-def _setup(ref):
+def _ref():
+    """the compiled reference (recording runs, tests/golden_util.ref_value)"""
+    ref = gu.recording_ref_lib()
     # the reference converts f16 through a table that ggml_init fills (W/ggml.c:2222-2235): make sure it ran once
     tmp = np.empty(65536, np.uint16)
     assert ref.ref_gelu_table(_p(tmp, C.POINTER(C.c_uint16))) == 65536
     for n in ("quantize_row_q8_1", "quantize_row_q8_0"):
         getattr(ref, n).restype = None; getattr(ref, n).argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    return ref
+
+
+def _qdigest(qs, d, s):
+    """one quantised activation row (int8 values, f32 scales, q8_1 sums) as a digest"""
+    return gu.digest(qs, d.view(np.uint32), *([] if s is None else [s.view(np.uint32)]))
+
+
+def _port_quantize(pl, r, kind):
+    k = r.size
+    qs = np.zeros(k, np.int8); d = np.zeros(k // 32, np.float32); s = np.zeros(k // 32, np.float32)
+    pl.port_quantize_row_q8(_p(r), k, 1 if kind == "q8_1" else 0, _p(qs), _p(d), _p(s))
+    return qs, d, s
+
+
+def _setup():
     pl = port.lib()
     pl.port_quantize_row_q8.restype = None
     pl.port_quantize_row_q8.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -60,29 +79,43 @@ def _rows(rng, n, k):
 
 
 @pytest.mark.parametrize("kind", ["q8_0", "q8_1"])
-def test_row_quantiser_is_bit_exact(ref_lib, kind):
-    pl = _setup(ref_lib)
+def test_row_quantiser_is_bit_exact(kind):
+    pl = _setup()
     rng = np.random.default_rng(7)
     for k in (128, 512, 1280, 5120):
         x = _rows(rng, 6, k)
-        for r in x:
-            qs_r, d_r, s_r, _ = _ref_quantize(ref_lib, r, kind)
-            qs = np.zeros(k, np.int8); d = np.zeros(k // 32, np.float32); s = np.zeros(k // 32, np.float32)
-            pl.port_quantize_row_q8(_p(r), k, 1 if kind == "q8_1" else 0, _p(qs), _p(d), _p(s))
-            assert np.array_equal(qs, qs_r)
-            assert np.array_equal(d.view(np.uint32), d_r.view(np.uint32))
-            if s_r is not None:
-                assert np.array_equal(s.view(np.uint32), s_r.view(np.uint32))
+        want = gu.ref_value(f"oracle_quants/row_quantiser/{kind}/{k}", lambda: [_qdigest(*_ref_quantize(_ref(), r, kind)[:3]) for r in x])
+        for r, w in zip(x, want):
+            qs, d, s = _port_quantize(pl, r, kind)
+            assert _qdigest(qs, d, s if kind == "q8_1" else None) == w
+
+
+def _ref_vec_dot(qtype, k, wq, x):
+    """the reference's quantised rows of x, its dot products of every row of wq with them (f32 bits) and its dequantised wq[1]"""
+    ref = _ref()
+    gtype, bb, akind = QT[qtype]
+    dot = getattr(ref, f"ggml_vec_dot_{qtype}_{akind}")
+    dot.restype = None; dot.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    deq = getattr(ref, f"dequantize_row_{qtype}")
+    deq.restype = None; deq.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    rows = []
+    for r in x:
+        qs, d, s, raw = _ref_quantize(ref, r, akind)
+        outs = []
+        for i in range(wq.shape[0]):
+            out = C.c_float()
+            dot(k, C.byref(out), _p(wq[i]), _p(raw))
+            outs.append(int(np.float32(out.value).view(np.uint32)))
+        rows.append([_qdigest(qs, d, s), outs])
+    y_r = np.zeros(k, np.float32)
+    deq(_p(wq[1]), _p(y_r), k)
+    return {"rows": rows, "dequantised": gu.digest(y_r.view(np.uint32))}
 
 
 @pytest.mark.parametrize("qtype", list(QT))
-def test_vec_dot_and_dequantise_are_bit_exact(ref_lib, qtype):
-    pl = _setup(ref_lib)
+def test_vec_dot_and_dequantise_are_bit_exact(qtype):
+    pl = _setup()
     gtype, bb, akind = QT[qtype]
-    dot = getattr(ref_lib, f"ggml_vec_dot_{qtype}_{akind}")
-    dot.restype = None; dot.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-    deq = getattr(ref_lib, f"dequantize_row_{qtype}")
-    deq.restype = None; deq.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     rng = np.random.default_rng(11)
     worst = 0.0
     for k in (128, 1280, 5120):
@@ -90,39 +123,43 @@ def test_vec_dot_and_dequantise_are_bit_exact(ref_lib, qtype):
         w[0, :40] *= 30.0
         wq = np.frombuffer(synth.quantize_blocks(w, qtype), np.uint8).reshape(9, k // 32 * bb).copy()
         x = _rows(rng, 5, k)
-        for r in x:
-            qs, d, s, raw = _ref_quantize(ref_lib, r, akind)
-            if s is None:
-                s = np.zeros_like(d)
+        want = gu.ref_value(f"oracle_quants/vec_dot/{qtype}/{k}", lambda: _ref_vec_dot(qtype, k, wq, x))
+        for r, (qd, outs) in zip(x, want["rows"]):
+            qs, d, s = _port_quantize(pl, r, akind)
+            assert _qdigest(qs, d, s if akind == "q8_1" else None) == qd          # the reference's quantised row, bit for bit
             for i in range(9):
-                out = C.c_float()
-                dot(k, C.byref(out), _p(wq[i]), _p(raw))
+                out = float(np.uint32(outs[i]).view(np.float32))
                 got = pl.port_vec_dot_q(gtype, k, _p(wq[i]), _p(qs), _p(d), _p(s))
-                assert np.float32(got).view(np.uint32) == np.float32(out.value).view(np.uint32), (qtype, k, i)
+                assert int(np.float32(got).view(np.uint32)) == outs[i], (qtype, k, i)
                 # the per-block order (what the GPU kernels do) differs from it by f32 rounding only
                 bw = pl.port_vec_dot_q_blockwise(gtype, k, _p(wq[i]), _p(qs), _p(d), _p(s))
                 mag = float(np.abs(w[i]).astype(np.float64) @ np.abs(r).astype(np.float64))
-                worst = max(worst, abs(bw - out.value) / mag)
-        y_r = np.zeros(k, np.float32); y_p = np.zeros(k, np.float32)
-        deq(_p(wq[1]), _p(y_r), k); pl.port_dequantize_row(gtype, _p(wq[1]), _p(y_p), k)
-        assert np.array_equal(y_r.view(np.uint32), y_p.view(np.uint32))
+                worst = max(worst, abs(bw - out) / mag)
+        y_p = np.zeros(k, np.float32)
+        pl.port_dequantize_row(gtype, _p(wq[1]), _p(y_p), k)
+        assert gu.digest(y_p.view(np.uint32)) == want["dequantised"]
     assert worst < 3e-6, worst              # f32 rounding over <= 160 block terms
 
 
 @pytest.mark.parametrize("qtype", ["q5_1", "q8_0", "q4_0", "q4_1", "q5_0"])
-def test_port_is_bit_exact_on_a_quantised_model(ref_lib, qtype):
+def test_port_is_bit_exact_on_a_quantised_model(qtype):
     model = synth.quantize_model(synth.make_model("micro.en", seed=1234), qtype)
     pcm = synth.make_pcm(4.0, seed=5)
-    ref = sc.RefSide(ref_lib, model); ps = port.PortSide(model)
+    ps = port.PortSide(model)
     try:
-        ref.mel(pcm); ps.mel(pcm)
-        er = ref.encode(0, 228); ep = ps.encode(0, 228)
-        for k in er:
-            assert np.array_equal(er[k], ep[k]), k
-        assert np.array_equal(ref.decode([ps.sot], 0), ps.decode([ps.sot], 0))
-        assert np.array_equal(ref.decode([1000, 2000, 3000], 1), ps.decode([1000, 2000, 3000], 1))
+        got = gu.stage_digests(ps, pcm, 228, ps.sot)
+        def ref():
+            r = sc.RefSide(gu.recording_ref_lib(), model)
+            try:
+                return gu.stage_digests(r, pcm, 228, ps.sot)
+            finally:
+                r.close()
+        want = gu.ref_value(f"oracle_quants/model/{qtype}", ref)
+        assert sorted(got) == sorted(want)
+        for k in want:
+            assert got[k] == want[k], k
     finally:
-        ref.close(); ps.close()
+        ps.close()
 
 
 def test_reference_sensitivity_of_quantised_models():

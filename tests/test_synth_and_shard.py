@@ -87,17 +87,21 @@ def test_two_process_broadcast_and_gather_over_gloo(tmp_path):
 
 @pytest.mark.parametrize("qtype", ["q5_1", "q4_0", "q8_0"])
 def test_quantiser_is_byte_identical_to_the_reference_tool(qtype, tmp_path):
-    """synth.quantize_model regenerates quantised models on the GPU box; here (build container) it is pinned against
-    the reference's own `quantize` tool (W/examples/quantize), compiled by oracle/Makefile."""
+    """synth.quantize_model regenerates quantised models on the GPU box; it is pinned against the reference's own `quantize`
+    tool (W/examples/quantize, compiled by oracle/Makefile): the SHA-256 of the tool's output file, recorded
+    (tests/golden/reference_records.json)."""
+    import hashlib
     import pathlib
-    tool = pathlib.Path(__file__).resolve().parent.parent / "oracle" / "_ref" / "quantize"
-    if not tool.exists():
-        pytest.skip("reference quantize tool not built")
+    import golden_util as gu
     mb = synth.make_model("micro.en", seed=5)
-    (tmp_path / "m.bin").write_bytes(mb)
-    r = subprocess.run([str(tool), str(tmp_path / "m.bin"), str(tmp_path / "o.bin"), qtype], capture_output=True)
-    assert r.returncode == 0
-    assert (tmp_path / "o.bin").read_bytes() == synth.quantize_model(mb, qtype)
+    def ref():
+        tool = pathlib.Path(__file__).resolve().parent.parent / "oracle" / "_ref" / "quantize"
+        assert tool.exists(), "recording needs oracle/_ref/quantize (make -C oracle ref)"
+        (tmp_path / "m.bin").write_bytes(mb)
+        r = subprocess.run([str(tool), str(tmp_path / "m.bin"), str(tmp_path / "o.bin"), qtype], capture_output=True)
+        assert r.returncode == 0
+        return hashlib.sha256((tmp_path / "o.bin").read_bytes()).hexdigest()
+    assert hashlib.sha256(synth.quantize_model(mb, qtype)).hexdigest() == gu.ref_value(f"quantize_tool/micro.en_seed5/{qtype}", ref)
 
 
 @pytest.mark.parametrize("qtype", [None, "q5_1"])
