@@ -469,6 +469,30 @@ int wmi_selftest_ts_refine(struct whisper_context * ctx, const float * envelope,
     }
 }
 
+// one step of whisper_full's greedy fast path (device.cpp: decode_greedy_step) on the context's own state, as full() runs it after two text
+// tokens: the default greedy parameters' static ban, the state counted busy (the solo forms), the filter of a history without timestamps
+int wmi_selftest_greedy_step(struct whisper_context * ctx, whisper_token token, int pos, float * logits, whisper_token_data * out, int * forms) {
+    if (!ctx || ctx->host_only || !out) return -1;
+    CtxScope lk(ctx);
+    if (!compute_ready(*ctx, __func__)) return -2;
+    (void) hipSetDevice(ctx->device);
+    BusyScope busy(ctx->device);
+    const Vocab & v = ctx->model.vocab;
+    if (pos < 0 || pos >= ctx->model.hp.n_text_ctx || token < 0 || token >= v.n_vocab) return -1;
+    if (!upload_static_ban(*ctx, whisper_full_default_params(WHISPER_SAMPLING_GREEDY))) return -3;
+    StepFilter f{};                                      // full.cpp: step_filter() of a decoder whose last two tokens are text, has_ts = false
+    f.ban_blank = false; f.last_ts = false; f.penult_ts = false; f.ts_floor_end = v.beg; f.ts_initial_start = v.n_vocab;
+    unsigned fm = 0;
+    if (!decode_greedy_step(*ctx, token, pos, f, *out, &fm)) return -4;
+    if (logits) {
+        DeviceState & d = ctx->state->dev;
+        if (!HIP_OK(hipMemcpyAsync(logits, d.logits, (size_t) ctx->model.hp.n_vocab * 4, hipMemcpyDeviceToHost, d.stream)) ||
+            !HIP_OK(hipStreamSynchronize(d.stream))) return -5;
+    }
+    if (forms) *forms = (int) fm;
+    return 0;
+}
+
 int wmi_selftest_resample_plan(int n_frames, int src_rate, int dst_rate, int converter, long long * frames_gen, long long * frames_used,
                                int * closed_form, int n_pos, long long * pos, double * frac) {
     if (n_frames < 0 || src_rate <= 0 || dst_rate <= 0 || src_rate == dst_rate || n_pos < 0 || (n_pos > 0 && (!pos || !frac))) return -1;

@@ -885,6 +885,22 @@ struct StepTicket {
 };
 }
 
+// which launches enqueue_greedy_step takes for the f16 step (STEP_FORM_PAIRED / _FRONTED / _BACKED; wmi.h)
+static unsigned greedy_step_forms(whisper_context & ctx, int Tc, bool long_kv, bool chained, bool solo) {
+    const DeviceState & d = ctx.state->dev; const HParams & hp = ctx.model.hp;
+    const int S = hp.n_text_state, H = hp.n_text_head, Lt = hp.n_text_layer;
+    const unsigned M = g_step_mask;
+    const k::Knobs & kn = k::knobs();
+    // the MLP form is decided once for the whole step: the paired launches' tags alternate between two words from launch to launch (an even
+    // number of layers keeps that up across steps), so either every layer pairs or none does
+    const bool paired = (M & 32) && (M & 64) && !kn.no_mlp_pair && solo && d.mlp_hand && (Lt & 1) == 0 && k::mlp_pair_usable(S, chained);
+    // the same decision for the front of the layers (k::front): short caches only; its status goes through the MLP pair's word, so it
+    // runs where that pair does (the pick kernel reports the word, a fault re-runs the step without either)
+    const bool fronted = paired && !long_kv && (M & 2) && (M & 4) && !kn.no_front && k::front_usable(S);
+    const bool backed = paired && (M & 8) && (M & 16) && !kn.no_xback && k::xback_usable(S, H, Tc);
+    return (paired ? STEP_FORM_PAIRED : 0u) | (fronted ? STEP_FORM_FRONTED : 0u) | (backed ? STEP_FORM_BACKED : 0u);
+}
+
 constexpr int PAIR_FAULT_WORD = 4;           // d.mlp_arrive as 32-bit words: [0], [1] the MLP launches' tags, [2], [3] the front launches', [6], [7] the cross-attention back's, [4] the hand-offs' status (k::MlpPairArgs::fault)
 static void enqueue_greedy_step(whisper_context & ctx, int Tc, bool long_kv = false, bool chained = false, bool solo = true) {
     if (ctx.model.quantised) { enqueue_greedy_step_q(ctx, Tc); return; }
@@ -912,14 +928,9 @@ static void enqueue_greedy_step(whisper_context & ctx, int Tc, bool long_kv = fa
         g.scale = scale; g.S = S; g.rows = nullptr; g.row_off = row_off;
         k::gemv(g, s);
     };
-    // the MLP form is decided once for the whole step: the paired launches' tags alternate between two words from launch to launch (an even
-    // number of layers keeps that up across steps), so either every layer pairs or none does
     const k::Knobs & kn = k::knobs();
-    const bool paired = (M & 32) && (M & 64) && !kn.no_mlp_pair && solo && d.mlp_hand && (Lt & 1) == 0 && k::mlp_pair_usable(S, chained);
-    // the same decision for the front of the layers (k::front): short caches only; its status goes through the MLP pair's word, so it
-    // runs where that pair does (the pick kernel reports the word, a fault re-runs the step without either)
-    const bool fronted = paired && !long_kv && (M & 2) && (M & 4) && !kn.no_front && k::front_usable(S);
-    const bool backed = paired && (M & 8) && (M & 16) && !kn.no_xback && k::xback_usable(S, H, Tc);
+    const unsigned forms = greedy_step_forms(ctx, Tc, long_kv, chained, solo);
+    const bool paired = forms & STEP_FORM_PAIRED, fronted = forms & STEP_FORM_FRONTED, backed = forms & STEP_FORM_BACKED;
     for (int il = 0; il < Lt; ++il) {
         const DecLayerW & l = w.dec[il];
         __half * ck = kv.k + ((size_t) il * n_ctx) * S, * cv = kv.v + ((size_t) il * n_ctx) * S;
@@ -1010,7 +1021,7 @@ static void enqueue_greedy_step(whisper_context & ctx, int Tc, bool long_kv = fa
     if (M & 256) k::filter_argmax(d.logits, d.ban_dev, stp, (k::SampleOut *) d.sample_dev, d.filter_scratch, s, (k::SampleOut *) d.sample_host, 1, &cn, fused_parts); chk("filter", Lt);
 }
 
-bool decode_greedy_step(whisper_context & ctx, int32_t token, int32_t pos, const StepFilter & f, whisper_token_data & out) {
+bool decode_greedy_step(whisper_context & ctx, int32_t token, int32_t pos, const StepFilter & f, whisper_token_data & out, unsigned * forms) {
     if (!compute_ready(ctx, __func__)) return false;
     State & st = *ctx.state; DeviceState & d = st.dev; const HParams & hp = ctx.model.hp; const Vocab & v = ctx.model.vocab;
     const int64_t t0 = time_us();
@@ -1099,6 +1110,9 @@ bool decode_greedy_step(whisper_context & ctx, int32_t token, int32_t pos, const
     // (WMI_NO_STEP_TICKET=1: off.  The general decode() path — beam search, t > 0 — has host work between its steps: no ticket.)
     static const bool no_ticket = getenv("WMI_NO_STEP_TICKET") != nullptr;
     StepTicket ticket(ctx.device, !no_ticket && !solo, &ctx);
+    if (forms)
+        *forms = (long_kv ? STEP_FORM_LONG_KV : 0u) | (chained ? STEP_FORM_CHAINED : 0u) | (use_graph && exec ? STEP_FORM_GRAPH : 0u) |
+                 (ctx.model.quantised ? STEP_FORM_QUANTISED : greedy_step_forms(ctx, Tc, long_kv, chained, solo));
     if (use_graph && exec) {
         HIP_TRY(hipGraphLaunch(exec, s));
     } else {
@@ -1111,6 +1125,7 @@ bool decode_greedy_step(whisper_context & ctx, int32_t token, int32_t pos, const
         // correct, but the launch's workgroups waited for each other for long: the device is shared with work this process does not
         // count (another process, the embedder's own kernels) — two launches for the next steps, then try again
         d.pair_backoff = 512; ++d.pair_slow_events;
+        if (forms) *forms |= STEP_FORM_SLOW;
         (void) hipMemsetAsync((uint32_t *) d.mlp_arrive + PAIR_FAULT_WORD, 0, sizeof(uint32_t), s);
     }
     if (status & k::SAMPLE_TAG_FAULT) {
@@ -1119,6 +1134,7 @@ bool decode_greedy_step(whisper_context & ctx, int32_t token, int32_t pos, const
         // record rewritten — and the state keeps that form from here on.  (W/whisper.cpp:2517-2595: a decode either succeeds or reports.)
         if (!d.pair_off) WMI_WARN("%s: in-launch hand-off of the MLP failed (status %#x) - step re-run, staying on the two-launch form\n", __func__, (unsigned) status);
         d.pair_off = true; ++d.pair_fallbacks;
+        if (forms) *forms |= STEP_FORM_RERUN;
         if (!HIP_OK(hipMemsetAsync((uint32_t *) d.mlp_arrive + PAIR_FAULT_WORD, 0, sizeof(uint32_t), s))) return false;
         hs->seq = d.step_seq = (d.step_seq + 1) & k::SAMPLE_SEQ_MASK;
         enqueue_greedy_step(ctx, Tc, long_kv, false, false);

@@ -420,7 +420,10 @@ bool decode_layers_q(whisper_context & ctx, int n, int n_kv, int kv_head, int Tc
 void enqueue_greedy_step_q(whisper_context & ctx, int Tc);
 // greedy fast path: decode ONE token of sequence 0 at position `pos` and pick the next token on the device
 struct StepFilter { bool ban_blank, last_ts, penult_ts; int ts_floor_end, ts_initial_start; };
-bool decode_greedy_step(whisper_context & ctx, int32_t token, int32_t pos, const StepFilter & f, whisper_token_data & out);
+// forms: when given, the launch form the step took (STEP_FORM_* bits; the test hook wmi_selftest_greedy_step reports them)
+enum : unsigned { STEP_FORM_LONG_KV = 1, STEP_FORM_CHAINED = 2, STEP_FORM_GRAPH = 4, STEP_FORM_PAIRED = 8, STEP_FORM_FRONTED = 16,
+                  STEP_FORM_BACKED = 32, STEP_FORM_RERUN = 64, STEP_FORM_SLOW = 128, STEP_FORM_QUANTISED = 256 };
+bool decode_greedy_step(whisper_context & ctx, int32_t token, int32_t pos, const StepFilter & f, whisper_token_data & out, unsigned * forms = nullptr);
 bool upload_static_ban(whisper_context & ctx, const whisper_full_params & params);
 // k draws per row from the filtered distribution of logits row `rows[r]` of the last decode() (keep_logits_on_device), r < n_rows <= 8;
 // u [n_rows][k] uniform numbers in [0, 1) from the decoders' generators.  out [n_rows][k].

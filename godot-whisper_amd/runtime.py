@@ -43,6 +43,8 @@ DEVICE_API = [
     ("wmi_sample_draws", C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_int,
                                     C.POINTER(abi.whisper_token_data)]),
     ("wmi_selftest_proj", C.c_double, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    ("wmi_selftest_greedy_step", C.c_int, [C.c_void_p, C.c_int32, C.c_int, C.POINTER(C.c_float), C.POINTER(abi.whisper_token_data),
+                                           C.POINTER(C.c_int)]),
     ("wmi_bench_kernel", C.c_double, [C.c_void_p, C.c_int, C.c_int]),
     ("wmi_reload_knobs", None, []),
     ("wmi_pair_status", C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int]),

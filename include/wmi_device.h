@@ -214,6 +214,18 @@ WHISPER_API int wmi_sample_draws(struct whisper_context * ctx, const float * pro
  * Returns the largest absolute difference over all outputs (negative on error). */
 WHISPER_API double wmi_selftest_proj(struct whisper_context * ctx, int op, int n, int layer);
 
+/* Test hook for the step whisper_full's greedy path runs (temperature 0, one decoder, no callbacks): decodes `token` at position `pos` of
+ * the context's own state with that step, exactly as whisper_full would after two text tokens without timestamps (the default greedy
+ * parameters' filters, the state counted busy).  The cache before `pos` is whatever whisper_decode / earlier steps left there; the step's
+ * slot bookkeeping is whisper_decode's, so both may be mixed.  logits (optional): the step's raw logits, n_vocab floats; out: the token
+ * the device picked (id, tid, p, plog, pt, ptsum); forms (optional): the launch form the step took, a bit set —
+ *   1 cache longer than 64 cells, 2 chained onto the previous step's pick, 4 replayed from a captured graph, 8 both MLP projections as
+ *   one launch, 16 the front of each layer as one launch, 32 the cross-attention back as one launch, 64 re-run after a failed in-launch
+ *   hand-off, 128 a slow hand-off was reported, 256 the block-quantised step.
+ * Returns 0, or a negative value on error. */
+WHISPER_API int wmi_selftest_greedy_step(struct whisper_context * ctx, whisper_token token, int pos, float * logits, whisper_token_data * out,
+                                         int * forms);
+
 /* Host half of wmi_resample on its own (no device needed; CPU-side tests): the frame counts src_simple reports for n_frames
  * mono frames at src_rate -> dst_rate (output capacity int(n_frames * ratio) as the host passes it), and the first n_pos output
  * positions (integer sample, fraction) the kernel would use.  Returns 0, or the converter error as wmi_resample logs it.

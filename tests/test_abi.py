@@ -28,6 +28,7 @@ def test_library_exports_every_declared_symbol():
     assert not missing, missing
     for n in abi.HOST_SYMBOLS:                       # the 11 entry points the Godot host binds
         assert n in names
+    assert "wmi_selftest_greedy_step" in names       # the greedy step's test hook (tests/test_gpu_decode_lengths.py)
 
 
 def test_by_value_struct_layouts():
