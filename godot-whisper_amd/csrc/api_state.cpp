@@ -183,7 +183,6 @@ int whisper_full_parallel(struct whisper_context * ctx, struct whisper_full_para
     {
         std::vector<std::thread> workers;
         struct Joiner { std::vector<std::thread> & t; ~Joiner() { for (auto & x : t) if (x.joinable()) x.join(); } } joiner{workers};
-        static const bool serial = getenv("WMI_PARALLEL_SERIAL") != nullptr;      // debug / A-B: one piece after the other
         for (int i = 0; i < n_processors - 1; ++i) {
             const int start = offset_samples + (i + 1) * per;
             const int n_cur = (i == n_processors - 2) ? n_samples - start : per;
@@ -194,7 +193,7 @@ int whisper_full_parallel(struct whisper_context * ctx, struct whisper_full_para
             cur.progress_callback = nullptr;    cur.progress_callback_user_data = nullptr;
             struct whisper_state * st = states[i];
             auto piece = [ctx, st, cur, samples, start, n_cur]() { (void) whisper_full_with_state(ctx, st, cur, samples + start, n_cur); };   // the reference drops the workers' return codes too
-            if (serial) piece(); else workers.emplace_back(piece);
+            workers.emplace_back(piece);
         }
         auto cur = params;
         cur.print_realtime = false;

@@ -155,14 +155,12 @@ bool encode_rows(whisper_context & ctx, const std::vector<int> & rows, const std
     // conv2 output t of chunk c from conv1 rows c R + 2 t .. + 2 (EPI_CONV2 with rows_per_chunk = R / 2 stores rows t < T at c T + t).
     // The rows conv1 computes across a chunk boundary (c R + 2 T + 1 .. (c + 1) R) are zeroed again before conv2 reads them.
     // Per element the arithmetic is the one-chunk launch's (same operands, same k order).  8 chunks: 32 launches -> 4.
-    // WMI_CONV_PER_CHUNK=1 (A/B): one chunk at a time as before.
-    static const bool conv_per_chunk = getenv("WMI_CONV_PER_CHUNK") != nullptr;
     const int rows_mel = 2 * T + 6;
     for (int r = 0; r < nb; ++r) {
         State & ls = *b.lanes[rows[r]];
         if (ls.mel.n_mel != nm || ls.dev.mel == nullptr) { WMI_ERR("%s: chunk row %d has no mel spectrogram\n", __func__, r); return false; }
     }
-    if (!conv_per_chunk && nb >= 2 && nb <= 16) {
+    if (nb >= 2 && nb <= 16) {
         const int R = 2 * T + 8;
         k::MelSliceBatch mb{};
         for (int r = 0; r < nb; ++r) { State & ls = *b.lanes[rows[r]]; mb.mel[r] = ls.dev.mel; mb.n_len[r] = ls.mel.n_len; mb.offset[r] = seek[r]; }
@@ -216,9 +214,8 @@ bool encode_rows(whisper_context & ctx, const std::vector<int> & rows, const std
     // Rows per chunk of LN1's output, q and k: T rounded up to 16 (1500 -> 1504), so that every 16-row MFMA fragment of the q|k|v GEMM lies
     // inside one chunk at a 16-step offset — its V^T third then leaves in whole 128-byte lines (gemm_epi.h: epilogue_vt_wide) instead of 32-byte
     // pieces (what the launch cost over a plain epilogue: 41 against 29.5 us at 8 chunks).  The padding rows are zero in xn (never written),
-    // finite junk in q / k / V^T (never read as queries or keys: the attention stops at T).  WMI_ENC_NO_ROWPAD=1: off (A/B).
-    static const bool no_rowpad = getenv("WMI_ENC_NO_ROWPAD") != nullptr;
-    const int TP = (nb >= 2 && !no_rowpad && (T & 15) != 0 && ((T + 15) & ~15) <= b.Tpad) ? (T + 15) & ~15 : T;
+    // finite junk in q / k / V^T (never read as queries or keys: the attention stops at T).
+    const int TP = (nb >= 2 && (T & 15) != 0 && ((T + 15) & ~15) <= b.Tpad) ? (T + 15) & ~15 : T;
     const int MP = nb * TP;
     b.qk_rows = TP;
     for (int il = 0; il < La; ++il) {
@@ -517,11 +514,10 @@ double bench_rows_step_chain(whisper_context & ctx, int nb, int iters) {
     hipEvent_t e0, e1;
     if (!HIP_OK(hipEventCreate(&e0)) || !HIP_OK(hipEventCreate(&e1))) return -1.0;
     // replayed from a captured graph like the product's step (eager launches are paced by the host, see bench_greedy_step_chain)
-    static const bool eager = getenv("WMI_CHAIN_EAGER") != nullptr;
     enqueue_rows_step(ctx, nb);
     (void) hipStreamSynchronize(s);
     hipGraph_t pg = nullptr; hipGraphExec_t pexec = nullptr;
-    if (!eager && hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess) {
+    if (hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess) {
         enqueue_rows_step(ctx, nb);
         if (hipStreamEndCapture(s, &pg) != hipSuccess || !pg || hipGraphInstantiate(&pexec, pg, nullptr, nullptr, 0) != hipSuccess) pexec = nullptr;
     }
@@ -632,10 +628,9 @@ int full_batch(whisper_context & ctx, whisper_full_params params, const float * 
         return rc;
     };
 
-    static const bool force_seq = getenv("WMI_BATCH_SEQUENTIAL") != nullptr;     // debug / A-B
     const bool lang_known = params.language && strlen(params.language) > 0 && strcmp(params.language, "auto") != 0 && !params.detect_language;
     const bool distilled = hp.n_text_layer == 2 && !params.no_timestamps;
-    const bool lockstep = !force_seq && fast_path_enabled() && params.strategy == WHISPER_SAMPLING_GREEDY && params.temperature < 1e-6f &&
+    const bool lockstep = params.strategy == WHISPER_SAMPLING_GREEDY && params.temperature < 1e-6f &&
                           lang_known && !distilled && !params.speed_up && !params.logits_filter_callback && !params.grammar_rules && params.n_grammar_rules == 0 && !params.new_segment_callback &&
                           !params.progress_callback && !params.encoder_begin_callback && !params.abort_callback &&
                           ctx.model.n_loaded > 0 && n_chunks > 1;
@@ -651,11 +646,9 @@ int full_batch(whisper_context & ctx, whisper_full_params params, const float * 
         const int rep_want = ctx.batch->replicas_wanted >= 0 ? ctx.batch->replicas_wanted : rep_env;
         const bool observers = params.logits_filter_callback || params.new_segment_callback || params.progress_callback ||
                                params.encoder_begin_callback || params.abort_callback || params.print_realtime;      // (print_progress only writes percent lines to stderr)
-        int n_rep = (!force_seq && !observers && ctx.model.n_loaded > 0) ? std::min(rep_want, n_chunks - 1) : 0;
+        int n_rep = (!observers && ctx.model.n_loaded > 0) ? std::min(rep_want, n_chunks - 1) : 0;
         if (n_rep < 0) n_rep = 0;
         n_rep = ensure_replicas(ctx, n_rep);                             // (out of memory: fewer workers)
-        static const bool dbg_rep = getenv("WMI_DEBUG_TIMING") != nullptr;
-        if (dbg_rep) fprintf(stderr, "[wmi] full_batch: %d chunks through the general driver on 1 + %d contexts (wanted %d, observers %d)\n", n_chunks, n_rep, rep_want, (int) observers);
         if (n_rep == 0) {
             for (int c = 0; c < n_chunks; ++c) { const int rc = run_alone(c); if (rc != 0) return rc; ctx.batch->redo[c] = 1; }
             return 0;
@@ -786,20 +779,18 @@ int full_batch(whisper_context & ctx, whisper_full_params params, const float * 
     for (int g0 = 0; g0 < n_chunks; g0 += group) {
         const int ng = std::min(group, n_chunks - g0);
         std::vector<Row> rows(ng);
-        static const int env_when_ = getenv("WMI_ENVELOPE_WHEN") ? atoi(getenv("WMI_ENVELOPE_WHEN")) : 0;
         // The envelopes of a lock-step call stay in HBM and the window sums + walks of the token timestamps run there (device.cpp
         // ts_refine_device, k_ts_refine: one workgroup per token, the window sum as order-free integer sums per binade over eight wavefronts —
         // every value equals the host loop's, tests/test_gpu_host_dsp.py).  15 MB of PCIe writes per 8-chunk call are not made: mel phase
         // 0.74 -> 0.57 ms, segments + timestamps unchanged at ~0.25 ms (one device call per window for all chunks), 6.14 -> 5.92 ms per call
         // (profiles/r04g_token_timestamps_on_device.txt).  WMI_TS_DEVICE=0: envelopes to pinned host memory, sums and walks on the host.
         static const bool ts_device = !(getenv("WMI_TS_DEVICE") && atoi(getenv("WMI_TS_DEVICE")) == 0);
-        const bool env_interleaved = env_when_ == 0 || env_when_ >= 3;   // each chunk's envelope kernel right behind its mel kernels (3: into HBM, copied out beside the decode steps)
         // ---- per chunk: PCM -> mel, envelope, window bounds (the head of full())
         // The mel kernels of all chunks, and their envelopes where those stay in HBM, are ONE launch per kernel (device.cpp:
         // pcm_to_mel_batch): per chunk on its own stream (3 mel launches + envelope + two event operations, 8 + 8 streams) the phase
         // was ~0.3 ms of host enqueue time per 8-chunk call.  WMI_MEL_PER_CHUNK=1 (A/B): the per-chunk form.
         static const bool mel_per_chunk = getenv("WMI_MEL_PER_CHUNK") != nullptr;
-        const bool env_batched = params.token_timestamps && ts_device && env_when_ == 0;
+        const bool env_batched = params.token_timestamps && ts_device;
         const bool mel_batched = !mel_per_chunk && ng >= 2 && (env_batched || !params.token_timestamps);
         if (mel_batched) {
             const int64_t tm0 = time_us();
@@ -824,27 +815,16 @@ int full_batch(whisper_context & ctx, whisper_full_params params, const float * 
             }
             if (params.token_timestamps) {
                 ls.t_beg = 0; ls.t_last = 0; ls.tid_last = 0;
-                if (!mel_batched && env_interleaved && n_samples[row.chunk] > 0 && !signal_energy_device(ctx, 32, false, (ts_device && env_when_ == 0) ? 3 : env_when_ >= 3 ? 2 : 0)) { WMI_ERR("%s: failed to compute the signal envelope\n", __func__); return -2; }
+                if (!mel_batched && n_samples[row.chunk] > 0 && !signal_energy_device(ctx, 32, false, ts_device ? 3 : 0)) { WMI_ERR("%s: failed to compute the signal envelope\n", __func__); return -2; }
             }
             b.t_mel_us += time_us() - tm0;
         }
-        // The |x| envelopes (token timestamps): 1875 workgroups per chunk whose waves sit on stores into pinned host memory (1.9 MB per
-        // chunk over PCIe).  WMI_ENVELOPE_WHEN (A/B): 0 = behind each chunk's mel kernels (default), 1 = behind the mel kernels of all
-        // chunks (beside the encoder), 2 = behind the first window's encoder (beside the decode steps).  Measured (profiles/
-        // r04b_envelope_placement.txt): they cost 0.3-0.4 ms of the 8-chunk call WHEREVER they run — mel phase 0.60 -> 0.24 ms with 1 or 2,
-        // and the encoder (its persistent GEMMs want every CU at once) or the decode steps (their 32-byte results queue behind 15 MB of
-        // bulk writes) give the same time back; the copy-engine form (WMI_ENVELOPE_DMA) is a blit kernel on this stack (rocprof:
-        // __amd_rocclr_copyBuffer, no SDMA), a thin grid (WMI_ENVELOPE_GRID) starves the kernel's 65-deep f64 chains.
-        static const int env_dma = getenv("WMI_ENVELOPE_DMA") ? std::max(1, atoi(getenv("WMI_ENVELOPE_DMA"))) : 0;
-        auto envelopes = [&]() -> bool {
-            if (!params.token_timestamps) return true;
-            for (int r = 0; r < ng; ++r) {
-                State & ls = *b.lanes[r];
-                StateSwap sw(ctx, &ls);
-                if (n_samples[g0 + r] > 0 && !signal_energy_device(ctx, 32, false, env_dma)) { WMI_ERR("%s: failed to compute the signal envelope\n", __func__); return false; }
-            }
-            return true;
-        };
+        // The |x| envelopes (token timestamps) run behind each chunk's mel kernels.  Measured where they go to pinned host memory (profiles/
+        // r04b_envelope_placement.txt): they cost 0.3-0.4 ms of the 8-chunk call WHEREVER they run — behind the mel kernels of all chunks
+        // (beside the encoder) or behind the first window's encoder (beside the decode steps) took mel phase 0.60 -> 0.24 ms, and the encoder
+        // (its persistent GEMMs want every CU at once) or the decode steps (their 32-byte results queue behind 15 MB of bulk writes) gave the
+        // same time back; the copy-engine form is a blit kernel on this stack (rocprof: __amd_rocclr_copyBuffer, no SDMA), a thin grid
+        // starves the kernel's 65-deep f64 chains.
         // one synchronisation for the mel kernels of all chunks (keeps the mel / encoder time buckets separate); the
         // envelopes are written to the host by the chunks' side streams and are awaited at emission time
         {
@@ -857,12 +837,6 @@ int full_batch(whisper_context & ctx, whisper_full_params params, const float * 
             if (!HIP_OK(hipStreamSynchronize(primary->dev.stream))) return -2;
             b.t_mel_us += time_us() - tm0;
         }
-        bool env_done = env_interleaved || !params.token_timestamps, env_flushed = false;
-        if (env_when_ == 4 && params.token_timestamps) {        // thin copies beside the encoder
-            for (int r = 0; r < ng; ++r) if (!signal_energy_flush(*b.lanes[r])) return -2;
-            env_flushed = true;
-        }
-        if (!env_done && env_when_ == 1) { if (!envelopes()) return -2; env_done = true; }
         for (int r = 0; r < ng; ++r) {
             Row & row = rows[r]; State & ls = *b.lanes[r];
             row.seek_start = params.offset_ms / 10;
@@ -883,11 +857,6 @@ int full_batch(whisper_context & ctx, whisper_full_params params, const float * 
                 std::vector<int> lanes(nb), seeks(nb);
                 for (int r = 0; r < nb; ++r) { lanes[r] = rows[act[r]].lane; seeks[r] = rows[act[r]].seek; }
                 if (!encode_rows(ctx, lanes, seeks, params.audio_ctx)) { WMI_ERR("%s: failed to encode\n", __func__); return -6; }
-                if (!env_done) { if (!envelopes()) return -2; env_done = true; }
-                if (env_when_ == 3 && !env_flushed) {            // the thin copies start now: beside the decode steps, done long before emission
-                    for (int r = 0; r < ng; ++r) if (!signal_energy_flush(*b.lanes[r])) return -2;
-                    env_flushed = true;
-                }
                 b.chain_valid = false;                             // new windows, possibly other chunks in the rows: every row restarts at cell 0
             }
             for (int r = 0; r < nb; ++r) {
@@ -1035,9 +1004,6 @@ int full_batch(whisper_context & ctx, whisper_full_params params, const float * 
             }
         }
     }
-    static const bool dbg_t = getenv("WMI_DEBUG_TIMING") != nullptr;
-    if (dbg_t) fprintf(stderr, "[wmi] full_batch: %d chunks | mel+envelope %.3f ms | encode %.3f | decode %.3f (%d steps, %d chained) | segments+timestamps %.3f\n",
-                       n_chunks, b.t_mel_us / 1e3, b.t_encode_us / 1e3, b.t_decode_us / 1e3, b.n_steps, b.n_chained, b.t_emit_us / 1e3);
     return 0;
 }
 

@@ -106,7 +106,7 @@ static bool init_state_into(whisper_context & ctx, State * st, bool replica_stat
     // replicas) take 18 ms per large-v3 chunk when all four launch on queues the process made early, and 40 ms — hardly better than one after
     // the other — when the calling context's stream was an ordinary one created after an earlier context had run lock-step batches (sixteen
     // more ordinary streams).  One chunk alone measures the same on either kind of stream.  WMI_POOLED_MAIN_STREAM=1: the ordinary kind.
-    static const bool pooled = getenv("WMI_POOLED_MAIN_STREAM") != nullptr || getenv("WMI_REPLICA_POOLED_QUEUES") != nullptr;
+    static const bool pooled = getenv("WMI_POOLED_MAIN_STREAM") != nullptr;
     if (adopt) { d.stream = adopt; d.stream_own_queue = true; }
     else if (!pooled && (d.stream = own_queue_stream_get(ctx.device))) d.stream_own_queue = true;
     else HIP_TRY(hipStreamCreateWithFlags(&d.stream, hipStreamNonBlocking));
@@ -213,7 +213,6 @@ void destroy_state(State * st) {
     if (d.step_dev) (void) hipFree(d.step_dev);
     if (d.sample_dev) (void) hipFree(d.sample_dev);
     if (d.filter_scratch) (void) hipFree(d.filter_scratch);
-    if (d.draw_dev) (void) hipFree(d.draw_dev);
     if (d.draw_scratch) (void) hipFree(d.draw_scratch);
     if (d.draw_host) (void) hipHostFree(d.draw_host);
     if (d.step_host) (void) hipHostFree(d.step_host);
@@ -343,7 +342,7 @@ bool pcm_to_mel_batch(whisper_context & ctx, const std::vector<State *> & states
         HIP_TRY(hipEventRecord(pd.mel_ev, pd.copy_stream));
         for (State * st : in) {
             DeviceState & d = st->dev;
-            d.energy_device_only = true; d.energy_unflushed = false; d.energy_pending = true; d.energy_wait_stream = pd.copy_stream;
+            d.energy_device_only = true; d.energy_pending = true; d.energy_wait_stream = pd.copy_stream;
         }
     }
     k::mel_batch(mb, nb, n_mel, ctx.w.mel_filters, ctx.w.mel_ranges, ctx.w.mel_taps, s);
@@ -374,41 +373,19 @@ bool signal_energy_device(whisper_context & ctx, int hw, bool sync, int via_dma)
     HIP_TRY(hipStreamWaitEvent(d.copy_stream, d.energy_ev, 0));
     {
         const size_t nb = (size_t) n / 256 + 2;
-        // via_dma (several chunks per call): the kernel writes a device buffer (~10 us) and the copy engine moves it to the pinned image —
-        // as stores from the kernel, 8 x 1875 workgroups sat on PCIe writes in the CUs' wave slots for 0.25-0.35 ms beside the mel kernels
-        // or the encoder, whichever they were queued next to.  One chunk: the direct stores (no copy call on the host's critical path).
+        // via_dma = 3 (several chunks per call): the kernel writes a device buffer (~10 us) that the timestamp walks read in place — as
+        // stores to pinned host memory, 8 x 1875 workgroups sat on PCIe writes in the CUs' wave slots for 0.25-0.35 ms beside the mel
+        // kernels or the encoder, whichever they were queued next to.  One chunk: the direct stores (no copy call on the host's critical path).
         const size_t need = d.energy_cap + 2 * nb;
         if (via_dma && d.energy_dev_cap < need) { dfree(d.energy); d.energy_dev_cap = 0; if (dalloc(d.energy, need)) d.energy_dev_cap = need; else via_dma = 0; }
         if (via_dma == 3) {
             k::signal_energy(d.last_pcm, n, hw, d.energy, d.energy + d.energy_cap, d.energy + d.energy_cap + nb, d.copy_stream);
-            d.energy_device_only = true; d.energy_unflushed = false;
-        } else
-        if (via_dma == 2) {
-            // the kernel runs now, into HBM (~10 us); the copy to the pinned image is signal_energy_flush()'s thin kernel, later
-            k::signal_energy(d.last_pcm, n, hw, d.energy, d.energy + d.energy_cap, d.energy + d.energy_cap + nb, d.copy_stream);
-            d.energy_unflushed = true;
-        } else
-        if (via_dma) {
-            k::signal_energy(d.last_pcm, n, hw, d.energy, d.energy + d.energy_cap, d.energy + d.energy_cap + nb, d.copy_stream);
-            HIP_TRY(hipMemcpyAsync(d.energy_host, d.energy, (size_t) n * 4, hipMemcpyDeviceToHost, d.copy_stream));
-            HIP_TRY(hipMemcpyAsync(d.energy_host + d.energy_cap, d.energy + d.energy_cap, 2 * nb * 4, hipMemcpyDeviceToHost, d.copy_stream));
+            d.energy_device_only = true;
         } else
         k::signal_energy(d.last_pcm, n, hw, d.energy_host, d.energy_host + d.energy_cap, d.energy_host + d.energy_cap + nb, d.copy_stream);
     }
     d.energy_pending = true;
     return sync ? signal_energy_wait(st) : true;
-}
-
-bool signal_energy_flush(State & st) {
-    DeviceState & d = st.dev;
-    if (!d.energy_pending || !d.energy_unflushed) return true;
-    static const int wgs = getenv("WMI_ENVELOPE_COPY_WGS") ? atoi(getenv("WMI_ENVELOPE_COPY_WGS")) : 2;
-    const size_t nb = (size_t) d.last_pcm_n / 256 + 2;
-    // envelope [n] and the block extrema behind energy_cap: the pinned image has the device buffer's layout
-    k::copy_thin(d.energy, d.energy_host, (size_t) d.last_pcm_n * 4, wgs, d.copy_stream);
-    k::copy_thin(d.energy + d.energy_cap, d.energy_host + d.energy_cap, 2 * nb * 4, 1, d.copy_stream);
-    d.energy_unflushed = false;
-    return hipGetLastError() == hipSuccess;
 }
 
 bool ts_refine_device(State & st, const k::TsTok * in, int n, k::TsOut * out) {
@@ -438,7 +415,6 @@ bool signal_energy_wait(State & st) {
         return true;
     }
     st.energy_on_device = false;
-    if (d.energy_unflushed && !signal_energy_flush(st)) return false;
     HIP_TRY(hipStreamSynchronize(d.copy_stream));
     st.energy = d.energy_host; st.energy_n = d.last_pcm_n;
     st.energy_bmin = d.energy_host + d.energy_cap; st.energy_bmax = st.energy_bmin + ((size_t) d.last_pcm_n / 256 + 2);
@@ -552,8 +528,6 @@ bool encode(whisper_context & ctx, int mel_offset, bool defer) {
     return true;
 }
 
-static int stamps_reduce(whisper_context & ctx, const unsigned long long * buf, int n, double * out, int cap);
-
 // ------------------------------------------------------------------------------------------------ decoder
 bool decode(whisper_context & ctx, const Batch & batch) {
     if (!compute_ready(ctx, __func__)) return false;
@@ -585,49 +559,14 @@ bool decode(whisper_context & ctx, const Batch & batch) {
     }
     // (the device block has the pinned block's layout for THIS n: tokens | positions | rows | mask, packed)
     d.d_pos = d.d_tokens + n; d.d_rows = d.d_pos + n; d.d_mask = (float *) (d.d_rows + n);
-    // WMI_DECODE_TRACE=1 (debug): GPU time between the first and the last command of the call (events) beside the host's wall time
-    static const bool trace = getenv("WMI_DECODE_TRACE") != nullptr;
-    static thread_local hipEvent_t tr0 = nullptr, tr1 = nullptr;      // (probe state per thread: states of one context decode concurrently)
-    if (trace) { if (!tr0) { (void) hipEventCreate(&tr0); (void) hipEventCreate(&tr1); } (void) hipEventRecord(tr0, s); }
     HIP_TRY(hipMemcpyAsync(d.d_tokens, p_tok, ((size_t) 3 * n + (size_t) n * n_kv) * 4, hipMemcpyHostToDevice, s));
 
     if (ctx.model.quantised) {
-        // WMI_DECODE_STAMPS=k (debug): in-kernel stamps of the k-th several-row call's launches (start, body, the kernels' two mid marks)
-        static const int stamp_call = getenv("WMI_DECODE_STAMPS") ? atoi(getenv("WMI_DECODE_STAMPS")) : -1;
-        static thread_local int n_multi = 0;
-        unsigned long long * sbuf = nullptr; constexpr int SMAXL = 512;
-        if (stamp_call >= 0 && n > 1 && n_multi++ == stamp_call) {
-            const size_t bytes = (size_t) SMAXL * k::STAMP_WAVES * 4 * sizeof(unsigned long long);
-            if (HIP_OK(hipMalloc((void **) &sbuf, bytes))) { (void) hipMemsetAsync(sbuf, 0, bytes, s); k::stamp_enable(sbuf); }
-        }
-        const bool layers_ok = decode_layers_q(ctx, n, n_kv, kv_head, Tc, rows);
-        if (sbuf) {
-            const int nl = std::min(k::stamp_count(), SMAXL);
-            k::stamp_enable(nullptr);
-            (void) hipStreamSynchronize(s);
-            std::vector<double> o((size_t) 6 * nl);
-            const int got = stamps_reduce(ctx, sbuf, nl, o.data(), nl);
-            for (int i = 0; i < got; ++i)
-                if (o[6 * i + 3] > 0)
-                    fprintf(stderr, "[wmi] stamps n=%d launch %3d: start %8.2f  last-start +%5.2f  body %5.2f  waves %4d  mark1 +%6.2f  mark2 +%6.2f  gap-before %5.2f\n", n, i,
-                            o[6 * i], o[6 * i + 1] - o[6 * i], o[6 * i + 2] - o[6 * i], (int) o[6 * i + 3], o[6 * i + 4] > 0 ? o[6 * i + 4] - o[6 * i] : -1.0,
-                            o[6 * i + 5] > 0 ? o[6 * i + 5] - o[6 * i] : -1.0, i ? o[6 * i] - o[6 * (i - 1) + 2] : 0.0);
-            (void) hipFree(sbuf);
-        }
-        if (!layers_ok) return false;
-        const int64_t t_enq = time_us();
-        if (trace) (void) hipEventRecord(tr1, s);
+        if (!decode_layers_q(ctx, n, n_kv, kv_head, Tc, rows)) return false;
         HIP_TRY(hipStreamSynchronize(s));
         if (!HIP_OK(hipGetLastError())) return false;
         int64_t dtq = time_us() - t0;
         { const int64_t done = phase_settle(st, false); if (done > t0) dtq = std::max<int64_t>(0, dtq - (done - t0)); }
-        if (trace) {
-            static thread_local int64_t t_prev_end = 0;
-            float ms = 0.f; (void) hipEventElapsedTime(&ms, tr0, tr1);
-            fprintf(stderr, "[wmi] decode n=%d n_kv=%d: wall %.0f us (enqueue done at %.0f) | first-to-last command on the GPU %.0f us | since the previous call returned %.0f us\n",
-                    n, n_kv, (double) dtq, (double) (t_enq - t0), ms * 1e3, t_prev_end ? (double) (t0 - t_prev_end) : 0.0);
-            t_prev_end = time_us();
-        }
         if (n == 1)      { st.t_decode_us += dtq; st.n_decode++; }
         else if (n < 16) { st.t_batchd_us += dtq; st.n_batchd += n; }
         else             { st.t_prompt_us += dtq; st.n_prompt += n; }
@@ -635,18 +574,13 @@ bool decode(whisper_context & ctx, const Batch & batch) {
     }
     k::dec_embed(d.d_tokens, d.d_pos, n, S, w.d_te, w.d_pe, d.dx, s);
     const float kq_scale = powf((float) S / H, -0.25f);
-    // WMI_DECODE_PATH=gemm|gemv forces one projection path (debug / A-B measurements); default: by batch size
-    static const char * force_path = getenv("WMI_DECODE_PATH");
-    static const int gemm_mask = getenv("WMI_GEMM_MASK") ? atoi(getenv("WMI_GEMM_MASK")) : 0;   // per-op override (debug)
-    const bool skinny_default = (force_path && !strcmp(force_path, "gemm")) ? false : n <= 8;
 
     // generic projection: y = W . LN?(x) with a fused epilogue, through the weight-streaming kernel
     // (n <= 8) or the MFMA GEMM (prompt / initial_prompt batches)
-    auto proj = [&](int op, int epi, const float * ln_g, const float * ln_b, const __half * a16, int K, int N, const __half * W,
+    auto proj = [&](int epi, const float * ln_g, const float * ln_b, const __half * a16, int K, int N, const __half * W,
                     const float * bias, void * C, int ldc, const float * resid, void * aux, int ldaux, void * aux2,
                     int ldaux2, float scale) {
-        const bool skinny = n <= 8 && (skinny_default ? !((gemm_mask >> op) & 1) : false);
-        if (skinny) {
+        if (n <= 8) {
             k::GemvArgs g{};
             g.x32 = d.dx; g.ln_g = ln_g; g.ln_b = ln_b; g.eps = hp.eps; g.a16 = a16; g.n = n; g.K = K; g.N = N; g.W = W;
             g.bias = bias; g.epi = epi; g.C = C; g.ldc = ldc; g.resid = resid; g.ldr = S; g.aux = aux; g.ldaux = ldaux;
@@ -666,19 +600,17 @@ bool decode(whisper_context & ctx, const Batch & batch) {
         const DecLayerW & l = w.dec[il];
         __half * ck = kv.k + ((size_t) il * n_ctx) * S, * cv = kv.v + ((size_t) il * n_ctx) * S;
         // self-attention: q | k -> cache | v -> cache  (W/whisper.cpp:2248-2290)
-        proj(0, k::EPI_QKV_DEC, l.ln1_g, l.ln1_b, nullptr, S, 3 * S, l.w_qkv, l.b_qkv, d.dq, S, nullptr,
+        proj(k::EPI_QKV_DEC, l.ln1_g, l.ln1_b, nullptr, S, 3 * S, l.w_qkv, l.b_qkv, d.dq, S, nullptr,
              ck + (size_t) kv_head * S, S, cv + (size_t) kv_head * S, S, kq_scale);
         k::attn_decoder(d.dq, n, S, H, ck, cv, n_kv, d.d_mask, n_kv, d.datt, s);
-        proj(1, k::EPI_F32_BIAS_RESID, nullptr, nullptr, d.datt, S, S, l.w_o, l.b_o, d.dx, S, d.dx, nullptr, 0, nullptr, 0, 0.f);
+        proj(k::EPI_F32_BIAS_RESID, nullptr, nullptr, d.datt, S, S, l.w_o, l.b_o, d.dx, S, d.dx, nullptr, 0, nullptr, 0, 0.f);
         // cross-attention against the encoder K/V of this layer, no mask (W/whisper.cpp:2359-2433)
-        proj(2, k::EPI_Q_SCALED, l.ln2_g, l.ln2_b, nullptr, S, S, l.w_cq, l.b_cq, d.dq, S, nullptr, nullptr, 0, nullptr, 0, kq_scale);
-        static const bool xattn_single = getenv("WMI_XATTN_SINGLE") != nullptr;     // debug: one workgroup per (token, head)
-        if (xattn_single) k::attn_decoder(d.dq, n, S, H, d.kvc_k + (size_t) il * Tc * S, d.kvc_v + (size_t) il * Tc * S, Tc, nullptr, 0, d.datt, s);
-        else k::attn_cross_split(d.dq, n, S, H, d.kvc_k + (size_t) il * Tc * S, d.kvc_v + (size_t) il * Tc * S, Tc, d.xattn, d.datt, s);
-        proj(3, k::EPI_F32_BIAS_RESID, nullptr, nullptr, d.datt, S, S, l.w_co, l.b_co, d.dx, S, d.dx, nullptr, 0, nullptr, 0, 0.f);
+        proj(k::EPI_Q_SCALED, l.ln2_g, l.ln2_b, nullptr, S, S, l.w_cq, l.b_cq, d.dq, S, nullptr, nullptr, 0, nullptr, 0, kq_scale);
+        k::attn_cross_split(d.dq, n, S, H, d.kvc_k + (size_t) il * Tc * S, d.kvc_v + (size_t) il * Tc * S, Tc, d.xattn, d.datt, s);
+        proj(k::EPI_F32_BIAS_RESID, nullptr, nullptr, d.datt, S, S, l.w_co, l.b_co, d.dx, S, d.dx, nullptr, 0, nullptr, 0, 0.f);
         // MLP
-        proj(4, k::EPI_F16_BIAS_GELU, l.ln3_g, l.ln3_b, nullptr, S, 4 * S, l.w_fc1, l.b_fc1, d.dh, 4 * S, nullptr, nullptr, 0, nullptr, 0, 0.f);
-        proj(5, k::EPI_F32_BIAS_RESID, nullptr, nullptr, d.dh, 4 * S, S, l.w_fc2, l.b_fc2, d.dx, S, d.dx, nullptr, 0, nullptr, 0, 0.f);
+        proj(k::EPI_F16_BIAS_GELU, l.ln3_g, l.ln3_b, nullptr, S, 4 * S, l.w_fc1, l.b_fc1, d.dh, 4 * S, nullptr, nullptr, 0, nullptr, 0, 0.f);
+        proj(k::EPI_F32_BIAS_RESID, nullptr, nullptr, d.dh, 4 * S, S, l.w_fc2, l.b_fc2, d.dx, S, d.dx, nullptr, 0, nullptr, 0, 0.f);
     }
 
     // final LN + logits = d_te . x for the rows that asked for them (the reference computes all rows
@@ -711,11 +643,6 @@ bool decode(whisper_context & ctx, const Batch & batch) {
 
 // ------------------------------------------------------------------------------------------------ greedy fast path
 namespace wmi {
-
-bool fast_path_enabled() {
-    static const bool off = getenv("WMI_HOST_SAMPLING") != nullptr;      // debug / A-B: force the host filter + sampling path
-    return !off;
-}
 
 // static part of the logit filters (W/whisper.cpp:4541-4593): one byte per vocabulary entry, rebuilt only when
 // the parameters that feed it change
@@ -787,8 +714,8 @@ bool sample_rows_device(whisper_context & ctx, const StepFilter * f, const int *
     if (n_rows < 1 || n_rows > 8 || k < 1 || k > 8) return false;
     const int64_t t0 = time_us();
     constexpr size_t OFF_U = 8 * sizeof(k::DecStep), OFF_OUT = OFF_U + 64 * sizeof(double), TOTAL = OFF_OUT + 64 * sizeof(k::SampleOut);
-    if (!d.draw_dev) {
-        if (!HIP_OK(hipMalloc(&d.draw_dev, TOTAL)) || !HIP_OK(hipHostMalloc(&d.draw_host, TOTAL, hipHostMallocDefault)) ||
+    if (!d.draw_host) {
+        if (!HIP_OK(hipHostMalloc(&d.draw_host, TOTAL, hipHostMallocDefault)) ||
             !HIP_OK(hipMalloc(&d.draw_scratch, k::filter_draw_scratch_bytes(8)))) return false;
     }
     hipStream_t s = d.stream;
@@ -804,10 +731,8 @@ bool sample_rows_device(whisper_context & ctx, const StepFilter * f, const int *
         for (int c = 0; c < k; ++c) hu[r * k + c] = u[r * k + c];
     }
     // The kernels read the step records and the uniform numbers straight from the pinned block and write their results into it: two small
-    // copies fewer per sampled step (WMI_DRAW_STAGED=1: through the device block, as before)
-    static const bool staged = getenv("WMI_DRAW_STAGED") != nullptr;
-    if (staged) HIP_TRY(hipMemcpyAsync(d.draw_dev, d.draw_host, OFF_OUT, hipMemcpyHostToDevice, s));
-    void * const blk = staged ? d.draw_dev : d.draw_host;
+    // copies fewer per sampled step
+    void * const blk = d.draw_host;
     const k::DecStep * ds = (const k::DecStep *) blk; const double * du = (const double *) ((char *) blk + OFF_U);
     k::SampleOut * dout = (k::SampleOut *) ((char *) blk + OFF_OUT);
     // rows that sit next to each other in d.logits go in one launch; the first step of a window draws every decoder from row 0
@@ -817,7 +742,6 @@ bool sample_rows_device(whisper_context & ctx, const StepFilter * f, const int *
     else for (int r = 0; r < n_rows; ++r)
         k::filter_draw(d.logits + (size_t) rows[r] * NV, d.ban_dev, ds + r, du + r * k, k, dout + r * k, d.draw_scratch, s, 1, tid_default);
     k::SampleOut * hout = (k::SampleOut *) ((char *) d.draw_host + OFF_OUT);
-    if (staged) HIP_TRY(hipMemcpyAsync(hout, dout, (size_t) n_rows * k * sizeof(k::SampleOut), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     for (int i = 0; i < n_rows * k; ++i)
         out[i] = whisper_token_data{ hout[i].id, hout[i].tid, hout[i].p, hout[i].plog, hout[i].pt, hout[i].ptsum, -1, -1, 0.0f };
@@ -957,7 +881,6 @@ static void enqueue_greedy_step(whisper_context & ctx, int Tc, bool long_kv = fa
         }
         }
         {   // LN2 + cross query folded into the score kernel; partials combined inside the out-projection's prologue
-            static const bool unfused_q = getenv("WMI_XATTN_UNFUSED_Q") != nullptr;          // debug / A-B
             const float * po = nullptr, * pl = nullptr, * pm = nullptr; int ns = 0;
             if (!(M & 8)) { k::attn_cross_partials_layout(1, H, Tc, d.xattn, &po, &pl, &pm, &ns); }
             else if (backed) {   // LN + cross query + key slices, the combine (once per head) and the out projection as ONE launch (k::xback)
@@ -970,7 +893,7 @@ static void enqueue_greedy_step(whisper_context & ctx, int Tc, bool long_kv = fa
                 k::xback(xb, H, d.xattn, s); chk("cross-attn + out", il);
                 goto mlp;
             }
-            else if (unfused_q || S > 1536) {                  // the fused kernel keeps a whole row per wavefront in registers: S <= 1536
+            else if (S > 1536) {                  // the fused kernel keeps a whole row per wavefront in registers: S <= 1536
                 gv(k::EPI_Q_SCALED, l.ln2_g, l.ln2_b, nullptr, S, S, l.w_cq, l.b_cq, d.dq, S, nullptr, nullptr, nullptr, kq_scale, nullptr);
                 k::attn_cross_split_partials(d.dq, 1, S, H, d.kvc_k + (size_t) il * Tc * S, d.kvc_v + (size_t) il * Tc * S, Tc, d.xattn, &po, &pl, &pm, &ns, s);
             } else
@@ -1176,20 +1099,14 @@ double bench_greedy_step_chain(whisper_context & ctx, int iters) {
     // The chain is ALWAYS replayed from a captured graph, also for a masked subset of the step's kernels: eager launches are
     // paced by the host (2.7 us per trivial launch on this stack against 1.63 us for the same chain replayed from a graph,
     // scratch/lab/chain_lab.hip), which is what round 2's per-kind table had measured for every kernel under ~4 us.
-    // WMI_CHAIN_EAGER=1 keeps the host-paced form for comparison.
-    static const bool eager = getenv("WMI_CHAIN_EAGER") != nullptr;
     hipGraph_t pg = nullptr; hipGraphExec_t pexec = nullptr;
     enqueue_greedy_step(ctx, Tc, long_kv);                      // function attributes, lazy allocations: outside the capture
     (void) hipStreamSynchronize(s);
-    // WMI_CHAIN_REPS = r: r copies of the (masked) step inside ONE graph — a replay of a handful of kernels is bounded by the
-    // replay's own fixed cost, not by the kernels (a per-kind chain of 6 launches is such a graph)
-    const int reps = getenv("WMI_CHAIN_REPS") ? std::max(1, atoi(getenv("WMI_CHAIN_REPS"))) : 1;
-    if (!eager && hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-        for (int r = 0; r < reps; ++r) enqueue_greedy_step(ctx, Tc, long_kv);
+    if (hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess) {
+        enqueue_greedy_step(ctx, Tc, long_kv);
         if (hipStreamEndCapture(s, &pg) != hipSuccess || !pg || hipGraphInstantiate(&pexec, pg, nullptr, nullptr, 0) != hipSuccess) pexec = nullptr;
     }
     auto once = [&]() { if (pexec) (void) hipGraphLaunch(pexec, s); else enqueue_greedy_step(ctx, Tc, long_kv); };
-    if (reps > 1) iters = (iters + reps - 1) / reps;
     for (int i = 0; i < 4; ++i) once();
     (void) hipStreamSynchronize(s);
     (void) hipEventRecord(e0, s);
@@ -1200,7 +1117,7 @@ double bench_greedy_step_chain(whisper_context & ctx, int iters) {
     if (pexec) (void) hipGraphExecDestroy(pexec);
     if (pg) (void) hipGraphDestroy(pg);
     (void) hipEventDestroy(e0); (void) hipEventDestroy(e1);
-    return (double) ms * 1000.0 / (iters * (pexec ? reps : 1));
+    return (double) ms * 1000.0 / iters;
 }
 
 // reduces the stamp records of n launches (kernels.h: Stamp) to out[6 i + 0..5] — see step_stamps

@@ -36,10 +36,7 @@ bool rows_fit(int n, int K) {
 // mlp.2 of the decoder with K split over two workgroups per row group (kernels.h GemvArgs::ksplit; WMI_Q_KSPLIT=0: off, A/B)
 bool fc2_ksplit(k::GemvArgs & g, float * kpart) {
     static const bool off = getenv("WMI_Q_KSPLIT") && atoi(getenv("WMI_Q_KSPLIT")) == 0;
-    static const bool dbg = getenv("WMI_DEBUG_KSPLIT") != nullptr;
-    const bool ok = !off && kpart && k::qrows_ksplit_ok(g, 2);
-    if (dbg) fprintf(stderr, "[wmi] mlp.2 K split: %s (n %d K %d N %d a16 %p epi %d)\n", ok ? "yes" : "no", g.n, g.K, g.N, (const void *) g.a16, g.epi);
-    if (!ok) return false;
+    if (off || !kpart || !k::qrows_ksplit_ok(g, 2)) return false;
     g.ksplit = 2; g.kpart = kpart;
     static const bool drop = getenv("WMI_DEBUG_KSPLIT_DROP") != nullptr;      // debug: the consumers ignore the pending half (results must change)
     return !drop;
@@ -121,9 +118,8 @@ bool decode_layers_q(whisper_context & ctx, int n, int n_kv, int kv_head, int Tc
 
     // y = W . q8(src) with a fused epilogue: <= 32 rows stream the weight tiles once (rows quantised in the kernel's prologue);
     // prompt-sized batches quantise once and go through the tiled GEMM
-    static const bool no_pf = getenv("WMI_NO_PREFETCH") != nullptr;            // A/B knob
     const k::QMat * pfW = nullptr; int pfN = 0, pfK = 0;                       // the next weight-streaming launch's matrix (k_qrows prefetch)
-    auto next = [&](const k::QMat & W, int N, int K) { pfW = no_pf ? nullptr : &W; pfN = N; pfK = K; };
+    auto next = [&](const k::QMat & W, int N, int K) { pfW = &W; pfN = N; pfK = K; };
     auto set_pf = [&](k::GemvArgs & g) {
         if (pfW && pfW->tiles && pfN <= 8192) {
             g.pf_ptr = pfW->tiles; g.pf_group_bytes = (uint32_t) ((size_t) (pfK / 64) * k::q_tile_bytes(pfW->qtype)); g.pf_groups = (uint32_t) ((pfN + 31) / 32);
@@ -224,9 +220,8 @@ void enqueue_greedy_step_q(whisper_context & ctx, int Tc) {
     const float kq_scale = powf((float) S / H, -0.25f);
     k::qdec_embed_step((const k::DecStep *) d.step_host, (k::DecStep *) d.step_dev, S, w.q_te, w.d_pe, d.dx, s);
     // pfW / pfN / pfK: the matrix of the next weight-streaming launch of the chain, prefetched by this one (k_qrows)
-    static const bool no_pf = getenv("WMI_NO_PREFETCH") != nullptr;            // A/B knob
     const k::QMat * pfW = nullptr; int pfN = 0, pfK = 0;
-    auto next = [&](const k::QMat & W, int N, int K) { pfW = no_pf ? nullptr : &W; pfN = N; pfK = K; };
+    auto next = [&](const k::QMat & W, int N, int K) { pfW = &W; pfN = N; pfK = K; };
     const float * pend = nullptr;                             // see decode_layers_q
     auto rows = [&](int epi, const Src & src, int K, int N, const k::QMat & W, const float * bias, void * C, int ldc, const float * resid,
                     void * aux, void * aux2, float scale, const int32_t * row_off, const float * co = nullptr, const float * cl = nullptr, int cns = 0, const float * cm = nullptr) {
@@ -242,16 +237,6 @@ void enqueue_greedy_step_q(whisper_context & ctx, int Tc) {
         if (resid && !co && !src.x16) pend = nullptr;                        // the self-attention's out projection writes the row whole again
         if (src.x16 && epi == k::EPI_F32_BIAS_RESID && fc2_ksplit(g, d.xattn)) pend = d.xattn;      // mlp.2
         k::qrows(g, src.ln_g ? nullptr : src.x32, W, s);
-#ifdef WMI_QROWS_PROBE
-        // (probe build, WMI_Q_DOUBLE=1) the same launch once more on the NEXT layer's matrix of the same kind: cold weights, warm
-        // instruction cache — what of a launch's body is instruction fetch?  (results are garbage: timing only)
-        static const bool dbl = getenv("WMI_Q_DOUBLE") != nullptr;
-        if (dbl && &W >= (const k::QMat *) &w.dec[0] && &W < (const k::QMat *) &w.dec[Lt - 1]) {
-            const k::QMat & W2 = *(const k::QMat *) ((const char *) &W + sizeof(DecLayerW));
-            k::GemvArgs g2 = g; g2.pf_ptr = nullptr;
-            k::qrows(g2, src.ln_g ? nullptr : src.x32, W2, s);
-        }
-#endif
     };
     for (int il = 0; il < Lt; ++il) {
         const DecLayerW & l = w.dec[il];
@@ -299,9 +284,8 @@ void enqueue_rows_step_q(whisper_context & ctx, int nb) {
     const int64_t cache_stride = (int64_t) Lt * n_ctx * S;
     const int64_t cross_layer = (int64_t) b.enc_rows * Tc * S;
     k::qdec_embed_step((const k::DecStep *) b.step_host, (k::DecStep *) b.step_dev, S, w.q_te, w.d_pe, b.dx, s, nb);
-    static const bool no_pf = getenv("WMI_NO_PREFETCH") != nullptr;            // A/B knob
     const k::QMat * pfW = nullptr; int pfN = 0, pfK = 0;                       // the next weight-streaming launch's matrix (k_qrows prefetch)
-    auto next = [&](const k::QMat & W, int N, int K) { pfW = no_pf ? nullptr : &W; pfN = N; pfK = K; };
+    auto next = [&](const k::QMat & W, int N, int K) { pfW = &W; pfN = N; pfK = K; };
     const float * pend = nullptr;                             // see decode_layers_q
     auto rows = [&](int epi, const Src & src, int K, int N, const k::QMat & W, const float * bias, void * C, int ldc, const float * resid,
                     void * aux, void * aux2, float scale, const int32_t * row_off) {

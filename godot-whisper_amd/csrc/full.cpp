@@ -46,12 +46,8 @@ void emit_segment(whisper_context & ctx, State & st, const whisper_full_params &
     st.result_all.push_back(std::move(seg));
     int n_new = 1;
     if (params.token_timestamps) {
-        static const bool dbg_e = getenv("WMI_DEBUG_EMIT") != nullptr;
-        const int64_t e0 = time_us();
         (void) signal_energy_wait(st);             // the envelope's D2H copy ran behind the encoder / decoder
-        const int64_t e1 = time_us();
         token_level_timestamps(ctx, st, (int) st.result_all.size() - 1, params.thold_pt, params.thold_ptsum);
-        if (dbg_e) fprintf(stderr, "[wmi] emit: envelope wait %lld us, token timestamps %lld us\n", (long long) (e1 - e0), (long long) (time_us() - e1));
         if (params.max_len > 0) n_new = wrap_segment(ctx, st, params.max_len, params.split_on_word);
     }
     if (params.new_segment_callback)
@@ -63,13 +59,6 @@ void emit_segment(whisper_context & ctx, State & st, const whisper_full_params &
 int full(whisper_context & ctx, whisper_full_params params, const float * samples, const float * d_samples, int n_samples) {
     BusyScope busy(ctx.device);                                      // (see wmi.h: kernels that wait inside a launch are used by a lone transcription only)
     State & st = *ctx.state;
-    static const bool dbg_t = getenv("WMI_DEBUG_TIMING") != nullptr;
-    const int64_t T0 = time_us(); int64_t T_mel = 0, T_energy = 0, T_emit = 0;
-    struct Report { bool on; int64_t t0; int64_t * mel, * en, * emit; State * st; ~Report() { if (on) fprintf(stderr,
-        "[wmi] full: total %.3f ms | mel %.3f | envelope %.3f | encode %.3f | decode %.3f (+prompt/batch %.3f) | segments+timestamps %.3f\n",
-        (time_us() - t0) / 1e3, *mel / 1e3, *en / 1e3, st->t_encode_us / 1e3, st->t_decode_us / 1e3, (st->t_prompt_us + st->t_batchd_us) / 1e3, *emit / 1e3); } }
-        report{dbg_t, T0, &T_mel, &T_energy, &T_emit, &st};
-    if (dbg_t) { st.t_encode_us = st.t_decode_us = st.t_prompt_us = st.t_batchd_us = 0; }
     const Vocab & v = ctx.model.vocab;
     const HParams & hp = ctx.model.hp;
     st.result_all.clear();
@@ -84,7 +73,6 @@ int full(whisper_context & ctx, whisper_full_params params, const float * sample
         // (no host wait behind the log-mel and the encoder: the next phase's launches queue up behind them; WMI_PHASE_SYNC=1: wait as before)
         const bool ok_mel = d_samples ? pcm_to_mel(ctx, d_samples, n_samples, true, true, defer_phases) : pcm_to_mel(ctx, samples, n_samples, false, true, defer_phases);
         if (!ok_mel) { WMI_ERR("%s: failed to compute log mel spectrogram\n", __func__); return -2; }
-        T_mel = time_us() - T0;
     }
 
     if (params.language == nullptr || strlen(params.language) == 0 || strcmp(params.language, "auto") == 0 || params.detect_language) {
@@ -101,8 +89,6 @@ int full(whisper_context & ctx, whisper_full_params params, const float * sample
         st.t_beg = 0; st.t_last = 0; st.tid_last = 0;
         // the |x| envelope is computed on the GPU from the samples pcm_to_mel just staged (bit-identical to the
         // CPU loop, k_signal_energy); the host loop remains only as the definition it is tested against
-        const int64_t te0 = time_us();
-        struct En { int64_t & acc; int64_t t0; ~En() { acc += time_us() - t0; } } en_timer{T_energy, te0};
         if (n_samples > 0 && !signal_energy_device(ctx, 32, false)) { WMI_ERR("%s: failed to compute the signal envelope\n", __func__); return -2; }
     }
 
@@ -215,14 +201,14 @@ int full(whisper_context & ctx, whisper_full_params params, const float * sample
             kv_clear(st.kv_self);
             // Greedy, temperature 0, one decoder, no user logit callback: filters + arg-max run on the GPU and each
             // step is one graph replay (device.cpp: decode_greedy_step).  Everything else takes the general path.
-            const bool fast = fast_path_enabled() && !beam && t_cur < 1e-6f && n_cur == 1 && !params.logits_filter_callback && !params.grammar_rules &&
+            const bool fast = !beam && t_cur < 1e-6f && n_cur == 1 && !params.logits_filter_callback && !params.grammar_rules &&
                               params.n_grammar_rules == 0 &&
                               ctx.model.n_loaded > 0 && upload_static_ban(ctx, params);
             // Beam search and t > 0 (whisper_sample_token_topk / whisper_sample_token(best = false)): the filters, the soft-max and the
             // CDF search of the draws run on the device as well (device.cpp: sample_rows_device) — the decoders' mt19937 generators stay
             // here and supply the uniform numbers.  User callbacks and grammars need the host arrays and keep the host path.
             const bool no_dev_draw = k::knobs().host_draws;                           // debug / A-B and the tests (wmi_reload_knobs after a change)
-            const bool dev_draw = !fast && !no_dev_draw && fast_path_enabled() && (beam || t_cur > 0.0f) && n_cur <= MAX_DECODERS &&
+            const bool dev_draw = !fast && !no_dev_draw && (beam || t_cur > 0.0f) && n_cur <= MAX_DECODERS &&
                                   !params.logits_filter_callback && !params.grammar_rules && params.n_grammar_rules == 0 &&
                                   ctx.model.n_loaded > 0 && upload_static_ban(ctx, params);
             st.dev.keep_logits_on_device = dev_draw;
@@ -245,11 +231,6 @@ int full(whisper_context & ctx, whisper_full_params params, const float * sample
             };
             if (fast) {
                 bool ok = true;
-                static const bool stepwise = getenv("WMI_PROMPT_STEPWISE") != nullptr;   // debug / A-B: prompt token by token
-                if (stepwise) {
-                    for (size_t t = 0; ok && t + 1 < prompt.size(); ++t)
-                        ok = decode_greedy_step(ctx, prompt[t], (int) t, step_filter(st.decoders[0]), fast_next);
-                } else
                 if (prompt.size() > 1) {            // all but the last prompt token: plain batch decode, no logits wanted
                     st.batch.prep_legacy(prompt.data(), (int) prompt.size() - 1, 0, 0);
                     st.batch.logits[prompt.size() - 2] = 0;
@@ -458,8 +439,6 @@ int full(whisper_context & ctx, whisper_full_params params, const float * sample
 
         // results of this window
         {
-            const int64_t tem0 = time_us();
-            struct Em { int64_t & acc; int64_t t0; ~Em() { acc += time_us() - t0; } } em_timer{T_emit, tem0};
             const Decoder & best = st.decoders[best_decoder_id];
             emit_window(ctx, st, params, seek, prompt, prompt_init.size(), best);
             if (st.ts_failed) { WMI_ERR("%s: failed to refine the token timestamps on the device\n", __func__); return -9; }
@@ -790,8 +769,6 @@ void token_level_timestamps(whisper_context & ctx, State & st, int i_segment, fl
     // they stand before this loop (iteration j rewrites tokens[j] only, after its own sum), so all sums are taken
     // first.  Each one must stay a sequential left-to-right f32 sum (the reference's rounding), i.e. a 4-cycle
     // dependency chain per add — eight tokens are therefore summed side by side, eight independent chains.
-    static const bool dbg_ts = getenv("WMI_DEBUG_EMIT") != nullptr;
-    const int64_t ts0 = time_us();
     std::vector<float> win_sum(n, 0.0f);
     {
         std::vector<int> idx;
@@ -806,8 +783,6 @@ void token_level_timestamps(whisper_context & ctx, State & st, int i_segment, fl
         };
         pool_run((int) idx.size(), sum_one);
     }
-    const int64_t ts1 = time_us();
-    struct TsReport { bool on; int64_t a, b; ~TsReport() { if (on) fprintf(stderr, "[wmi] token timestamps: window sums %lld us, walks %lld us\n", (long long) (b - a), (long long) (time_us() - b)); } } ts_report{dbg_ts, ts0, ts1};
     for (int j = 0; j < n; ++j) {
         if (tokens[j].id >= v.eot) continue;
         int s0 = ts_to_sample(tokens[j].t0, n_samples), s1 = ts_to_sample(tokens[j].t1, n_samples);

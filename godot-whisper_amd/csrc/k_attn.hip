@@ -1216,18 +1216,15 @@ void attn_encoder(const __half * q, const __half * k, const __half * vt, int T, 
     // WMI_ATTN_FORM: 2 (default) = 32-row wavefronts, one sweep with a running maximum; 1 = the same kernel with the exact row
     // maximum found in a first sweep (the reference's soft-max argument); 0 = the round-1/2 kernel (16-row wavefronts, two sweeps)
     static const int form = getenv("WMI_ATTN_FORM") ? atoi(getenv("WMI_ATTN_FORM")) : 2;
-    static const int ksplit = getenv("WMI_ATTN_KSPLIT") ? atoi(getenv("WMI_ATTN_KSPLIT")) : -1;      // A/B knob; default: by grid size
     if (form >= 1 && scale == 0.125f && (Tpad % 64) == 0) {
-        const bool split = ksplit >= 0 ? ksplit > 1 : (((T + 127) / 128) * H * B < 512 && T >= 512 && !g_attn_one_group);
+        const bool split = ((T + 127) / 128) * H * B < 512 && T >= 512 && !g_attn_one_group;
         attn_encoder2(q, k, vt, T, Tpad, S, H, out, st, B, out32, form == 2, split, qk_rows);
         return;
     }
-    static const int nw = getenv("WMI_ATTN_NW") ? atoi(getenv("WMI_ATTN_NW")) : 4;      // wavefronts per workgroup (A/B knob)
     const int nblk = ((T + 63) / 64) * H * B;
-    const bool ks2 = ksplit >= 0 ? ksplit == 2 : (nblk <= 512 && T >= 256 && !g_attn_one_group);
-    if (nw == 4 && ks2) hipLaunchKernelGGL((k_attn_enc<4, 2>), dim3((T + 63) / 64, H, B), dim3(512), 0, st, q, k, vt, T, Tpad, S, scale, out, out32, qk_rows);
-    else if (nw == 4)   hipLaunchKernelGGL((k_attn_enc<4, 1>), dim3((T + 63) / 64, H, B), dim3(256), 0, st, q, k, vt, T, Tpad, S, scale, out, out32, qk_rows);
-    else                hipLaunchKernelGGL((k_attn_enc<2, 1>), dim3((T + 31) / 32, H, B), dim3(128), 0, st, q, k, vt, T, Tpad, S, scale, out, out32, qk_rows);
+    const bool ks2 = nblk <= 512 && T >= 256 && !g_attn_one_group;
+    if (ks2) hipLaunchKernelGGL((k_attn_enc<4, 2>), dim3((T + 63) / 64, H, B), dim3(512), 0, st, q, k, vt, T, Tpad, S, scale, out, out32, qk_rows);
+    else     hipLaunchKernelGGL((k_attn_enc<4, 1>), dim3((T + 63) / 64, H, B), dim3(256), 0, st, q, k, vt, T, Tpad, S, scale, out, out32, qk_rows);
 }
 
 void attn_decoder(const __half * q, int n, int S, int H, const __half * kc, const __half * vc, int n_kv,

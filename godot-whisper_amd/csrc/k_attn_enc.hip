@@ -43,7 +43,7 @@ __device__ __forceinline__ float max3(float a, float b, float c) { float d; asm(
 //                   cross-attention already makes: e is rounded to f16 relative to the maximum SO FAR);
 //            false: two sweeps, exact row maximum first (the reference's soft-max argument bit for bit).
 //   KS       key groups per workgroup (own tiles, common barriers); partial (m, sum, O^T) combined through LDS at the end.
-template <int QW, int KS, bool ONE, int NST, bool WIDE_OUT = true>
+template <int QW, int KS, bool ONE, int NST>
 __global__ __launch_bounds__(QW * KS * 64) void k_attn_enc2(const __half * __restrict__ q, const __half * __restrict__ k,
                                                             const __half * __restrict__ vt, int T, int Tpad, int S,
                                                             __half * __restrict__ out, float * __restrict__ out32, int xcd_order, int qk_rows) {
@@ -303,33 +303,31 @@ __global__ __launch_bounds__(QW * KS * 64) void k_attn_enc2(const __half * __res
 
     // O^T: lane = query row q0 + i, value columns 32 mt + 8 j + 4 g + r
     const int qg = q0 + i;
-    if constexpr (WIDE_OUT) {
-        if (!out32) {
-            // f16 output through a wavefront-private 4 KB LDS image (32 rows x 128 B, 16-byte chunks XOR-swizzled by the row): as 8-byte
-            // stores a wave instruction covered 32 rows x 16 B = 32 partial-line requests and the eight of them per wavefront were
-            // request-bound like the GEMM epilogues' (gemm_epi.h); read back 16 B per lane an instruction covers 8 rows x 128 B.
-            // Wavefront-private: no barrier, only the wave's own lgkmcnt wait.  The stored values are the plain form's.
-            if constexpr (KS == 1) __syncthreads();          // the ring's last tile has been read by every wavefront
-            unsigned char * tb = smem + TB_OFF + qw * 4096;
-            const float inv = (float) (1.0 / (double) l);
+    if (!out32) {
+        // f16 output through a wavefront-private 4 KB LDS image (32 rows x 128 B, 16-byte chunks XOR-swizzled by the row): as 8-byte
+        // stores a wave instruction covered 32 rows x 16 B = 32 partial-line requests and the eight of them per wavefront were
+        // request-bound like the GEMM epilogues' (gemm_epi.h); read back 16 B per lane an instruction covers 8 rows x 128 B.
+        // Wavefront-private: no barrier, only the wave's own lgkmcnt wait.
+        if constexpr (KS == 1) __syncthreads();          // the ring's last tile has been read by every wavefront
+        unsigned char * tb = smem + TB_OFF + qw * 4096;
+        const float inv = (float) (1.0 / (double) l);
 #pragma unroll
-            for (int mt = 0; mt < 2; ++mt)
+        for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    half4 w;
+            for (int j = 0; j < 4; ++j) {
+                half4 w;
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) w[r] = (_Float16) pin_f32(o[mt][4 * j + r] * inv);
-                    *(half4 *) (tb + i * 128 + (((4 * mt + j) ^ (i & 7)) << 4) + g * 8) = w;
-                }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-            for (int p = 0; p < 4; ++p) {
-                const int row = p * 8 + (lane >> 3), ch = lane & 7;
-                const uint4 v = *(const uint4 *) (tb + row * 128 + ((ch ^ (row & 7)) << 4));
-                if (q0 + row < T) *(uint4 *) (out + (size_t) (q0 + row) * S + head * 64 + ch * 8) = v;
+                for (int r = 0; r < 4; ++r) w[r] = (_Float16) pin_f32(o[mt][4 * j + r] * inv);
+                *(half4 *) (tb + i * 128 + (((4 * mt + j) ^ (i & 7)) << 4) + g * 8) = w;
             }
-            return;
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            const int row = p * 8 + (lane >> 3), ch = lane & 7;
+            const uint4 v = *(const uint4 *) (tb + row * 128 + ((ch ^ (row & 7)) << 4));
+            if (q0 + row < T) *(uint4 *) (out + (size_t) (q0 + row) * S + head * 64 + ch * 8) = v;
         }
+        return;
     }
     if (qg < T) {
         const float inv = (float) (1.0 / (double) l);
@@ -337,18 +335,11 @@ __global__ __launch_bounds__(QW * KS * 64) void k_attn_enc2(const __half * __res
         for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
+                // a quantised out-projection quantises the f32 tensor (the reference's KQV_merged is f32): no f16 rounding in between
                 const size_t at = (size_t) qg * S + head * 64 + mt * 32 + 8 * j + 4 * g;
-                if (out32) {
-                    // a quantised out-projection quantises the f32 tensor (the reference's KQV_merged is f32): no f16 rounding in between
-                    float4 w;
-                    w.x = o[mt][4 * j] * inv; w.y = o[mt][4 * j + 1] * inv; w.z = o[mt][4 * j + 2] * inv; w.w = o[mt][4 * j + 3] * inv;
-                    *(float4 *) (out32 + at) = w;
-                } else {
-                    half4 w;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) w[r] = (_Float16) pin_f32(o[mt][4 * j + r] * inv);
-                    *(half4 *) (out + at) = w;
-                }
+                float4 w;
+                w.x = o[mt][4 * j] * inv; w.y = o[mt][4 * j + 1] * inv; w.z = o[mt][4 * j + 2] * inv; w.w = o[mt][4 * j + 3] * inv;
+                *(float4 *) (out32 + at) = w;
             }
     }
 }
@@ -361,24 +352,14 @@ void launch_attn_enc2(const __half * q, const __half * k, const __half * vt, int
     constexpr size_t extra = (!ONE && KS > 1) ? (size_t) KS * QW * 32 * 4 : 0;
     constexpr size_t comb = KS > 1 ? (size_t) (KS - 1) * QW * 64 * 34 * 4 : 0;
     constexpr size_t smem0 = (ring + extra) > comb ? (ring + extra) : comb;
-    static const bool narrow = getenv("WMI_ATTN_NARROW_STORES") != nullptr;       // A/B knob: 8-byte output stores
-    // A/B knob: 0 = launch order, 1 = XCD runs.  Default: XCD runs for several chunks (operand fetches 213 -> ~40 MB per launch at 8 chunks;
-    // time unchanged within the noise: the Infinity Cache was serving the re-fetches), launch order for one chunk (14.3 against 15.0 us)
-    static const int xcd_env = getenv("WMI_ATTN_XCD") ? atoi(getenv("WMI_ATTN_XCD")) : -1;
+    // XCD runs for several chunks (operand fetches 213 -> ~40 MB per launch at 8 chunks; time unchanged within the noise: the Infinity
+    // Cache was serving the re-fetches), launch order for one chunk (14.3 against 15.0 us)
     static const int prio_env = getenv("WMI_ATTN_PRIO") ? atoi(getenv("WMI_ATTN_PRIO")) : 0;      // A/B knob: s_setprio 1 around the MFMA clusters
-    const int xcd_order = (xcd_env >= 0 ? (xcd_env & 1) : (B > 1)) | (prio_env ? 2 : 0);
-    if (narrow) {
-        static_assert(smem0 <= 160 * 1024, "LDS");
-        if (smem0 > 48 * 1024) allow_full_lds((const void *) k_attn_enc2<QW, KS, ONE, NST, false>, lds_ok);
-        hipLaunchKernelGGL((k_attn_enc2<QW, KS, ONE, NST, false>), dim3((T + QW * 32 - 1) / (QW * 32), H, B), dim3(QW * KS * 64), smem0, st,
-                           q, k, vt, T, Tpad, S, out, out32, xcd_order, qk_rows);
-        return;
-    }
+    const int xcd_order = (B > 1) | (prio_env ? 2 : 0);
     constexpr size_t smem = KS == 1 ? (smem0 > (size_t) QW * 4096 ? smem0 : (size_t) QW * 4096) : smem0 + (size_t) QW * 4096;      // the query wavefronts' output images: inside the ring (one key group) or behind it
     static_assert(smem <= 160 * 1024, "LDS");
-    static std::atomic<uint64_t> lds_ok_w{0};
-    if (smem > 48 * 1024) allow_full_lds((const void *) k_attn_enc2<QW, KS, ONE, NST, true>, lds_ok_w);
-    hipLaunchKernelGGL((k_attn_enc2<QW, KS, ONE, NST, true>), dim3((T + QW * 32 - 1) / (QW * 32), H, B), dim3(QW * KS * 64), smem, st,
+    if (smem > 48 * 1024) allow_full_lds((const void *) k_attn_enc2<QW, KS, ONE, NST>, lds_ok);
+    hipLaunchKernelGGL((k_attn_enc2<QW, KS, ONE, NST>), dim3((T + QW * 32 - 1) / (QW * 32), H, B), dim3(QW * KS * 64), smem, st,
                        q, k, vt, T, Tpad, S, out, out32, xcd_order, qk_rows);
 }
 
@@ -389,26 +370,14 @@ void attn_encoder2(const __half * q, const __half * k, const __half * vt, int T,
                    int B, float * out32, bool one_sweep, bool split, int qk_chunk_rows) {
     const int qk_rows = qk_chunk_rows > 0 ? qk_chunk_rows : T;
     // one key group wherever the result must not depend on how many chunks share the launch (lock-step "exact" mode) and
-    // wherever the grid fills the chip by itself; four key groups of two wavefronts for one or two chunks
-    // WMI_ATTN_CFG = <wavefronts per key group><key groups><ring depth>, e.g. 242 (A/B knob; the defaults are the measured best)
-    static const int cfg_env = getenv("WMI_ATTN_CFG") ? atoi(getenv("WMI_ATTN_CFG")) : 0;
-    const int cfg = cfg_env ? cfg_env : (split ? 242 : 412);
-#define WMI_ATTN_CASE(C, QW, KS, NST) case C: if (one_sweep) launch_attn_enc2<QW, KS, true, NST>(q, k, vt, T, Tpad, S, H, out, st, B, out32, qk_rows); \
-                                              else           launch_attn_enc2<QW, KS, false, NST>(q, k, vt, T, Tpad, S, H, out, st, B, out32, qk_rows); break;
-    switch (cfg) {
-        WMI_ATTN_CASE(242, 2, 4, 2)
-        WMI_ATTN_CASE(223, 2, 2, 3)
-        WMI_ATTN_CASE(224, 2, 2, 4)
-        WMI_ATTN_CASE(423, 4, 2, 3)
-        WMI_ATTN_CASE(422, 4, 2, 2)
-        WMI_ATTN_CASE(222, 2, 2, 2)
-        WMI_ATTN_CASE(413, 4, 1, 3)
-        WMI_ATTN_CASE(414, 4, 1, 4)
-        WMI_ATTN_CASE(213, 2, 1, 3)
-        default:
-        WMI_ATTN_CASE(412, 4, 1, 2)
+    // wherever the grid fills the chip by itself; four key groups of two wavefronts for one or two chunks (the measured best)
+    if (split) {
+        if (one_sweep) launch_attn_enc2<2, 4, true, 2>(q, k, vt, T, Tpad, S, H, out, st, B, out32, qk_rows);
+        else           launch_attn_enc2<2, 4, false, 2>(q, k, vt, T, Tpad, S, H, out, st, B, out32, qk_rows);
+    } else {
+        if (one_sweep) launch_attn_enc2<4, 1, true, 2>(q, k, vt, T, Tpad, S, H, out, st, B, out32, qk_rows);
+        else           launch_attn_enc2<4, 1, false, 2>(q, k, vt, T, Tpad, S, H, out, st, B, out32, qk_rows);
     }
-#undef WMI_ATTN_CASE
 }
 
 }}  // namespace wmi::k

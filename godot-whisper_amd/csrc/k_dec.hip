@@ -645,7 +645,7 @@ template <bool NT> __device__ __forceinline__ uint4 ldw(const __half * p) {
     return *(const uint4 *) p;
 }
 
-template <int R, int ROWS_IN_FLIGHT, bool NT = false>
+template <int R, int ROWS_IN_FLIGHT>
 __global__ __launch_bounds__(256) void k_gemv(const GemvArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __half * act = (__half *) smem;                         // [R][K]
@@ -662,7 +662,7 @@ __global__ __launch_bounds__(256) void k_gemv(const GemvArgs a) {
 #pragma unroll
         for (int u = 0; u < ROWS_IN_FLIGHT; ++u) {
             int o = gw * ROWS_IN_FLIGHT + u; if (o > a.N - 1) o = a.N - 1;
-            wpre[u] = ldw<NT>(a.W + (size_t) o * K + lane * 8);
+            wpre[u] = *(const uint4 *) (a.W + (size_t) o * K + lane * 8);
         }
     }
 
@@ -762,7 +762,7 @@ __global__ __launch_bounds__(256) void k_gemv(const GemvArgs a) {
 #pragma unroll
                     for (int u = 0; u < ROWS_IN_FLIGHT; ++u) {
                         int o = on + u; if (o > a.N - 1) o = a.N - 1;
-                        wpre[u] = ldw<NT>(a.W + (size_t) o * K + lane * 8);
+                        wpre[u] = *(const uint4 *) (a.W + (size_t) o * K + lane * 8);
                     }
                     first = true;                       // consumed by the next o0 iteration's first chunk
                 }
@@ -770,7 +770,7 @@ __global__ __launch_bounds__(256) void k_gemv(const GemvArgs a) {
 #pragma unroll
                 for (int u = 0; u < ROWS_IN_FLIGHT; ++u) {
                     int o = o0 + u; if (o > a.N - 1) o = a.N - 1;
-                    w[u] = ldw<NT>(a.W + (size_t) o * K + c);
+                    w[u] = *(const uint4 *) (a.W + (size_t) o * K + c);
                 }
             }
             float av[R][8];
@@ -1241,19 +1241,14 @@ void launch_gemv1(const GemvArgs & a, hipStream_t st, int max_blocks = 512) {
     hipLaunchKernelGGL((k_gemv1<RIF, NCH, NT, PRO, EPI, HPW, WPB, FS>), dim3(blocks, rows), dim3(64 * WPB), smem, st, a);
 }
 
-static int logits_blocks_cap() {
-    static const int lb = getenv("WMI_LOGITS_BLOCKS") ? std::min(atoi(getenv("WMI_LOGITS_BLOCKS")), FS_MAX_PARTS) : 768;
-    return lb;
-}
 // the decode step's hot (prologue, epilogue) combinations at one row; false = no specialised kernel for these arguments
 static bool launch_gemv1_special(const GemvArgs & a, int nch, hipStream_t st) {
-    static const bool off = getenv("WMI_GEMV1_GENERIC") != nullptr;       // debug / A-B
-    if (off || a.rows) return false;
+    if (a.rows) return false;
     const int pro = a.ln_g ? 1 : a.sa_q ? 2 : a.comb_o ? 3 : 0;
     if (a.N >= 16384) {                                      // vocabulary projection: its own lean instantiation (the generic kernel carries
         // the attention prologues: 251 VGPRs, 2 workgroups per CU; this one 143).  768 workgroups = 3 per CU: 9.55 us = 5.56 TB/s
         // (512: 10.6, 1024: 10.8, the generic kernel at 512: 11.4)
-        const int lb = logits_blocks_cap();
+        const int lb = FS_MAX_PARTS;
         if (pro == 1 && a.epi == EPI_LOGITS && a.fs_part) {      // + the logit filters' statistics in the epilogue (greedy step)
             if (nch == 1) { launch_gemv1<8, 1, false, 1, EPI_LOGITS, 0, 4, true>(a, st, lb); return true; }
             if (nch == 2) { launch_gemv1<8, 2, false, 1, EPI_LOGITS, 0, 4, true>(a, st, lb); return true; }
@@ -1297,10 +1292,7 @@ static bool launch_gemv1_special(const GemvArgs & a, int nch, hipStream_t st) {
             // mlp.2 of base.en (512 x 2048): 2 MB through 32 four-wavefront workgroups is 64 KB per CU — the CU's own load path is the
             // limit (~60 GB/s per CU: 1 us from "row ready" to "tile reduced"); one-wavefront workgroups put the same rows on 4x the CUs
             // (measured body: 256 threads x 4 rows per wavefront 2.93 us, 64 x 4 rows 2.40, 64 x 2 rows 2.22)
-            static const int shape = getenv("WMI_FC2_SHAPE") ? atoi(getenv("WMI_FC2_SHAPE")) : 2;      // A/B knob
-            if (shape == 2) launch_gemv1<2, 4, false, 0, EPI_F32_BIAS_RESID, 0, 1>(a, st, 4096);
-            else if (shape == 1) launch_gemv1<4, 4, false, 0, EPI_F32_BIAS_RESID, 0, 1>(a, st, 4096);
-            else launch_gemv1<4, 4, false, 0, EPI_F32_BIAS_RESID>(a, st);
+            launch_gemv1<2, 4, false, 0, EPI_F32_BIAS_RESID, 0, 1>(a, st, 4096);
             return true;
         }
         // mlp.2 of the wider models (K = 4 S = 3072 / 4096 / 5120): register budget = activation row + two row tiles of weights
@@ -1708,39 +1700,31 @@ void launch_rows_mfma(const GemvArgs & a, hipStream_t st) {
     int blocks = KSPLIT ? ntiles : (ntiles + 3) / 4;
     // vocabulary projection: 2 workgroups per CU, all resident at once, each wavefront walking ~1.6 tiles with the next tile's
     // weights in flight (811 workgroups, one tile per wavefront: 19.9 us at 8 rows; 512: 15.9; 576 and more: 20.5)
-    static const int cap = getenv("WMI_ROWS_BLOCKS") ? atoi(getenv("WMI_ROWS_BLOCKS")) : 512;        // A/B knob
     if (blocks > 1024) blocks = 1024;
     const bool mirror = !KSPLIT && a.rows_mirror_src;        // the step-record mirror (see the kernel): one more workgroup, inside the resident-sized grid
-    if (!KSPLIT && blocks > cap - (mirror ? 1 : 0)) blocks = cap - (mirror ? 1 : 0);
+    if (!KSPLIT && blocks > 512 - (mirror ? 1 : 0)) blocks = 512 - (mirror ? 1 : 0);
     static std::atomic<uint64_t> lds_ok{0};
     if (smem > 48 * 1024) allow_full_lds((const void *) k_rows_mfma<KSPLIT, EPI_T>, lds_ok);
     if (mirror) blocks += 1;
     hipLaunchKernelGGL((k_rows_mfma<KSPLIT, EPI_T>), dim3(blocks), dim3(256), smem, st, a);
 }
 
-template <int R, int RIF, bool NT = false>
+template <int R, int RIF>
 void launch_gemv_t(const GemvArgs & a, hipStream_t st, int max_blocks = 512) {
     size_t smem = (size_t) R * a.K * sizeof(__half);
     if (a.sa_q) smem = ((smem + 15) & ~(size_t) 15) + (sa_score_floats(a.K, a.sa_cap) + a.K) * sizeof(float);
     int blocks = (a.N + 4 * RIF - 1) / (4 * RIF);
     if (blocks > max_blocks) blocks = max_blocks;       // 2 workgroups per CU; longer rows-per-wave loops are software-pipelined
     static std::atomic<uint64_t> lds_ok{0};
-    if (smem > 48 * 1024) allow_full_lds((const void *) k_gemv<R, RIF, NT>, lds_ok);
-    hipLaunchKernelGGL((k_gemv<R, RIF, NT>), dim3(blocks), dim3(256), smem, st, a);
+    if (smem > 48 * 1024) allow_full_lds((const void *) k_gemv<R, RIF>, lds_ok);
+    hipLaunchKernelGGL((k_gemv<R, RIF>), dim3(blocks), dim3(256), smem, st, a);
 }
 
 template <int R>
 void launch_gemv(const GemvArgs & a, hipStream_t st) {
     // the vocabulary projection streams 53 MB: keep 8 rows (8 KB) per wavefront in flight; small matrices use 4
-    if (R == 1 && a.N >= 16384) {
-        static const int rif = getenv("WMI_LOGITS_RIF") ? atoi(getenv("WMI_LOGITS_RIF")) : 8;          // A/B knobs
-        static const int mb = getenv("WMI_LOGITS_BLOCKS") ? atoi(getenv("WMI_LOGITS_BLOCKS")) : 512;
-        static const bool nt = getenv("WMI_LOGITS_NT") != nullptr;
-        if (rif == 16)     { if (nt) launch_gemv_t<1, 16, true>(a, st, mb); else launch_gemv_t<1, 16>(a, st, mb); }
-        else if (rif == 4) { if (nt) launch_gemv_t<1, 4, true>(a, st, mb);  else launch_gemv_t<1, 4>(a, st, mb); }
-        else               { if (nt) launch_gemv_t<1, 8, true>(a, st, mb);  else launch_gemv_t<1, 8>(a, st, mb); }
-    }
-    else launch_gemv_t<R, 4>(a, st);
+    if (R == 1 && a.N >= 16384) launch_gemv_t<1, 8>(a, st);
+    else                        launch_gemv_t<R, 4>(a, st);
 }
 
 } // namespace
@@ -1773,16 +1757,14 @@ static std::atomic<int> g_mode_epoch{0};
 int  mode_epoch() { return g_mode_epoch.load(std::memory_order_relaxed); }
 void bump_mode_epoch() { g_mode_epoch.fetch_add(1, std::memory_order_relaxed); }
 void set_rows_valu(bool on) { if (on != g_rows_valu) bump_mode_epoch(); g_rows_valu = on; }
-bool rows_valu_enabled() { static const bool env = getenv("WMI_ROWS_VALU") != nullptr; return env || g_rows_valu; }
+bool rows_valu_enabled() { return g_rows_valu; }
 
 static void gemv_(const GemvArgs & a, hipStream_t st);
 int gemv_fused_parts(const GemvArgs & a) {
     // mirrors the dispatch below: one row, LayerNorm prologue, EPI_LOGITS, rows of <= 1536 columns, no row gather
-    static const bool off = getenv("WMI_GEMV1_GENERIC") != nullptr || getenv("WMI_GEMV1_OFF") != nullptr || getenv("WMI_GEMV1_MASK") != nullptr ||
-                            getenv("WMI_NO_FUSED_STATS") != nullptr;
-    if (off || !a.fs_part || a.n != 1 || a.lanes || a.rows || !a.ln_g || a.epi != EPI_LOGITS || a.N < 16384 || a.K > 1536 || (a.K % 8) != 0) return 0;
+    if (!a.fs_part || a.n != 1 || a.lanes || a.rows || !a.ln_g || a.epi != EPI_LOGITS || a.N < 16384 || a.K > 1536 || (a.K % 8) != 0) return 0;
     const int blocks = (a.N + 31) / 32;
-    return std::min(blocks, logits_blocks_cap());
+    return std::min(blocks, FS_MAX_PARTS);
 }
 // ------------------------------------------------------------------------------------------------ one MLP, one launch
 // Phase 1 = k_gemv1<4, 1, false, 1, EPI_F16_BIAS_GELU> (LayerNorm in every wavefront, four weight rows per wavefront, the same halving
@@ -2194,7 +2176,6 @@ __global__ __launch_bounds__(64 * WPB) void k_front(const FrontArgs a_in, const 
 static Knobs read_knobs() {
     Knobs kn{};
     kn.no_mlp_pair = getenv("WMI_NO_MLP_PAIR") != nullptr;
-    kn.pair_wpb = getenv("WMI_PAIR_WPB") ? atoi(getenv("WMI_PAIR_WPB")) : 4;
     kn.sa_wpb = getenv("WMI_SA_WPB") ? atoi(getenv("WMI_SA_WPB")) : 8;
     kn.gemv1_wide_generic = getenv("WMI_GEMV1_WIDE_GENERIC") != nullptr;
     kn.host_draws = getenv("WMI_HOST_DRAWS") != nullptr;
@@ -2220,10 +2201,9 @@ const Knobs & knobs() {
 }
 void reload_knobs() { g_knobs.store(new Knobs(read_knobs()), std::memory_order_release); }      // (the old block is left in place: a reader may still hold it)
 
-// (S, 8-wavefront workgroups?) -> instantiation; the two functions below walk the same table
-#define WMI_PAIR_TABLE(S, w8, nch2, X) do { \
-        if (w8)             { if ((nch2) <= 3) X(1, 3, 8); else X(1, 4, 8); } \
-        else if ((S) <= 512) { if ((nch2) <= 3) X(1, 3, 4); else X(1, 4, 4); } \
+// S -> instantiation; the two functions below walk the same table
+#define WMI_PAIR_TABLE(S, nch2, X) do { \
+        if ((S) <= 512)      { if ((nch2) <= 3) X(1, 3, 4); else X(1, 4, 4); } \
         else if ((S) <= 768) X(2, 6, 4); \
         else                X(2, 8, 4); } while (0)
 
@@ -2252,28 +2232,25 @@ bool mlp_pair_usable(int S, bool with_mirror) {
     // base.en 155.4 / 158.9, small 384.8 / 406.5 (-5.3 %), medium 873.8 / 890.3, large-v3 (f16) 1563 / 1541 — at S = 1280 the two 13 MB
     // matrices are a bandwidth matter and one row per wavefront streams them worse than the two-launch tiling: two launches there
     if (S > 1024 || (S % 64) != 0) return false;
-    const int wpb = knobs().pair_wpb;
-    const bool w8 = wpb == 8 && (S % 8) == 0 && S <= 512;
-    const int blocks = S / (w8 ? 8 : 4) + (with_mirror ? 1 : 0);
+    const int blocks = S / 4 + (with_mirror ? 1 : 0);
     const int nch2 = (4 * S + 511) / 512;
     int fit = 0;
 #define WMI_PAIR_FIT(N1, N2, W) fit = pair_fit<N1, N2, W>()
-    WMI_PAIR_TABLE(S, w8, nch2, WMI_PAIR_FIT);
+    WMI_PAIR_TABLE(S, nch2, WMI_PAIR_FIT);
 #undef WMI_PAIR_FIT
     return blocks <= fit;
 }
 
 void mlp_pair(const MlpPairArgs & a, float * x_inout, hipStream_t st) {
     const int S = a.S;
-    // 4 S rows of W1, four per wavefront, 4-wavefront workgroups.  (WMI_PAIR_WPB=8: eight — half as many sweeping workgroups, one 16-byte
-    // load per thread and sweep instead of two: measured SLOWER, step chain 157.5 against 155.4 us; two launches 158.9, same process)
-    const bool w8 = knobs().pair_wpb == 8 && (S % 8) == 0 && S <= 512;
-    const int G = S / (w8 ? 8 : 4);
+    // 4 S rows of W1, four per wavefront, 4-wavefront workgroups.  (eight — half as many sweeping workgroups, one 16-byte load per thread
+    // and sweep instead of two — measured SLOWER: step chain 157.5 against 155.4 us; two launches 158.9, same process)
+    const int G = S / 4;
     const int blocks = G + (a.step_copy_src ? 1 : 0);
     const int nch2 = (4 * S + 511) / 512;
     const Stamp sp = stamp_next();
 #define WMI_PAIR_GO(N1, N2, W) hipLaunchKernelGGL((k_mlp_pair<N1, N2, W>), dim3(blocks), dim3(64 * W), 0, st, a, x_inout, G, sp)
-    WMI_PAIR_TABLE(S, w8, nch2, WMI_PAIR_GO);
+    WMI_PAIR_TABLE(S, nch2, WMI_PAIR_GO);
 #undef WMI_PAIR_GO
 }
 #undef WMI_PAIR_TABLE
@@ -2317,50 +2294,41 @@ void gemv(const GemvArgs & a, hipStream_t st) {
     gemv_(a, st);
 }
 static bool rows_on_mfma(const GemvArgs & a) {
-    static const bool rows_valu_env = getenv("WMI_ROWS_VALU") != nullptr;
-    const bool rows_valu = rows_valu_env || g_rows_valu;
     return a.lanes && a.n >= 2 && a.n <= 16 && !a.sa_q && (!a.comb_o || a.N < 8192) && (a.K % 128) == 0 &&
-           (a.epi != EPI_QKV_DEC || (a.S % 16) == 0) && (!rows_valu || a.n > 8);
+           (a.epi != EPI_QKV_DEC || (a.S % 16) == 0) && (!g_rows_valu || a.n > 8);
 }
 bool gemv_rows_carries_mirror(const GemvArgs & a) { return rows_on_mfma(a) && a.N >= 8192; }
 bool gemv_rows_take_self_attention(const GemvArgs & a) {
-    static const int rows_y = getenv("WMI_ROWS_Y") ? atoi(getenv("WMI_ROWS_Y")) : 1;
-    static const bool off = getenv("WMI_GEMV1_GENERIC") != nullptr;
     const int nch = (a.K + 511) / 512, hpw = (a.K / 64 + 3) / 4;
     const bool inst = (nch == 1 && (hpw == 1 || hpw == 2)) || (nch == 2 && (hpw == 3 || hpw == 4)) || (nch == 3 && (hpw == 5 || hpw == 4));
-    return rows_y && !off && a.lanes && a.n >= 2 && a.n <= 16 && a.N < 8192 && a.K <= 2048 && (a.K % 64) == 0 && a.epi == EPI_F32_BIAS_RESID && inst;
+    return a.lanes && a.n >= 2 && a.n <= 16 && a.N < 8192 && a.K <= 2048 && (a.K % 64) == 0 && a.epi == EPI_F32_BIAS_RESID && inst;
 }
 static void gemv_(const GemvArgs & a, hipStream_t st) {
-    // lock-step chunk rows go to the matrix cores (WMI_ROWS_VALU=1 keeps them on the VALU kernel, whose per-row
+    // lock-step chunk rows go to the matrix cores (wmi_set_lockstep_exact keeps them on the VALU kernel, whose per-row
     // arithmetic is bit-identical to the single-row path: used by the parity tests to pin the control flow)
     // ... except the small projections (everything but the vocabulary): as n one-row problems, row = grid.y of the one-row kernels
     // (k_gemv1).  The matrix-core rows kernel reads every weight once but normalises / gathers all n rows in each of its workgroups and
     // runs 6.3-6.6 us per launch at 8 rows where the one-row kernels take 4.2-4.8; with the row dimension on grid.y the extra weight
     // reads come from the XCD's own L2, and the out projection takes the self-attention in its prologue like the one-row step (one
-    // launch fewer per layer).  Per row the arithmetic IS the one-row path's.  WMI_ROWS_Y=0: off (A/B).
-    static const int rows_y = getenv("WMI_ROWS_Y") ? atoi(getenv("WMI_ROWS_Y")) : 1;
-    if (rows_y && a.lanes && a.n >= 2 && a.n <= 16 && a.N < 8192 && !a.rows && a.K <= 2048 && (a.K % 8) == 0 && (!a.ln_g || a.K <= 1536) && !a.step_copy_src) {
+    // launch fewer per layer).  Per row the arithmetic IS the one-row path's.
+    if (a.lanes && a.n >= 2 && a.n <= 16 && a.N < 8192 && !a.rows && a.K <= 2048 && (a.K % 8) == 0 && (!a.ln_g || a.K <= 1536) && !a.step_copy_src) {
         if (launch_gemv1_special(a, (a.K + 511) / 512, st)) return;
     }
     const bool mfma_ok = rows_on_mfma(a) && !a.sa_q;
     if (mfma_ok) {
-        static const bool generic = getenv("WMI_ROWS_GENERIC_EPI") != nullptr;       // A/B knob
-        const bool vec = !generic && (a.N % 16) == 0 && (a.ldc % 4) == 0 && (!a.resid || (a.ldr % 4) == 0) &&
+        const bool vec = (a.N % 16) == 0 && (a.ldc % 4) == 0 && (!a.resid || (a.ldr % 4) == 0) &&
                          (a.epi != EPI_QKV_DEC || ((a.ldaux % 4) == 0 && (a.ldaux2 % 4) == 0));
         // vocabulary projection: whole tiles leave as one 16-byte store per lane; the ragged last tile keeps the element-wise form
-        if (a.N >= 8192) { if (!generic && a.epi == EPI_LOGITS && (a.ldc % 4) == 0 && !a.bias) launch_rows_mfma<false, EPI_LOGITS>(a, st); else launch_rows_mfma<false>(a, st); }
+        if (a.N >= 8192) { if (a.epi == EPI_LOGITS && (a.ldc % 4) == 0 && !a.bias) launch_rows_mfma<false, EPI_LOGITS>(a, st); else launch_rows_mfma<false>(a, st); }
         else if (vec && a.epi == EPI_QKV_DEC)        launch_rows_mfma<true, EPI_QKV_DEC>(a, st);
         else if (vec && a.epi == EPI_F32_BIAS_RESID) launch_rows_mfma<true, EPI_F32_BIAS_RESID>(a, st);
         else if (vec && a.epi == EPI_F16_BIAS_GELU)  launch_rows_mfma<true, EPI_F16_BIAS_GELU>(a, st);
         else launch_rows_mfma<true>(a, st);
         return;
     }
-    static const bool gemv1_off = getenv("WMI_GEMV1_OFF") != nullptr;       // debug / A-B: LDS-staged one-row path
-    static const int gemv1_mask = getenv("WMI_GEMV1_MASK") ? atoi(getenv("WMI_GEMV1_MASK")) : 0;   // debug: per-prologue opt-out
-    const int kind = a.ln_g ? 1 : a.sa_q ? 2 : a.comb_o ? 4 : 8;
-    if (a.n == 1 && !a.lanes && a.K > 2048 && a.K <= 5120 && (a.K % 8) == 0 && !gemv1_off && !(gemv1_mask & kind) && kind == 8 &&
-        launch_gemv1_special(a, (a.K + 511) / 512, st)) return;
-    if (a.n == 1 && !a.lanes && a.K <= 2048 && (a.K % 8) == 0 && !gemv1_off && !(gemv1_mask & kind) && (!a.ln_g || a.K <= 1536)) {
+    const bool plain = !a.ln_g && !a.sa_q && !a.comb_o;
+    if (a.n == 1 && !a.lanes && a.K > 2048 && a.K <= 5120 && (a.K % 8) == 0 && plain && launch_gemv1_special(a, (a.K + 511) / 512, st)) return;
+    if (a.n == 1 && !a.lanes && a.K <= 2048 && (a.K % 8) == 0 && (!a.ln_g || a.K <= 1536)) {
         const int nch = (a.K + 511) / 512;
         if (launch_gemv1_special(a, nch, st)) return;
         if (a.N >= 16384) {                       // vocabulary projection: 8 rows (8 KB) per wavefront in flight

@@ -259,18 +259,16 @@ void launch_n(const GemmArgs & a, hipStream_t st) {
 }
 template <int BM, int BN, int EPI>
 void launch(const GemmArgs & a, hipStream_t st) {
-    static const bool shallow = getenv("WMI_GEMM_RING2") != nullptr;         // debug / A-B
     const long nwg = (long) ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN);
     // (a 3-deep ring for the grids in between — q|k|v 576, mlp.0 768 tiles — measured the same as 2)
-    if (BM < 128 && nwg <= 400 && !shallow) launch_n<BM, BN, EPI, 4>(a, st);
-    else                                    launch_n<BM, BN, EPI, 2>(a, st);
+    if (BM < 128 && nwg <= 400) launch_n<BM, BN, EPI, 4>(a, st);
+    else                        launch_n<BM, BN, EPI, 2>(a, st);
 }
 
 template <int EPI>
 void dispatch(const GemmArgs & a, hipStream_t st) {
     // 256 CUs: prefer the 128x128 tile only when it still yields >= ~1.5 waves of workgroups
     const long t128 = (long) ((a.M + 127) / 128) * ((a.N + 127) / 128);
-    static const bool no_narrow = getenv("WMI_GEMM_NO_NARROW") != nullptr;  // debug / A-B
     const long t64 = (long) ((a.M + 63) / 64) * ((a.N + 63) / 64);
     // WMI_GEMM_WIDE=1 (A/B knob, off): 128 x 256 tiles on eight wavefronts with a three-deep ring for the big grids (lock-step encoder,
     // M = chunks x T).  Measured (profiles/r03b_gemm_wide_tile_and_gelu.txt): mlp.0 x 8 45.8 us against 43.5 us for two co-resident
@@ -282,63 +280,39 @@ void dispatch(const GemmArgs & a, hipStream_t st) {
     if constexpr (EPI == EPI_F16_BIAS_GELU || EPI == EPI_QKV_ENC || EPI == EPI_CROSS_KV || EPI == EPI_F16_BIAS) {
         if (wide && (a.N % 256) == 0 && t256 >= 384 && (a.K % BK) == 0 && !(a.no_glds & 1)) { launch_n<128, 256, EPI, 3, 8>(a, st); return; }
     }
-    // WMI_GEMM_TALL (A/B knob, off): wave tiles of 128 x 64 instead of 64 x 64 on the big grids.  Per k the fragment reads of a wavefront are
-    // (TM + TN) x 2 bytes for 2 TM TN flops: 64 x 64 wave tiles read 1 KB of LDS per 16-cycle MFMA quartet, which together with the DMA writes
-    // is ~1.5x the LDS cycles of the MFMA cycles they feed; 128 x 64 cuts the reads per flop by a quarter.
-    //   1: 256 x 128 tiles, four wavefronts, two-deep ring (96 KB)   2: the same, three-deep (144 KB)   3: 256 x 256, eight wavefronts (128 KB)
-    static const int tall = getenv("WMI_GEMM_TALL") ? atoi(getenv("WMI_GEMM_TALL")) : 0;
-    if constexpr (EPI == EPI_F16_BIAS_GELU) {
-        if (tall && a.M >= 4096 && (a.K % BK) == 0 && (a.N % 256) == 0 && !(a.no_glds & 1)) {
-            if (tall == 1) { launch_n<256, 128, EPI, 2, 4>(a, st); return; }
-            if (tall == 2) { launch_n<256, 128, EPI, 3, 4>(a, st); return; }
-            if (tall == 3) { launch_n<256, 256, EPI, 2, 8>(a, st); return; }
-        }
-    }
     // Round 6: the N = S projections of the big grids (out, mlp.2 at M = chunks x 1500) on 192 x 128 tiles, ONE workgroup of eight wavefronts per CU
     // on a three-deep ring: 252 tiles at 8 chunks = one round, 76.8 flop per operand byte against 54.9 for two co-resident 96 x 128 workgroups.
     // Measured at 8 chunks (profiles/r06e_*): mlp.2 40.3 -> 34.2 us, out 15.5 -> 13.8; 16 chunks mlp.2 75.6 -> 72.2; 4 chunks mlp.2 34.3 -> 28.2 but
     // out 9.2 -> 10.6 (128 tiles: half the chip) — so the short-K projection takes it only with >= 200 tiles.  Ring depth: two 40.0, three 35.8, four
     // (all 160 KB of LDS) 33.4 - 34.8 us for mlp.2; four wavefronts 42.1; the conv front-end on this tile 33.3 - 33.9 against 33.4 - 34.7 us (stays).
-    //   WMI_GEMM_NS192: 0 = off   1 = eight wavefronts, three-deep   2 = two-deep   3 = four wavefronts   4 = four-deep (default)
-    static const int ns192 = getenv("WMI_GEMM_NS192") ? atoi(getenv("WMI_GEMM_NS192")) : 4;
     if constexpr (EPI == EPI_F32_BIAS_RESID) {
         const long t192 = (long) ((a.M + 191) / 192) * (a.N / 128);
-        if (ns192 && a.M >= 4096 && a.N <= 1024 && (a.N % 128) == 0 && (a.K % BK) == 0 && !(a.no_glds & 1) && (a.K >= 1024 || t192 >= 200)) {
-            if (ns192 == 1) { launch_n<192, 128, EPI, 3, 8>(a, st); return; }
-            if (ns192 == 2) { launch_n<192, 128, EPI, 2, 8>(a, st); return; }
-            if (ns192 == 3) { launch_n<192, 128, EPI, 3, 4>(a, st); return; }
-            if (ns192 == 4) { launch_n<192, 128, EPI, 4, 8>(a, st); return; }
+        if (a.M >= 4096 && a.N <= 1024 && (a.N % 128) == 0 && (a.K % BK) == 0 && !(a.no_glds & 1) && (a.K >= 1024 || t192 >= 200)) {
+            launch_n<192, 128, EPI, 4, 8>(a, st); return;
         }
     }
-    static const long t128_min = getenv("WMI_GEMM_T128") ? atol(getenv("WMI_GEMM_T128")) : 320;        // A/B knob; 376 tiles (out projection at M = 12 000): 18.6 us against 23.0 us as 1 504 tiles of 64 x 64
-    if (t128 >= t128_min || (t128 >= 256 && a.K >= 1024)) {
+    // 376 tiles (out projection at M = 12 000): 18.6 us against 23.0 us as 1 504 tiles of 64 x 64
+    if (t128 >= 320 || (t128 >= 256 && a.K >= 1024)) {
         // Round quantisation on the big grids: two workgroups per CU = 512 resident tiles; q|k|v at M = 12 000 is 1 128 tiles of 128 rows
         // (2.2 rounds: the third runs 20 % full), the N = S projections 376 (one round, 73 % full).  Tiles of 96 rows make that 1 500 and
         // 500: whole rounds.  Taken when they fill the rounds better by more than their ~5 % lower operand reuse costs.
         // (round 6: the conv front-end's big grids on 96-row tiles too — conv2 x8 is 376 tiles of 128 rows = 0.73 of the 512 resident slots, 504 of 96
-        //  rows fill them: 38.5 -> 33.4 us, conv1 18.6 -> 17.6; WMI_GEMM_CONV96=0: off)
-        static const bool conv96 = getenv("WMI_GEMM_CONV96") ? atoi(getenv("WMI_GEMM_CONV96")) != 0 : true;
+        //  rows fill them: 38.5 -> 33.4 us, conv1 18.6 -> 17.6)
         if constexpr (EPI == EPI_QKV_ENC || EPI == EPI_F32_BIAS_RESID || EPI == EPI_CONV2 || EPI == EPI_F16_BIAS_GELU) {
-            if (!conv96 && (EPI == EPI_CONV2 || EPI == EPI_F16_BIAS_GELU)) { launch<128, 128, EPI>(a, st); return; }
-            static const bool no96 = getenv("WMI_GEMM_NO_96") != nullptr;          // A/B knob
             const long t96 = (long) ((a.M + 95) / 96) * ((a.N + 127) / 128);
             auto fill = [](long t) { return (double) t / (double) (((t + 511) / 512) * 512); };
-            if (!no96 && a.M >= 4096 && (a.K % BK) == 0 && fill(t96) > fill(t128) + 0.08) { launch_n<96, 128, EPI, 2>(a, st); return; }
+            if (a.M >= 4096 && (a.K % BK) == 0 && fill(t96) > fill(t128) + 0.08) { launch_n<96, 128, EPI, 2>(a, st); return; }
         }
         launch<128, 128, EPI>(a, st);
     }
     else if constexpr (EPI == EPI_F32_BIAS_RESID) {
         // The N = S projections of the widest models at one chunk (large-v3: 1500 x 1280, K = 1280 / 5120): 240 tiles of 64 x 128 on a four-deep ring
         // instead of 480 of 64 x 64 — a quarter fewer LDS fragment reads per flop.  Measured on the large-v3 q5_1 encoder (64 of these GEMMs):
-        // 6.85 -> 6.70 ms; 128 x 64 tiles 6.83, 64 x 128 on a two-deep ring 6.99 (profiles/r03c_gemm_ns_tile.txt).  WMI_GEMM_NS_TILE=0: off.
-        static const int ns_tile = getenv("WMI_GEMM_NS_TILE") ? atoi(getenv("WMI_GEMM_NS_TILE")) : 1;
-        if (ns_tile && a.K >= 1024 && (a.N % 128) == 0 && (a.K % BK) == 0 && t64 >= 400 && !(a.no_glds & 1)) {
-            if (ns_tile == 2) { launch_n<128, 64, EPI, 4>(a, st); return; }
-            launch_n<64, 128, EPI, 4>(a, st); return;
-        }
+        // 6.85 -> 6.70 ms; 128 x 64 tiles 6.83, 64 x 128 on a two-deep ring 6.99 (profiles/r03c_gemm_ns_tile.txt).
+        if (a.K >= 1024 && (a.N % 128) == 0 && (a.K % BK) == 0 && t64 >= 400 && !(a.no_glds & 1)) { launch_n<64, 128, EPI, 4>(a, st); return; }
         // one chunk, N = S: 64x64 tiles give fewer workgroups than CUs (192 for base.en) and each walks K alone with nothing to
         // overlap its loads; 64x32 tiles double the workgroups
-        if (t64 < 256 && !no_narrow) launch<64, 32, EPI>(a, st); else launch<64, 64, EPI>(a, st);
+        if (t64 < 256) launch<64, 32, EPI>(a, st); else launch<64, 64, EPI>(a, st);
     }
     else             launch<64, 64, EPI>(a, st);
 }
@@ -368,19 +342,17 @@ void gemm(int epi, const GemmArgs & a_in, hipStream_t st) {
     // persistent ping-pong kernel (k_gemm8.hip): mlp.0 (N = 4 S) and the cross K / V of all decoder layers (N = 2 L S).  Measured at
     // M = 12 000 (profiles/r04a_gemm8_lab_*): mlp.0 41 -> 35.7 us, cross K/V 132 -> 105 us, every output element identical.  The N = S
     // projections (one or two column tiles) and q|k|v (its V^T third wants the other fragment orientation) stay here.
-    static const int g8 = getenv("WMI_GEMM8") ? atoi(getenv("WMI_GEMM8")) : 1;         // A/B knob: 0 = off
-    if (g8 && !no_glds && (epi == EPI_F16_BIAS_GELU || epi == EPI_CROSS_KV) && a.M >= 4096 && a.N >= 1024 && (a.N % 256) == 0 && (a.K % 64) == 0 &&
+    if (!no_glds && (epi == EPI_F16_BIAS_GELU || epi == EPI_CROSS_KV) && a.M >= 4096 && a.N >= 1024 && (a.N % 256) == 0 && (a.K % 64) == 0 &&
         (epi != EPI_CROSS_KV || (a.S % 64) == 0)) {
         const long t192 = (long) ((a.M + 191) / 192) * (a.N / 256);
         // (round 6: 288-row tiles for these two measured slower — cross K/V 90.4 against 85.0 us, mlp.0 43.5 against 32.7: profiles/r06c_*)
         if (t192 >= 384) { GemmArgs b = a; b.no_glds = a.no_glds & 16; if (gemm8(epi, 192, true, b, st)) return; }
     }
     // (q|k|v stays below: on 288-row tiles — 42 x 6 = 252, ONE round at M = 12 000 — the persistent kernel measures 41.1 us against 41.0 us
-    //  here, in situ 37.5 against 37.4: the V^T third's epilogue decides, not the tiling; WMI_GEMM8_QKV=1 routes it there for A/B)
+    //  here, in situ 37.5 against 37.4: the V^T third's epilogue decides, not the tiling)
     // (round 6: with the V^T third leaving in whole lines — gemm_epi.h: epilogue_vt_wide, chunks on 16-row boundaries — the tiling decides again:
-    //  288-row tiles in whole rounds of the persistent kernel; WMI_GEMM8_QKV=0: off)
-    static const bool g8_qkv = getenv("WMI_GEMM8_QKV") ? atoi(getenv("WMI_GEMM8_QKV")) != 0 : true;
-    if (g8_qkv && g8 && !no_glds && epi == EPI_QKV_ENC && a.M >= 4096 && (a.N % 256) == 0 && (a.K % 64) == 0 && a.S > 0 && (a.S % 128) == 0 && a.N == 3 * a.S) {
+    //  288-row tiles in whole rounds of the persistent kernel)
+    if (!no_glds && epi == EPI_QKV_ENC && a.M >= 4096 && (a.N % 256) == 0 && (a.K % 64) == 0 && a.S > 0 && (a.S % 128) == 0 && a.N == 3 * a.S) {
         const long t288 = (long) ((a.M + 287) / 288) * (a.N / 256);
         const long n_cu = cu_count_x8(), rounds = (t288 + n_cu - 1) / n_cu;
         if (t288 * 5 >= rounds * n_cu * 4) { GemmArgs b = a; b.no_glds = a.no_glds & 16; if (gemm8(epi, 288, true, b, st, 32)) return; }

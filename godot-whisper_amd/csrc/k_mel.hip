@@ -312,9 +312,9 @@ __global__ void k_fill_zero_strided(uint32_t * p, size_t words, size_t stride_wo
 __device__ __forceinline__ void signal_energy_body(const float * __restrict__ x, int n, int hw, float * __restrict__ out,
                                                        float * __restrict__ bmin, float * __restrict__ bmax) {
     __shared__ float s_min[4], s_max[4];
-    // block-stride loop: the grid may be thinner than one workgroup per 256 samples (WMI_ENVELOPE_GRID, A/B: the kernel is bound by its
-    // stores into pinned host memory and its stalled waves hold slots beside whatever runs next to it — but 64 workgroups starve the
-    // 65-deep f64 chains: the lock-step call 6.0 -> 6.5 ms; the one-chunk call within noise)
+    // block-stride loop; the launch gives one workgroup per 256 samples (a thinner grid was measured: the kernel is bound by its stores
+    // into pinned host memory and its stalled waves hold slots beside whatever runs next to it — but 64 workgroups starve the 65-deep
+    // f64 chains: the lock-step call 6.0 -> 6.5 ms; the one-chunk call within noise)
     for (int blk = blockIdx.x; blk * 256 < n; blk += gridDim.x) {
     if (blk != (int) blockIdx.x) __syncthreads();          // s_min / s_max are reused
     const int i = blk * blockDim.x + threadIdx.x;
@@ -515,9 +515,8 @@ void fill_zero_strided(void * p, size_t bytes, size_t stride_bytes, int count, h
 }
 
 void signal_energy(const float * pcm, int n, int hw, float * out, float * bmin, float * bmax, hipStream_t st) {
-    static const int thin = getenv("WMI_ENVELOPE_GRID") ? atoi(getenv("WMI_ENVELOPE_GRID")) : 0;      // A/B knob; 0 = one workgroup per block
     const int nblk = (n + 255) / 256;
-    hipLaunchKernelGGL(k_signal_energy, dim3(thin > 0 && thin < nblk ? thin : nblk), dim3(256), 0, st, pcm, n, hw, out, bmin, bmax);
+    hipLaunchKernelGGL(k_signal_energy, dim3(nblk), dim3(256), 0, st, pcm, n, hw, out, bmin, bmax);
 }
 
 // ---------------------------------------------------------------- token timestamps: window sums + walks over the envelope (kernels.h TsTok / TsOut)
@@ -698,28 +697,6 @@ __global__ __launch_bounds__(TS_W * 64) void k_ts_refine(const float * __restric
 }
 void ts_refine(const float * en, const float * bmin, const float * bmax, int n_samples, const TsTok * in, TsOut * out, int n_tok, hipStream_t st) {
     if (n_tok > 0) hipLaunchKernelGGL(k_ts_refine, dim3(n_tok), dim3(TS_W * 64), 0, st, en, bmin, bmax, n_samples, in, out);
-}
-
-// A copy by a handful of workgroups: 16 bytes per lane and trip, four trips in flight.  Used for the |x| envelopes of a lock-step call
-// (15 MB to pinned host memory for 8 chunks): as stores of the full-grid envelope kernel — or of the runtime's blit kernel — thousands
-// of wavefronts queue megabytes of PCIe writes at once, and the 32-byte results of the decode steps running beside them wait behind
-// that queue; a few wavefronts keep it a few KB deep and take as long as the decode phase lets them.
-__global__ __launch_bounds__(256) void k_copy_thin(const uint4 * __restrict__ src, uint4 * __restrict__ dst, size_t n16, const unsigned char * __restrict__ tsrc,
-                                                   unsigned char * __restrict__ tdst, int tail) {
-    const size_t stride = (size_t) gridDim.x * 256;
-    size_t i = (size_t) blockIdx.x * 256 + threadIdx.x;
-    for (; i + 3 * stride < n16; i += 4 * stride) {
-        const uint4 a = src[i], b = src[i + stride], c = src[i + 2 * stride], d = src[i + 3 * stride];
-        dst[i] = a; dst[i + stride] = b; dst[i + 2 * stride] = c; dst[i + 3 * stride] = d;
-    }
-    for (; i < n16; i += stride) dst[i] = src[i];
-    if (blockIdx.x == 0 && (int) threadIdx.x < tail) tdst[threadIdx.x] = tsrc[threadIdx.x];
-}
-void copy_thin(const void * src, void * dst, size_t bytes, int wgs, hipStream_t st) {
-    if (!bytes) return;
-    const size_t n16 = bytes / 16; const int tail = (int) (bytes - n16 * 16);
-    hipLaunchKernelGGL(k_copy_thin, dim3(wgs < 1 ? 1 : wgs), dim3(256), 0, st, (const uint4 *) src, (uint4 *) dst, n16,
-                       (const unsigned char *) src + n16 * 16, (unsigned char *) dst + n16 * 16, tail);
 }
 
 void downmix_stereo(const float * frames, int n_frames, float * out, hipStream_t st) {

@@ -559,13 +559,9 @@ void qgemm_tile(const GemmArgs & a, Q8Rows A, const uint8_t * Wt, hipStream_t st
     // 64-row tiles: 158 VGPRs, three workgroups per CU with a 3-deep ring (53 KB of LDS each): the per-block scaling is a chain
     // MFMA -> 48 VALU per fragment, so a SIMD wants several wavefronts to interleave; 128-row tiles (256 VGPRs, two per CU) only
     // where the grid is large enough to keep them busy anyway
-    static const int force_bm = getenv("WMI_QGEMM_BM") ? atoi(getenv("WMI_QGEMM_BM")) : 0;       // A/B knobs
-    static const int nst64 = getenv("WMI_QGEMM_NST") ? atoi(getenv("WMI_QGEMM_NST")) : 3;
     const long t128 = (long) ((a.M + 127) / 128) * (a.N / 128);
-    const bool big = force_bm ? force_bm == 128 : t128 >= 1536;
-    if (big) launch_qgemm<QT, 128, EPI, 3>(a, A, Wt, st);
-    else if (nst64 == 4) launch_qgemm<QT, 64, EPI, 4>(a, A, Wt, st);
-    else launch_qgemm<QT, 64, EPI, 3>(a, A, Wt, st);
+    if (t128 >= 1536) launch_qgemm<QT, 128, EPI, 3>(a, A, Wt, st);
+    else              launch_qgemm<QT, 64, EPI, 3>(a, A, Wt, st);
 }
 
 template <int QT>
@@ -763,9 +759,6 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 && NR4 == 1) ? 4 : 1) void k_qrow
             }
         } else                                               // few rows: a (row, slice) task per wavefront, the row's statistics recomputed by each
         for (int task = wave; task < n * nsl; task += NW) {
-#ifdef WMI_QROWS_PROBE
-            if (a.stamps && !tm1) tm1 = wall_clock64();          // (probe build) mark 1 = the prologue's code has been reached
-#endif
             const int r = n == 1 ? 0 : task / nsl, sl = task - r * nsl;
             const int src = a.rows ? a.rows[r] : r;
             const float * xr = a.x32 + (size_t) src * K;
@@ -790,9 +783,6 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 && NR4 == 1) ? 4 : 1) void k_qrow
                 else v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
             }
             _Pragma("unroll") for (int o = 32; o > 0; o >>= 1) sum += WMI_SHX(sum, o);
-#ifdef WMI_QROWS_PROBE
-            if (a.stamps && !tm2) { asm volatile("" :: "v"(sum)); tm2 = wall_clock64(); }      // (probe build) mark 2 = the row has arrived
-#endif
             const float mean = sum / (float) K;
             float sqs = 0.0f;
 #pragma unroll
@@ -874,9 +864,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 && NR4 == 1) ? 4 : 1) void k_qrow
     // scale slots of absent rows: finite zeros (they are multiplied, never stored)
     if (n < R8) for (int e = tid; e < nb * R8; e += NT) { if ((e % R8) >= n) { sd[e] = 0.0f; ss[e] = 0.0f; } }
     __syncthreads();
-#ifndef WMI_QROWS_PROBE
     if (a.stamps) tm1 = wall_clock64();
-#endif
 
     const int arow = (lane & 31) < n ? (lane & 31) : 0;     // activation row this lane feeds the MFMA with
     const int fk = lane >> 5;
@@ -1194,8 +1182,7 @@ void launch_qrows(const GemvArgs & a, const float * a32, const uint8_t * Wt, hip
     // The vocabulary projection (1 621 row groups): as many workgroups as are resident at once (124 VGPRs x 8 wavefronts: two per CU; 164 x 4:
     // three), each walking its groups with the next group's tiles in flight — with 1 024 workgroups the second round paid the prologue
     // (LayerNorm + quantiser, ~4 us) again behind the first.
-    static const int cap_env = getenv("WMI_QROWS_BLOCKS") ? atoi(getenv("WMI_QROWS_BLOCKS")) : 0;      // A/B knob
-    const int cap = cap_env > 0 ? cap_env : NW == 4 ? 768 : NW == 8 ? 512 : 256;
+    const int cap = NW == 4 ? 768 : NW == 8 ? 512 : 256;
     int blocks = ngroups; if (blocks > cap) blocks = cap;
     if (a.ksplit > 1) blocks = ngroups * a.ksplit;            // (qrows() grants the split only where every (row group, part) gets its own workgroup)
     if (a.pf_ptr) blocks += PF_WG;                          // the prefetch workgroups (see the kernel)

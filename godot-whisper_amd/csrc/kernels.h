@@ -120,7 +120,6 @@ struct TsOut { float sum, thold; int32_t e0, e1;            // e0 = en[s0] > tho
                int32_t w_down_above_s0, w_up_below_s0, w_up_above_s1, w_down_below_s1; };   // walk results (bounds: 0, s1, n - 1, 0)
 void ts_refine(const float * en, const float * bmin, const float * bmax, int n_samples, const TsTok * in, TsOut * out, int n_tok, hipStream_t st);
 // device -> pinned host (or anywhere) by `wgs` workgroups only: a deliberately slow copy that keeps the PCIe write queue short
-void copy_thin(const void * src, void * dst, size_t bytes, int wgs, hipStream_t st);
 
 // host-adjacent DSP of the streaming node: stereo -> mono and the energy VAD, bit-identical to the host's C++
 // (src/speech_to_text.cpp:45-51, 53-104).  res = {no-activity decision, energy_all, energy_last}
@@ -360,7 +359,7 @@ bool front_usable(int S, int rows = 1);
 void front(const FrontArgs & a, hipStream_t st);
 // A/B switches of the launch paths that are read from the environment: once per process (reload_knobs(): lab scripts that flip them between
 // probe calls of one process, exported as wmi_reload_knobs — not while a transcription runs on another thread)
-struct Knobs { bool no_mlp_pair; int pair_wpb; int sa_wpb; bool gemv1_wide_generic; bool host_draws; bool debug_sync; int pair_withhold; uint32_t pair_spin_cap; bool no_front; int front_withhold; bool no_xback; int xback_withhold; int front_wpb; };
+struct Knobs { bool no_mlp_pair; int sa_wpb; bool gemv1_wide_generic; bool host_draws; bool debug_sync; int pair_withhold; uint32_t pair_spin_cap; bool no_front; int front_withhold; bool no_xback; int xback_withhold; int front_wpb; };
 const Knobs & knobs();
 void reload_knobs();
 void set_attn_one_group(bool on);              // encoder attention: never split the keys over two wave groups (bit-identical for any batch)

@@ -198,7 +198,6 @@ struct DeviceState {
     bool    energy_pending = false;                            // copy in flight: signal_energy_wait() before reading state.energy
     bool    energy_device_only = false;                        // the envelope stays in HBM: the timestamp walks run there too (ts_refine_device), nothing crosses PCIe
     void *  ts_host = nullptr;                                 // pinned block: TsTok[448] | TsOut[448] (ts_refine_device)
-    bool    energy_unflushed = false;                          // the envelope sits in the device buffer `energy`: signal_energy_flush() starts its copy to the pinned image
     // encoder activations, token-major
     __half * mel_t = nullptr;                                 // [2T+2+pad][n_mel_pad] f16, rows -1 and 2T are zero
     __half * conv1 = nullptr;                                 // [2T+2][S] f16 (row 0 and 2T+1 zero)
@@ -247,7 +246,7 @@ struct DeviceState {
     int32_t step_seq = 0;                                             // sequence number of the last greedy step launched
     // device-side draws (beam search, t > 0): decode() leaves the logits rows in d.logits, sample_rows_device() draws from them
     bool    keep_logits_on_device = false;
-    void  * draw_dev = nullptr;  void * draw_host = nullptr;          // DecStep[8] | u[8][8] | SampleOut[8][8] (device / pinned)
+    void  * draw_host = nullptr;                                   // DecStep[8] | u[8][8] | SampleOut[8][8] (pinned)
     void  * draw_scratch = nullptr;
     bool    step_capture_failed = false;                               // a failed capture is not retried
     int     step_seen_T = -1;                                          // encoder length of recent steps (StepGraph::seen counts them)
@@ -430,7 +429,6 @@ bool upload_static_ban(whisper_context & ctx, const whisper_full_params & params
 bool sample_rows_device(whisper_context & ctx, const StepFilter * f, const int * rows, int n_rows, float temperature, int k,
                         const double * u, int tid_default, whisper_token_data * out);
 bool wait_for_sample(const k::SampleOut * r, int32_t want, hipStream_t s, int32_t * status = nullptr);   // spin on a pinned, self-tagged result record (device.cpp)
-bool fast_path_enabled();
 // host worker pool (pool.cpp): fn(0..n_tasks-1) on a few persistent threads + the caller; nested calls run inline
 void pool_run(int n_tasks, const std::function<void(int)> & fn);
 double bench_greedy_step_chain(whisper_context & ctx, int iters);
@@ -445,7 +443,7 @@ struct BusyScope { int dev; bool counted; explicit BusyScope(int device); ~BusyS
 int busy_transcriptions(int device);
 // |x| envelope of the last PCM on the GPU; the D2H copy runs on a side stream while the encoder works.
 // sync = false: state.energy is valid only after signal_energy_wait()
-bool signal_energy_device(whisper_context & ctx, int hw, bool sync = true, int via_dma = 0);   // via_dma 1: kernel -> device buffer -> hipMemcpyAsync; 2: kernel -> device buffer now, signal_energy_flush() later
+bool signal_energy_device(whisper_context & ctx, int hw, bool sync = true, int via_dma = 0);
 // via_dma 3: the envelope is computed into HBM and STAYS there (lock-step calls): token_level_timestamps() asks ts_refine_device() for the
 // window sums and walks instead of reading it (15 MB of PCIe writes per 8-chunk call, ~0.3 ms of whatever runs beside them, are not made)
 bool ts_refine_device(State & st, const k::TsTok * in, int n, k::TsOut * out);
@@ -454,7 +452,6 @@ struct TsRef { State * st; int seg, j; };
 // back to) and the transcription call reports it as -9 — never silently unrefined t0 / t1
 bool flush_token_timestamps(whisper_context & ctx, State & st);      // full.cpp: the pending segments' envelope-side refinement, one device call
 bool flush_token_timestamps_of(whisper_context & ctx, const std::vector<State *> & states);    // ... of several states (lock-step chunks) in ONE device call
-bool signal_energy_flush(State & st);             // via_dma 2: a THIN copy kernel moves the envelope to the pinned image (lock-step calls: beside the decode steps)
 bool signal_energy_wait(State & st);
 
 // host logic (logits filters, sampling, driver)

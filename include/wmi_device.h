@@ -273,7 +273,7 @@ WHISPER_API int wmi_selftest_quant(int device, int qtype, int mode, const void *
  */
 WHISPER_API double wmi_bench_kernel(struct whisper_context * ctx, int which, int iters);
 
-/* The A/B switches that the launch paths read from the environment (WMI_NO_MLP_PAIR, WMI_PAIR_WPB, WMI_SA_WPB, WMI_GEMV1_WIDE_GENERIC,
+/* The A/B switches that the launch paths read from the environment (WMI_NO_MLP_PAIR, WMI_SA_WPB, WMI_GEMV1_WIDE_GENERIC,
  * WMI_HOST_DRAWS, WMI_DEBUG_SYNC, WMI_PAIR_WITHHOLD, WMI_PAIR_SPIN_CAP, WMI_NO_FRONT, WMI_FRONT_WITHHOLD, WMI_NO_XBACK, WMI_XBACK_WITHHOLD) are read ONCE per process; a lab script that flips them between
  * probe calls of one process calls this afterwards.  Not while a transcription runs on another thread. */
 WHISPER_API void wmi_reload_knobs(void);

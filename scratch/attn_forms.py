@@ -36,9 +36,6 @@ if len(sys.argv) > 1 and sys.argv[1] == "child":
     node.close()
 else:
     for form in os.environ.get("FORMS", "0 1 2").split():
-        for ks in os.environ.get("KSPLITS", "-1").split():
-            for cfg in os.environ.get("CFGS", "0").split():
-                env = dict(os.environ, WMI_ATTN_FORM=form, WMI_ATTN_KSPLIT=ks)
-                if cfg != "0": env["WMI_ATTN_CFG"] = cfg
-                print("WMI_ATTN_FORM=%s WMI_ATTN_KSPLIT=%s WMI_ATTN_CFG=%s" % (form, ks, cfg), flush=True)
-                subprocess.run([sys.executable, __file__, "child"], env=env)
+        env = dict(os.environ, WMI_ATTN_FORM=form)
+        print("WMI_ATTN_FORM=%s" % form, flush=True)
+        subprocess.run([sys.executable, __file__, "child"], env=env)

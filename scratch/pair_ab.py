@@ -22,11 +22,10 @@ for shape in os.environ.get("SHAPES", "base.en,tiny.en").split(","):
         libc.unsetenv(b"WMI_SA_WPB"); res["sa8"].append(lib.wmi_bench_kernel(node.ctx, 20, 300))
         libc.setenv(b"WMI_SA_WPB", b"4", 1); res["sa4"].append(lib.wmi_bench_kernel(node.ctx, 20, 300)); libc.unsetenv(b"WMI_SA_WPB")
     print(shape, "step chain us | self-attention + out on 8 wavefronts (one head each):", " ".join("%.2f" % v for v in res["sa8"]), "| 4 wavefronts:", " ".join("%.2f" % v for v in res["sa4"]), flush=True)
-    res = {"pair8": [], "pair4": [], "two": []}
+    res = {"pair": [], "two": []}
     for rep in range(5):
-        libc.unsetenv(b"WMI_NO_MLP_PAIR"); libc.unsetenv(b"WMI_PAIR_WPB"); res["pair8"].append(lib.wmi_bench_kernel(node.ctx, 20, 300))
-        libc.setenv(b"WMI_PAIR_WPB", b"4", 1); res["pair4"].append(lib.wmi_bench_kernel(node.ctx, 20, 300)); libc.unsetenv(b"WMI_PAIR_WPB")
+        libc.unsetenv(b"WMI_NO_MLP_PAIR"); res["pair"].append(lib.wmi_bench_kernel(node.ctx, 20, 300))
         libc.setenv(b"WMI_NO_MLP_PAIR", b"1", 1); res["two"].append(lib.wmi_bench_kernel(node.ctx, 20, 300))
     libc.unsetenv(b"WMI_NO_MLP_PAIR")
-    print(shape, "step chain us | one launch per MLP, 8-wavefront workgroups:", " ".join("%.2f" % v for v in res["pair8"]), "| 4-wavefront:", " ".join("%.2f" % v for v in res["pair4"]), "| two launches:", " ".join("%.2f" % v for v in res["two"]), flush=True)
+    print(shape, "step chain us | one launch per MLP:", " ".join("%.2f" % v for v in res["pair"]), "| two launches:", " ".join("%.2f" % v for v in res["two"]), flush=True)
     node.close()

@@ -58,17 +58,14 @@ lib.wmi_bench_kernel.restype = C.c_double
 libc = C.CDLL(None)
 libc.setenv(b"WMI_STEP_MASK", b"0x1ff", 1)
 print("whole step chain (graph, non-chained form): %.1f us" % lib.wmi_bench_kernel(node.ctx, 20, 200))
-# per-kind chains with several copies per graph (a 6-launch graph is bounded by the replay itself)
+# per-kind chains
 if os.environ.get("KINDS"):
     kinds = [("qkv (LN)", 2, 6), ("self-attn + out", 4, 6), ("cross-attention (fused)", 8, 6), ("combine + cross out", 16, 6),
              ("mlp.0 (LN, GELU)", 32, 6), ("mlp.2 (K = 4S)", 64, 6), ("logits", 128, 1), ("filters (2 kernels)", 256, 2)]
-    for reps in (1, 8):
-        libc.setenv(b"WMI_CHAIN_REPS", str(reps).encode(), 1)
-        for name, m, n in kinds:
-            libc.setenv(b"WMI_STEP_MASK", str(m).encode(), 1)
-            t = lib.wmi_bench_kernel(node.ctx, 20, 96)
-            print("reps/graph %d  %-24s %6.1f us per step = %5.2f us per launch" % (reps, name, t, t / n))
-    libc.unsetenv(b"WMI_CHAIN_REPS")
+    for name, m, n in kinds:
+        libc.setenv(b"WMI_STEP_MASK", str(m).encode(), 1)
+        t = lib.wmi_bench_kernel(node.ctx, 20, 96)
+        print("%-24s %6.1f us per step = %5.2f us per launch" % (name, t, t / n))
 # host-paced: decode time per token inside whisper_full
 t6 = (C.c_int64 * 6)(); n5 = (C.c_int32 * 5)()
 lib.whisper_reset_timings(node.ctx)
