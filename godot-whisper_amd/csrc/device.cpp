@@ -818,9 +818,9 @@ static unsigned greedy_step_forms(whisper_context & ctx, int Tc, bool long_kv, b
     // the MLP form is decided once for the whole step: the paired launches' tags alternate between two words from launch to launch (an even
     // number of layers keeps that up across steps), so either every layer pairs or none does
     const bool paired = (M & 32) && (M & 64) && !kn.no_mlp_pair && solo && d.mlp_hand && (Lt & 1) == 0 && k::mlp_pair_usable(S, chained);
-    // the same decision for the front of the layers (k::front): short caches only; its status goes through the MLP pair's word, so it
-    // runs where that pair does (the pick kernel reports the word, a fault re-runs the step without either)
-    const bool fronted = paired && !long_kv && (M & 2) && (M & 4) && !kn.no_front && k::front_usable(S);
+    // the same decision for the front of the layers (k::front), for the form this cache length takes; its status goes through the MLP
+    // pair's word, so it runs where that pair does (the pick kernel reports the word, a fault re-runs the step without either)
+    const bool fronted = paired && (M & 2) && (M & 4) && !kn.no_front && k::front_usable(S, 1, long_kv ? hp.n_text_ctx : 0);
     const bool backed = paired && (M & 8) && (M & 16) && !kn.no_xback && k::xback_usable(S, H, Tc);
     return (paired ? STEP_FORM_PAIRED : 0u) | (fronted ? STEP_FORM_FRONTED : 0u) | (backed ? STEP_FORM_BACKED : 0u);
 }
@@ -865,7 +865,7 @@ static void enqueue_greedy_step(whisper_context & ctx, int Tc, bool long_kv = fa
             f.gq = (unsigned long long *) ((unsigned char *) d.mlp_hand + (size_t) 16 * S + 64); f.ga = f.gq + 3 * S / 2;
             f.epoch = (uint32_t *) d.mlp_arrive + 2; f.par = il & 1; f.fault = (uint32_t *) d.mlp_arrive + PAIR_FAULT_WORD;
             f.spin_cap = kn.pair_spin_cap; f.withhold = kn.front_withhold;
-            k::front(f, s); chk("front", il);
+            k::front(f, s, long_kv); chk("front", il);
         } else {
         if (M & 2) gv(k::EPI_QKV_DEC, l.ln1_g, l.ln1_b, nullptr, S, 3 * S, l.w_qkv, l.b_qkv, d.dq, S, nullptr, ck, cv, kq_scale, &stp->kv_head); chk("qkv", il);
         if ((M & 4) && long_kv) {
@@ -1003,6 +1003,7 @@ bool decode_greedy_step(whisper_context & ctx, int32_t token, int32_t pos, const
     int seen_all = 0; for (const auto & g2 : d.step_graphs) seen_all += g2.seen;
     const bool capture_now = use_graph && !exec && !d.step_capture_failed && seen_all > 64;
     if (capture_now) {
+        (void) greedy_step_forms(ctx, Tc, long_kv, chained, solo);      // (the forms' occupancy queries, cached from here on: not inside the capture)
         // first use: run once eagerly (lets the launchers set their function attributes), then capture
         // (not for the chained form: a step's pick kernel advances the device-side record, so the step must not run twice — and its
         // kernels are the plain form's, which has run many times by now)

@@ -1937,12 +1937,18 @@ __global__ __launch_bounds__(64 * WPB) void k_mlp_pair(const MlpPairArgs a, floa
 //   phase 3 = k_gemv1<2, 1, false, 2, EPI_F32_BIAS_RESID, 1, 8>'s projection on S / 16 of the workgroups: the attention row swept once
 //             per workgroup (S / 2 granules), weights / bias / residual requested at the start of the launch.
 // Per value the operations and their order are the two launches': bit-identical (tests/test_gpu_variants.py).  Caches of <= 64 cells
-// (the caller keeps the two launches beyond), S <= 1024 (NCH chunks of 512 columns per row), one head per 64 columns.  Tags, bounded spins and the status word: k_mlp_pair's
+// (beyond: the LONG form below), S <= 1024 (NCH chunks of 512 columns per row), one head per 64 columns.  Tags, bounded spins and the status word: k_mlp_pair's
 // (MlpPairArgs); the phase-3 store overwrites x only after every phase-1 wavefront has consumed it (it cannot gather its row before).
 // WPB wavefronts per workgroup: 8 (3 S / 32 workgroups, phase 3 with two rows per wavefront) or 4 (3 S / 16 workgroups, four rows per
 // wavefront: k_gemv1<4, ...>'s halving sum, the same bits) — S / 16 workgroups sweep the attention row either way
-template <int NCH, int WPB>
+// LONG (one row, WPB = 4; the host picks it for caches of more than 64 cells): phase 2 of head h on all four wavefronts of workgroup h with
+// k_self_attn_rows_long's arithmetic, operation for operation — one key per thread, exact maximum, l per thread in key order, P.V in four
+// contiguous quarters — what the three launches (k_gemv1, k_self_attn_rows_long, k_gemv1) compute for such a cache.  The cell at the
+// step's slot is never taken from the cache (other workgroups of this launch write it): its k / v are the granules'.  Dynamic LDS:
+// front_long_lds(cap) bytes.  Phases 1 and 3 are the short form's.
+template <int NCH, int WPB, bool LONG = false>
 __global__ __launch_bounds__(64 * WPB) void k_front(const FrontArgs a_in, const Stamp sp) {
+    static_assert(!LONG || WPB == 4, "the long form's quarters are four wavefronts");
     // lock-step rows: row y is a one-row problem of its own (k_gemv1's convention): shift the per-row operands, everything below is the one-row kernel
     FrontArgs a = a_in;
     {
@@ -1973,6 +1979,13 @@ __global__ __launch_bounds__(64 * WPB) void k_front(const FrontArgs a_in, const 
     //  the CUs' address pipes in front of the late wavefronts' rows: LayerNorm done 0.3 - 0.5 us later)
     const int g = lane >> 3, o8 = lane & 7;
     uint4 kv[1][8], vv[1][8];
+    if constexpr (LONG) {                                    // every thread of a head workgroup: its first key, j = tid (k_self_attn_rows_long's order)
+        if (wg < H) {
+            const int jc = tid < a.cap ? tid : 0;
+#pragma unroll
+            for (int c8 = 0; c8 < 8; ++c8) kv[0][c8] = *(const uint4 *) (a.ck + (size_t) jc * K + wg * 64 + c8 * 8);
+        }                                                    // (read under wg < H only: the other workgroups leave them unset)
+    } else
     if (head_wave) {
 #pragma unroll
         for (int t = 0; t < 4; ++t) {                        // keys [0, 32) (self_attn_wave's first batch)
@@ -2070,6 +2083,115 @@ __global__ __launch_bounds__(64 * WPB) void k_front(const FrontArgs a_in, const 
     const uint32_t spin_cap = a.spin_cap ? a.spin_cap : (1u << 20);
     typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
     unsigned long long tm2 = 0;
+    // ---- phase 2, long caches: this workgroup's head, on its four wavefronts (k_self_attn_rows_long's steps; every branch and barrier
+    // below is uniform across the workgroup)
+    if constexpr (LONG) {
+      if (wg < H) {
+        extern __shared__ __attribute__((aligned(16))) unsigned char front_smem[];
+        float * row = (float *) front_smem;                 // [cap, rounded up to 4] scores -> probabilities of this head
+        float * part = row + ((a.cap + 3) & ~3);            // [4][64] partial outputs
+        float * red = part + 256;                           // [4]
+        const int h = wg;
+        if (wave == 0) {                                    // the head's q, k, v granules -> hq (the short form's gather)
+            const int part3 = lane >> 4;
+            const unsigned long long * src = a.gq + (lane < 48 ? part3 * (S >> 1) + 32 * h + (lane & 15) * 2 : 32 * h);
+            uint32_t spins = 0; bool landed = false; u32x4 q;
+            for (; spins < spin_cap; ++spins) {
+                asm volatile("global_load_dwordx4 %0, %1, off sc0 sc1\n\ts_waitcnt vmcnt(0)" : "=&v"(q) : "v"(src) : "memory");
+                const bool ok = lane >= 48 || (q[1] == tag && q[3] == tag);
+                if (__all(ok)) { landed = true; break; }
+            }
+            if (lane == 0 && (!landed || spins > PAIR_SLOW_POLLS))
+                __hip_atomic_fetch_or(a.fault, landed ? PAIR_SLOW : PAIR_FAULT_TIMEOUT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (lane < 48) *(uint2 *) (hq + part3 * 64 + (lane & 15) * 4) = make_uint2(q[0], q[2]);
+        }
+        __syncthreads();
+        const int n_kv = min(__builtin_amdgcn_readfirstlane(nkv_pre), a.cap), slot = __builtin_amdgcn_readfirstlane(ro_pre);
+        const __half * sk = a.ck + h * 64, * sv = a.cv + h * 64;
+        float m = -INFINITY;
+        for (int j = tid; j < n_kv; j += 256) {
+            uint4 u[8];
+            if (j == slot) {                                // this step's key: the granules' bits, the ones phase 1 sends to the cache
+#pragma unroll
+                for (int c8 = 0; c8 < 8; ++c8) u[c8] = *(const uint4 *) (hq + 64 + c8 * 8);
+            } else if (j < 256) {                           // requested at the top of the launch
+#pragma unroll
+                for (int c8 = 0; c8 < 8; ++c8) u[c8] = kv[0][c8];
+            } else {
+                const uint4 * kp = (const uint4 *) (sk + (size_t) j * K);
+#pragma unroll
+                for (int c8 = 0; c8 < 8; ++c8) u[c8] = kp[c8];
+            }
+            float dot = 0.0f;
+#pragma unroll
+            for (int c8 = 0; c8 < 8; ++c8) {
+                const uint4 q4 = *(const uint4 *) (hq + c8 * 8);
+                const __half2 * hh = (const __half2 *) &u[c8], * qh = (const __half2 *) &q4;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float2 f = __half22float2(hh[e]), q2 = __half22float2(qh[e]);
+                    dot = fmaf(f.x, q2.x, dot);
+                    dot = fmaf(f.y, q2.y, dot);
+                }
+            }
+            row[j] = dot;
+            m = fmaxf(m, dot);
+        }
+        // P.V's values do not wait for the probabilities: this wavefront's quarter of the keys, the first VB of them requested here, the
+        // next VB while a batch is multiplied (k_self_attn_rows_long asks for eight at a time behind the soft-max: one memory round
+        // trip per eight keys, 14 of them in a row at 448 cells; 16 ahead against 8 at the point of use was not measured on its own).
+        // The sums are its sums: ascending keys, one fmaf chain per column
+        constexpr int VB = 16;
+        const int per = (n_kv + 3) >> 2, j0 = wave * per, j1 = min(n_kv, j0 + per);
+        const __half * vp = sv + lane;
+        __half vh[VB];
+#pragma unroll
+        for (int t = 0; t < VB; ++t) vh[t] = vp[(size_t) (j0 + t < j1 ? j0 + t : max(j1 - 1, 0)) * K];
+        _Pragma("unroll") for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, WMI_SHX(m, o));
+        if (lane == 0) red[wave] = m;
+        __syncthreads();
+        m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+        __syncthreads();                                    // red is reused for the sums
+        float l = 0.0f;
+        for (int j = tid; j < n_kv; j += 256) { const float e = round_f16(expf(round_f16(row[j] - m))); row[j] = e; l += e; }
+        _Pragma("unroll") for (int o = 32; o > 0; o >>= 1) l += WMI_SHX(l, o);
+        if (lane == 0) red[wave] = l;
+        __syncthreads();
+        const float inv = (float) (1.0 / (double) ((red[0] + red[1]) + (red[2] + red[3])));
+        for (int j = tid; j < n_kv; j += 256) row[j] = round_f16(row[j] * inv);
+        __syncthreads();
+        {
+            const __half vnew = hq[128 + lane];
+            float acc = 0.0f;
+            for (int j = j0; j < j1; j += VB) {
+                const bool more = j + VB < j1;
+                __half vn[VB];                              // the next batch, in flight while this one is multiplied
+                if (more) {
+#pragma unroll
+                    for (int t = 0; t < VB; ++t) vn[t] = vp[(size_t) (j + VB + t < j1 ? j + VB + t : j1 - 1) * K];
+                }
+#pragma unroll
+                for (int t = 0; t < VB; ++t) if (j + t < j1) acc = fmaf(row[j + t], __half2float(j + t == slot ? vnew : vh[t]), acc);
+                if (more) {
+#pragma unroll
+                    for (int t = 0; t < VB; ++t) vh[t] = vn[t];
+                }
+            }
+            part[wave * 64 + lane] = acc;
+        }
+        __syncthreads();
+        if (wave == 0) {
+            const float acc = (part[lane] + part[64 + lane]) + (part[128 + lane] + part[192 + lane]);
+            const uint32_t mine = (uint32_t) __half_as_ushort(f2h(acc));
+            const uint32_t other = (uint32_t) WMI_SHX((int) mine, 1);
+            if (!(lane & 1)) {
+                const unsigned long long gr = ((unsigned long long) tag << 32) | (unsigned long long) (mine | (other << 16));
+                __hip_atomic_store(a.ga + (h * 32 + (lane >> 1)), gr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+        tm2 = stamp_t0(sp.base);
+      }
+    } else
     // ---- phase 2: this workgroup's head, on wavefront 0
     if (head_wave) {
         const int h = wg;
@@ -2116,6 +2238,9 @@ __global__ __launch_bounds__(64 * WPB) void k_front(const FrontArgs a_in, const 
     }
     // ---- phase 3: the attention row, swept once per workgroup; two rows per wavefront
     if (p3) {
+        // (long caches: the heads' phase 2 is linear in the cells — scores, soft-max and P.V each walk them — so the polls after which the
+        //  wait for its row counts as slow are too: the short form's 64 for every 64 cells beyond its own)
+        const uint32_t slow_polls = LONG ? PAIR_SLOW_POLLS * (1u + (uint32_t) (__builtin_amdgcn_readfirstlane(nkv_pre) >> 6)) : PAIR_SLOW_POLLS;
         if (tid < (S >> 2)) {
             const unsigned long long * src = a.ga + tid * 2;
             uint32_t spins = 0; bool landed = false; u32x4 q;
@@ -2124,7 +2249,7 @@ __global__ __launch_bounds__(64 * WPB) void k_front(const FrontArgs a_in, const 
                 const bool ok = q[1] == tag && q[3] == tag;
                 if (__all(ok)) { landed = true; break; }
             }
-            if (lane == 0 && (!landed || spins > PAIR_SLOW_POLLS))
+            if (lane == 0 && (!landed || spins > slow_polls))
                 __hip_atomic_fetch_or(a.fault, landed ? PAIR_SLOW : PAIR_FAULT_TIMEOUT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             *(uint2 *) (act + tid * 4) = make_uint2(q[0], q[2]);
         }
@@ -2258,25 +2383,53 @@ void mlp_pair(const MlpPairArgs & a, float * x_inout, hipStream_t st) {
 // wavefronts per workgroup: four for one row (eight-wavefront workgroups get going ~0.7 us later: LayerNorm done + 2.1 - 2.3 us against
 // + 1.9 - 2.0, decode 141.2 -> 137.5 us per token), eight for lock-step rows (half as many workgroups to keep resident; measured with eight)
 static int front_wpb(int rows) { return rows > 1 ? 8 : (knobs().front_wpb == 8 ? 8 : 4); }
-bool front_usable(int S, int rows) {
+// dynamic LDS of the long-cache form: the score row (cap floats, rounded up to 16 bytes), 4 x 64 partial outputs, 4 reduction words
+static size_t front_long_lds(int cap) { return sizeof(float) * (size_t) (((cap + 3) & ~3) + 256 + 4); }
+bool front_usable(int S, int rows, int long_cap) {
     // <= two 512-column chunks per row, one head per 64 columns, every workgroup of the launch resident at once (they wait for each other)
     if (S > 1024 || (S % 64) != 0 || S < 128) return false;
-    static std::atomic<int> cache[64][2][2];
     int dev = 0; (void) hipGetDevice(&dev);
     const int wide = S > 512 ? 1 : 0, wpb = front_wpb(rows), w8 = wpb == 8 ? 1 : 0;
-    int v = cache[dev & 63][wide][w8].load(std::memory_order_relaxed);
-    if (v == 0) {
+    auto resident = [&](const void * fn, size_t lds) {
         int cus = 0, nb = 0;
         (void) hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        const void * fn = wpb == 4 ? (wide ? (const void *) k_front<2, 4> : (const void *) k_front<1, 4>) : (wide ? (const void *) k_front<2, 8> : (const void *) k_front<1, 8>);
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, 64 * wpb, 0) != hipSuccess) nb = 0;
-        v = 1 + std::max(0, (cus - 1) * std::min(nb, 2));       // workgroups resident at once, one CU left to others (two per CU at most counted)
-        cache[dev & 63][wide][w8].store(v, std::memory_order_relaxed);
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, 64 * wpb, lds) != hipSuccess) nb = 0;
+        return 1 + std::max(0, (cus - 1) * std::min(nb, 2));    // workgroups resident at once, one CU left to others (two per CU at most counted)
+    };
+    int v;
+    if (long_cap > 0) {
+        // the long-cache form: one row on four-wavefront workgroups only (with WMI_FRONT_WPB=8 long caches keep the three launches), its
+        // LDS within what a workgroup may ask for without further ado; the occupancy is this instantiation's with this cache's LDS
+        if (rows > 1 || wpb != 4 || front_long_lds(long_cap) > 48 * 1024) return false;
+        static std::atomic<long long> lcache[64][2][4];          // (cap << 32) | workgroups: the first four cache sizes asked about per device
+        v = 0;
+        for (auto & e : lcache[dev & 63][wide]) {
+            long long c = e.load(std::memory_order_acquire);
+            if (c == 0) {                                        // a free entry: this cap's (a race for it loses nothing but the entry)
+                const long long mine = ((long long) long_cap << 32) | resident(wide ? (const void *) k_front<2, 4, true> : (const void *) k_front<1, 4, true>, front_long_lds(long_cap));
+                if (e.compare_exchange_strong(c, mine, std::memory_order_acq_rel)) c = mine;
+            }
+            if ((int) (c >> 32) == long_cap) { v = (int) (c & 0xffffffffll); break; }
+        }
+        if (v == 0) v = resident(wide ? (const void *) k_front<2, 4, true> : (const void *) k_front<1, 4, true>, front_long_lds(long_cap));      // (a fifth size: asked every time)
+    } else {
+        static std::atomic<int> cache[64][2][2];
+        v = cache[dev & 63][wide][w8].load(std::memory_order_relaxed);
+        if (v == 0) {
+            v = resident(wpb == 4 ? (wide ? (const void *) k_front<2, 4> : (const void *) k_front<1, 4>) : (wide ? (const void *) k_front<2, 8> : (const void *) k_front<1, 8>), 0);
+            cache[dev & 63][wide][w8].store(v, std::memory_order_relaxed);
+        }
     }
     return (3 * S / (wpb == 4 ? 16 : 32)) * std::max(rows, 1) <= v - 1;
 }
-void front(const FrontArgs & a, hipStream_t st) {
+void front(const FrontArgs & a, hipStream_t st, bool long_kv) {
     const int rows = a.rows > 1 ? a.rows : 1;
+    if (long_kv) {                                          // (front_usable(S, 1, cap): one row, four wavefronts)
+        const dim3 grid(3 * a.S / 16, 1);
+        const size_t lds = front_long_lds(a.cap);
+        if (a.S <= 512) hipLaunchKernelGGL((k_front<1, 4, true>), grid, dim3(256), lds, st, a, stamp_next());
+        else            hipLaunchKernelGGL((k_front<2, 4, true>), grid, dim3(256), lds, st, a, stamp_next());
+    } else
     if (front_wpb(rows) == 4) {
         const dim3 grid(3 * a.S / 16, rows);
         if (a.S <= 512) hipLaunchKernelGGL((k_front<1, 4>), grid, dim3(256), 0, st, a, stamp_next());

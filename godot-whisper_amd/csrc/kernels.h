@@ -326,7 +326,7 @@ constexpr uint32_t PAIR_SLOW_POLLS = 64;
 bool mlp_pair_usable(int S, bool with_mirror);
 void mlp_pair(const MlpPairArgs & a, float * x_inout, hipStream_t st);
 // The front of a decoder layer of the one-row step as one launch (k_dec.hip: k_front): LayerNorm + q|k|v with EPI_QKV_DEC's stores, the
-// self-attention over a cache of <= 64 cells computed once per head, the out projection + residual (in place: xout = x).  gq: 3 S / 2
+// self-attention over the cache computed once per head (a form for <= 64 cells, one for longer caches), the out projection + residual (in place: xout = x).  gq: 3 S / 2
 // granules, ga: S / 2 granules (8 bytes each, zeroed once); epoch / par / fault / spin_cap / withhold as in MlpPairArgs (own epoch words).
 struct FrontArgs {
     const float * x; float * xout; const float * ln_g, * ln_b; float eps; int S;
@@ -355,8 +355,9 @@ struct XbackArgs {
 constexpr int XBACK_ROW_GRANULES = 8 * 8 * 66 + 256;        // a row's partials (<= 8 heads x 8 slices x 66) + its attention row (S / 2 <= 256)
 bool xback_usable(int S, int H, int T, int rows = 1);
 void xback(XbackArgs a, int H, float * scratch, hipStream_t st);
-bool front_usable(int S, int rows = 1);
-void front(const FrontArgs & a, hipStream_t st);
+// long_cap > 0: the long-cache form (caches of more than 64 cells, one row) for a cache of long_cap cells; front(): long_kv launches it
+bool front_usable(int S, int rows = 1, int long_cap = 0);
+void front(const FrontArgs & a, hipStream_t st, bool long_kv = false);
 // A/B switches of the launch paths that are read from the environment: once per process (reload_knobs(): lab scripts that flip them between
 // probe calls of one process, exported as wmi_reload_knobs — not while a transcription runs on another thread)
 struct Knobs { bool no_mlp_pair; int sa_wpb; bool gemv1_wide_generic; bool host_draws; bool debug_sync; int pair_withhold; uint32_t pair_spin_cap; bool no_front; int front_withhold; bool no_xback; int xback_withhold; int front_wpb; };

@@ -220,8 +220,8 @@ WHISPER_API double wmi_selftest_proj(struct whisper_context * ctx, int op, int n
  * slot bookkeeping is whisper_decode's, so both may be mixed.  logits (optional): the step's raw logits, n_vocab floats; out: the token
  * the device picked (id, tid, p, plog, pt, ptsum); forms (optional): the launch form the step took, a bit set —
  *   1 cache longer than 64 cells, 2 chained onto the previous step's pick, 4 replayed from a captured graph, 8 both MLP projections as
- *   one launch, 16 the front of each layer as one launch, 32 the cross-attention back as one launch, 64 re-run after a failed in-launch
- *   hand-off, 128 a slow hand-off was reported, 256 the block-quantised step.
+ *   one launch, 16 the front of each layer as one launch (together with 1: that launch's long-cache form), 32 the cross-attention back
+ *   as one launch, 64 re-run after a failed in-launch hand-off, 128 a slow hand-off was reported, 256 the block-quantised step.
  * Returns 0, or a negative value on error. */
 WHISPER_API int wmi_selftest_greedy_step(struct whisper_context * ctx, whisper_token token, int pos, float * logits, whisper_token_data * out,
                                          int * forms);
