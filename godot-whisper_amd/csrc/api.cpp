@@ -493,6 +493,100 @@ int wmi_selftest_greedy_step(struct whisper_context * ctx, whisper_token token, 
     return 0;
 }
 
+// the product's logit-filter launches on caller logits: the step records come from make_step_filter (parameters + history, as full() and
+// wmi_full_batch build them), the static ban from upload_static_ban.  Every argument check and the "takes the fused path" check of mode 1
+// run before the first device call; the device memory is the hook's own and is released on every way out.
+int wmi_selftest_filters(struct whisper_context * ctx, struct whisper_full_params params, int mode, int n_rows, const float * logits,
+                         const whisper_token * hist, const int * n_hist, const int * has_ts, const int * seek_delta, float temperature,
+                         const void * W, const float * x, int K, float * logits_out, const double * u, int k, int tid_default,
+                         whisper_token_data * out) {
+    if (!ctx || !ctx->state || !out || !n_hist || !has_ts || !seek_delta || mode < 0 || mode > 2) return -1;
+    if (mode == 0 && (n_rows < 1 || n_rows > 16 || !logits)) return -1;
+    if (mode == 1 && (n_rows != 1 || !W || !x || !logits_out || K <= 0)) return -1;
+    if (mode == 2 && (n_rows < 1 || n_rows > 8 || k < 1 || k > 8 || !logits || !u)) return -1;
+    if (mode != 2) k = 1;
+    for (int r = 0; r < n_rows; ++r) if (n_hist[r] < 0 || (n_hist[r] > 0 && !hist)) return -1;
+    const Vocab & v = ctx->model.vocab; const HParams & hp = ctx->model.hp;
+    const int NV = v.n_vocab;
+    k::GemvArgs g{};
+    if (mode == 1) {                                      // the vocabulary projection of the greedy step (device.cpp), on the caller's matrix
+        static const float one = 1.0f; static k::FsPartial none;
+        g.ln_g = &one; g.fs_part = &none;               // placeholders: the dispatch looks at presence only
+        g.eps = hp.eps; g.n = 1; g.K = K; g.N = NV; g.epi = k::EPI_LOGITS; g.ldc = NV; g.ldr = K; g.ldaux = K; g.ldaux2 = K; g.S = K;
+        if (k::gemv_fused_parts(g) <= 0) return -4;
+    }
+    CtxScope lk(ctx);
+    if (!compute_ready(*ctx, __func__)) return -2;
+    struct DevBufs {
+        std::vector<void *> p;
+        ~DevBufs() { for (void * q : p) (void) hipFree(q); }
+        void * get(size_t bytes) { void * q = nullptr; if (!HIP_OK(hipMalloc(&q, bytes))) return nullptr; p.push_back(q); return q; }
+    } bufs;
+    try {
+        (void) hipSetDevice(ctx->device);
+        if (!upload_static_ban(*ctx, params)) return -3;
+        DeviceState & d = ctx->state->dev;
+        hipStream_t s = d.stream;
+        int space_id = -1; { auto sp = v.token_to_id.find(" "); if (sp != v.token_to_id.end()) space_id = sp->second; }
+        std::vector<k::DecStep> steps(n_rows);
+        const whisper_token * hp_ = hist;
+        for (int r = 0; r < n_rows; ++r) {
+            Decoder dec;
+            for (int i = 0; i < n_hist[r]; ++i) dec.sequence.tokens.push_back(whisper_token_data{ hp_[i], 0, 0.f, 0.f, 0.f, 0.f, -1, -1, 0.f });
+            hp_ += n_hist[r];
+            dec.has_ts = has_ts[r] != 0; dec.seek_delta = seek_delta[r];
+            const StepFilter f = make_step_filter(v, hp, params, dec);
+            k::DecStep & st = steps[r];
+            memset(&st, 0, sizeof(st));
+            st.flags = (f.ban_blank ? 1 : 0) | (f.last_ts ? 2 : 0) | (f.penult_ts ? 4 : 0);
+            st.space_id = space_id; st.eot = v.eot; st.beg = v.beg; st.n_vocab = NV;
+            st.ts_floor_end = f.ts_floor_end; st.ts_initial_start = f.ts_initial_start;
+            st.seq = 1; st.temperature = temperature > 0.0f ? temperature : 0.0f;
+        }
+        const size_t n_out = (size_t) n_rows * k;
+        float * d_logits = (float *) bufs.get((size_t) n_rows * NV * 4);
+        k::DecStep * d_step = (k::DecStep *) bufs.get((size_t) n_rows * sizeof(k::DecStep));
+        k::SampleOut * d_out = (k::SampleOut *) bufs.get(n_out * sizeof(k::SampleOut));
+        void * scratch = bufs.get(k::filter_draw_scratch_bytes(n_rows));
+        if (!d_logits || !d_step || !d_out || !scratch) return -3;
+        bool ok = HIP_OK(hipMemcpyAsync(d_step, steps.data(), (size_t) n_rows * sizeof(k::DecStep), hipMemcpyHostToDevice, s)) &&
+                  HIP_OK(hipMemsetAsync(d_out, 0, n_out * sizeof(k::SampleOut), s));
+        if (ok && mode != 1) ok = HIP_OK(hipMemcpyAsync(d_logits, logits, (size_t) n_rows * NV * 4, hipMemcpyHostToDevice, s));
+        if (!ok) return -3;
+        if (mode == 0) {
+            k::filter_argmax(d_logits, d.ban_dev, d_step, d_out, scratch, s, nullptr, n_rows, nullptr, 0);
+        } else if (mode == 1) {
+            __half * d_W = (__half *) bufs.get((size_t) NV * K * 2);
+            float * d_x = (float *) bufs.get((size_t) K * 4), * d_g = (float *) bufs.get((size_t) K * 4), * d_b = (float *) bufs.get((size_t) K * 4);
+            if (!d_W || !d_x || !d_g || !d_b) return -3;
+            const std::vector<float> ones((size_t) K, 1.0f);
+            if (!HIP_OK(hipMemcpyAsync(d_W, W, (size_t) NV * K * 2, hipMemcpyHostToDevice, s)) ||
+                !HIP_OK(hipMemcpyAsync(d_x, x, (size_t) K * 4, hipMemcpyHostToDevice, s)) ||
+                !HIP_OK(hipMemcpyAsync(d_g, ones.data(), (size_t) K * 4, hipMemcpyHostToDevice, s)) ||
+                !HIP_OK(hipMemsetAsync(d_b, 0, (size_t) K * 4, s)) || !HIP_OK(hipStreamSynchronize(s))) return -3;
+            g.x32 = d_x; g.ln_g = d_g; g.ln_b = d_b; g.W = d_W; g.C = d_logits;
+            g.fs_ban = d.ban_dev; g.fs_step = d_step; g.fs_part = (k::FsPartial *) scratch;
+            const int fused_parts = k::gemv_fused_parts(g);
+            if (fused_parts <= 0) return -4;
+            k::gemv(g, s);
+            k::filter_argmax(d_logits, d.ban_dev, d_step, d_out, scratch, s, nullptr, 1, nullptr, fused_parts);
+            if (!HIP_OK(hipMemcpyAsync(logits_out, d_logits, (size_t) NV * 4, hipMemcpyDeviceToHost, s))) return -3;
+        } else {
+            double * d_u = (double *) bufs.get(n_out * sizeof(double));
+            if (!d_u || !HIP_OK(hipMemcpyAsync(d_u, u, n_out * sizeof(double), hipMemcpyHostToDevice, s))) return -3;
+            k::filter_draw(d_logits, d.ban_dev, d_step, d_u, k, d_out, scratch, s, n_rows, tid_default);
+        }
+        std::vector<k::SampleOut> res(n_out);
+        if (!HIP_OK(hipGetLastError()) || !HIP_OK(hipMemcpyAsync(res.data(), d_out, n_out * sizeof(k::SampleOut), hipMemcpyDeviceToHost, s)) ||
+            !HIP_OK(hipStreamSynchronize(s))) return -3;
+        for (size_t i = 0; i < n_out; ++i) out[i] = whisper_token_data{ res[i].id, res[i].tid, res[i].p, res[i].plog, res[i].pt, res[i].ptsum, -1, -1, 0.0f };
+        return 0;
+    } catch (const std::exception & e) {
+        WMI_ERR("%s: %s\n", __func__, e.what());
+        return -3;
+    }
+}
+
 int wmi_selftest_resample_plan(int n_frames, int src_rate, int dst_rate, int converter, long long * frames_gen, long long * frames_used,
                                int * closed_form, int n_pos, long long * pos, double * frac) {
     if (n_frames < 0 || src_rate <= 0 || dst_rate <= 0 || src_rate == dst_rate || n_pos < 0 || (n_pos > 0 && (!pos || !frac))) return -1;

@@ -903,17 +903,10 @@ int full_batch(whisper_context & ctx, whisper_full_params params, const float * 
                     if (row.n_fed < np) { st.token = row.prompt[row.n_fed]; st.pos = row.n_fed; }
                     else                { st.token = d.sequence.tokens.back().id; st.pos = np + row.i - 1; }
                     st.n_kv = st.pos + 1; st.kv_head = st.pos;
-                    // filter state of the token this step will sample (W/whisper.cpp:4541-4657); see full()'s step_filter
-                    const auto & h = d.sequence.tokens;
-                    const bool initial = h.empty();
-                    const bool last_ts = !h.empty() && h.back().id >= v.beg;
-                    const bool penult_ts = h.size() < 2 || h[h.size() - 2].id >= v.beg;
-                    st.flags = ((params.suppress_blank && initial) ? 1 : 0) | (last_ts ? 2 : 0) | (penult_ts ? 4 : 0);
-                    if (d.has_ts) st.ts_floor_end = v.beg + d.seek_delta / 2;
-                    if (initial && params.max_initial_ts > 0.0f) {
-                        const float precision = float(WHISPER_CHUNK_SIZE) / hp.n_audio_ctx;
-                        st.ts_initial_start = v.beg + (int) std::round(params.max_initial_ts / precision) + 1;
-                    }
+                    // filter state of the token this step will sample (W/whisper.cpp:4541-4657)
+                    const StepFilter f = make_step_filter(v, hp, params, d);
+                    st.flags = (f.ban_blank ? 1 : 0) | (f.last_ts ? 2 : 0) | (f.penult_ts ? 4 : 0);
+                    st.ts_floor_end = f.ts_floor_end; st.ts_initial_start = f.ts_initial_start;
                 }
                 if (!any) break;
                 ++b.step_seq;

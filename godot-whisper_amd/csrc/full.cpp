@@ -214,21 +214,7 @@ int full(whisper_context & ctx, whisper_full_params params, const float * sample
             st.dev.keep_logits_on_device = dev_draw;
             struct KeepOff { bool & f; ~KeepOff() { f = false; } } keep_off{st.dev.keep_logits_on_device};
             whisper_token_data fast_next{};      // token picked on the device for the upcoming sampling step
-            auto step_filter = [&](const Decoder & d) {
-                const auto & h = d.sequence.tokens;
-                StepFilter f{};
-                const bool initial = h.empty();
-                f.ban_blank = params.suppress_blank && initial;
-                f.last_ts = !h.empty() && h.back().id >= v.beg;
-                f.penult_ts = h.size() < 2 || h[h.size() - 2].id >= v.beg;
-                f.ts_floor_end = d.has_ts ? v.beg + d.seek_delta / 2 : v.beg;
-                f.ts_initial_start = v.n_vocab;
-                if (initial && params.max_initial_ts > 0.0f) {
-                    const float precision = float(WHISPER_CHUNK_SIZE) / hp.n_audio_ctx;
-                    f.ts_initial_start = v.beg + (int) std::round(params.max_initial_ts / precision) + 1;
-                }
-                return f;
-            };
+            auto step_filter = [&](const Decoder & d) { return make_step_filter(v, hp, params, d); };
             if (fast) {
                 bool ok = true;
                 if (prompt.size() > 1) {            // all but the last prompt token: plain batch decode, no logits wanted

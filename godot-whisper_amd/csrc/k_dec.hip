@@ -1173,7 +1173,7 @@ __global__ __launch_bounds__(64 * WPB) void k_gemv1(const GemvArgs a_in) {
                     if (flags & 2) { if (flags & 4) { if (n >= beg) al = false; } else { if (n < eot) al = false; } }
                     if (n >= ts_initial_start) al = false;
                     if (n >= beg && n < ts_floor_end) al = false;
-                    if (al) {
+                    if (al && v > -INFINITY) {                   // (as k_filter_stats: a raw -inf is out; first in a lane it made exp(-inf + inf))
                         const float lv = fs_temp > 0.0f ? v / fs_temp : v;
                         const float mo = fs_all.v, mn = fmaxf(mo, lv);
                         // (v_exp_f32: ~1e-6 relative on the terms that carry weight; two libm expf per row cost the projection 2.6 us)

@@ -69,7 +69,7 @@ __global__ __launch_bounds__(NT) void k_filter_stats(const float * __restrict__ 
             if (last_ts) { if (pen_ts) { if (i >= beg) a = false; } else { if (i < st.eot) a = false; } }
             if (i >= st.ts_initial_start) a = false;
             if (i >= beg && i < st.ts_floor_end) a = false;
-            if (a) {
+            if (a && lraw[e] > -INFINITY) {              // (a raw -inf is out, as in process_logits: a block of nothing else would sum exp(-inf + inf))
                 ok[e] = true; lv[e] = st.temperature > 0.0f ? lraw[e] / st.temperature : lraw[e];
                 const MaxIdx c = {lv[e], i};
                 m_all = better(m_all, c);

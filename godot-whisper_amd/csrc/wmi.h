@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <map>
@@ -419,6 +420,23 @@ bool decode_layers_q(whisper_context & ctx, int n, int n_kv, int kv_head, int Tc
 void enqueue_greedy_step_q(whisper_context & ctx, int Tc);
 // greedy fast path: decode ONE token of sequence 0 at position `pos` and pick the next token on the device
 struct StepFilter { bool ban_blank, last_ts, penult_ts; int ts_floor_end, ts_initial_start; };
+// the filter state of the token a decoder samples next (W/whisper.cpp:4541-4657), from its history, has_ts and seek_delta: the one place
+// that maps (parameters, history) to the step record's fields — full(), the lock-step rows of wmi_full_batch and wmi_selftest_filters
+inline StepFilter make_step_filter(const Vocab & v, const HParams & hp, const whisper_full_params & params, const Decoder & d) {
+    const auto & h = d.sequence.tokens;
+    StepFilter f{};
+    const bool initial = h.empty();
+    f.ban_blank = params.suppress_blank && initial;
+    f.last_ts = !h.empty() && h.back().id >= v.beg;
+    f.penult_ts = h.size() < 2 || h[h.size() - 2].id >= v.beg;
+    f.ts_floor_end = d.has_ts ? v.beg + d.seek_delta / 2 : v.beg;
+    f.ts_initial_start = v.n_vocab;
+    if (initial && params.max_initial_ts > 0.0f) {
+        const float precision = float(WHISPER_CHUNK_SIZE) / hp.n_audio_ctx;
+        f.ts_initial_start = v.beg + (int) std::round(params.max_initial_ts / precision) + 1;
+    }
+    return f;
+}
 // forms: when given, the launch form the step took (STEP_FORM_* bits; the test hook wmi_selftest_greedy_step reports them)
 enum : unsigned { STEP_FORM_LONG_KV = 1, STEP_FORM_CHAINED = 2, STEP_FORM_GRAPH = 4, STEP_FORM_PAIRED = 8, STEP_FORM_FRONTED = 16,
                   STEP_FORM_BACKED = 32, STEP_FORM_RERUN = 64, STEP_FORM_SLOW = 128, STEP_FORM_QUANTISED = 256 };

@@ -45,6 +45,9 @@ DEVICE_API = [
     ("wmi_selftest_proj", C.c_double, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     ("wmi_selftest_greedy_step", C.c_int, [C.c_void_p, C.c_int32, C.c_int, C.POINTER(C.c_float), C.POINTER(abi.whisper_token_data),
                                            C.POINTER(C.c_int)]),
+    ("wmi_selftest_filters", C.c_int, [C.c_void_p, abi.whisper_full_params, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                       C.c_void_p]),
     ("wmi_bench_kernel", C.c_double, [C.c_void_p, C.c_int, C.c_int]),
     ("wmi_reload_knobs", None, []),
     ("wmi_pair_status", C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int]),

@@ -226,6 +226,26 @@ WHISPER_API double wmi_selftest_proj(struct whisper_context * ctx, int op, int n
 WHISPER_API int wmi_selftest_greedy_step(struct whisper_context * ctx, whisper_token token, int pos, float * logits, whisper_token_data * out,
                                          int * forms);
 
+/* Test hook for the device logit filters, the greedy pick and the draws (csrc/k_sample.hip, the fused epilogue of the vocabulary projection
+ * in csrc/k_dec.hip) on caller logits.  The static ban is uploaded from `params` exactly as whisper_full does; row r's step record is built
+ * as whisper_full / wmi_full_batch build it from `params`, the row's token history (hist: the histories one after the other, n_hist[r]
+ * tokens each), has_ts[r] and seek_delta[r]; `temperature` (> 0: the logits are divided by it) is written into every record.
+ *   mode 0  the statistics pass + the pick (k_filter_stats, k_filter_pick) on logits [n_rows][n_vocab], 1 <= n_rows <= 16 (n_rows > 1: the
+ *           lock-step form, the row on grid.y); out [n_rows]
+ *   mode 1  the fused form of ONE row: the vocabulary projection with the statistics in its epilogue, then the pick.  The caller supplies
+ *           the projection: W f16 [n_vocab][K] and an f32 row x [K]; logits = W . LayerNorm(x) with gain 1 and bias 0.  logits_out
+ *           [n_vocab] receives the logits the launch wrote (`logits` is ignored).  -4 when these arguments do not take the fused path
+ *           (K not a multiple of 8 or above 1536, a vocabulary below 16384); out [1]
+ *   mode 2  k draws per row (k_filter_stats, k_prob_blocks, k_draw) with the caller's uniform numbers u [n_rows][k], 1 <= n_rows <= 8,
+ *           1 <= k <= 8; tid_default: the tid reported when every timestamp probability underflows; out [n_rows][k]
+ * out: id, tid, p, plog, pt, ptsum of every pick / draw.  The hook allocates and frees its own device memory.
+ * Returns 0; -1 bad arguments, -2 the context cannot compute (host-only, weights pending), -3 device error, -4 see mode 1.  Every
+ * argument error returns before the device is touched. */
+WHISPER_API int wmi_selftest_filters(struct whisper_context * ctx, struct whisper_full_params params, int mode, int n_rows,
+                                     const float * logits, const whisper_token * hist, const int * n_hist, const int * has_ts,
+                                     const int * seek_delta, float temperature, const void * W, const float * x, int K, float * logits_out,
+                                     const double * u, int k, int tid_default, whisper_token_data * out);
+
 /* Host half of wmi_resample on its own (no device needed; CPU-side tests): the frame counts src_simple reports for n_frames
  * mono frames at src_rate -> dst_rate (output capacity int(n_frames * ratio) as the host passes it), and the first n_pos output
  * positions (integer sample, fraction) the kernel would use.  Returns 0, or the converter error as wmi_resample logs it.
