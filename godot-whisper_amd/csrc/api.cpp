@@ -373,7 +373,7 @@ int wmi_downmix_stereo(struct whisper_context * ctx, const float * frames, int n
 int wmi_resample(struct whisper_context * ctx, const float * src, int n_frames, int src_rate, int dst_rate, int converter, int on_device,
                  float * dst, int dst_capacity) {
     if (!ctx || !ctx->state || ctx->host_only || !src || !dst || n_frames < 0 || src_rate <= 0 || dst_rate <= 0 || dst_capacity < 0 ||
-        converter < 0 || converter > 2) return -1;
+        converter < 0 || converter > 4) return -1;
     CtxScope lk(ctx);
     if (!HIP_OK(hipSetDevice(ctx->device))) return -2;
     hipStream_t s = ctx->state->dev.stream;
@@ -388,18 +388,26 @@ int wmi_resample(struct whisper_context * ctx, const float * src, int n_frames, 
     if (out_frames > dst_capacity) return -4;
     try {                                                                                          // (the plan allocates: nothing throws across the C ABI)
     const k::ResamplePlan pl = k::resample_plan(n_frames, out_frames, ratio, converter);
+    if (pl.error == -31) {                                                                         // undefined in the library: it reads data_in[-1]
+        WMI_ERR("wmi_resample: SRC_LINEAR cannot upsample a single frame, 0 frames\n");
+        return 0;
+    }
     if (pl.error) {
         WMI_ERR("wmi_resample: converter error %d (src_simple would report it through src_strerror)\n", -pl.error);
         return pl.error == -10 ? -10 : 0;                                                          // the host returns 0 frames on a converter error (:33-36)
     }
     if (pl.n_out == 0) return 0;
-    float *& d_tab = ctx->d_sinc[converter];
+    const float * d_tab = nullptr;                                                                 // SRC_ZERO_ORDER_HOLD, SRC_LINEAR: no coefficients
     bool ok = true;
-    if (!d_tab) {
-        const float * coeffs; int count, inc;
-        (void) k::sinc_table(converter, &coeffs, &count, &inc);
-        ok = HIP_OK(hipMalloc((void **) &d_tab, (size_t) count * 4)) && HIP_OK(hipMemcpyAsync(d_tab, coeffs, (size_t) count * 4, hipMemcpyHostToDevice, s));
-        if (!ok) { if (d_tab) { (void) hipFree(d_tab); d_tab = nullptr; } return -3; }
+    if (converter <= 2) {
+        float *& d_sinc = ctx->d_sinc[converter];
+        if (!d_sinc) {
+            const float * coeffs; int count, inc;
+            (void) k::sinc_table(converter, &coeffs, &count, &inc);
+            ok = HIP_OK(hipMalloc((void **) &d_sinc, (size_t) count * 4)) && HIP_OK(hipMemcpyAsync(d_sinc, coeffs, (size_t) count * 4, hipMemcpyHostToDevice, s));
+            if (!ok) { if (d_sinc) { (void) hipFree(d_sinc); d_sinc = nullptr; } return -3; }
+        }
+        d_tab = d_sinc;
     }
     float * d_in = nullptr, * d_out = nullptr; int * d_pos = nullptr; double * d_frac = nullptr;
     const float * in = src; float * out = dst;

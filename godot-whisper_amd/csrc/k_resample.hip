@@ -1,4 +1,4 @@
-// SINC resampler of the streaming node on the device.
+// Resampler of the streaming node on the device: the two SINC converters, zero-order hold and linear.
 //
 // replaces: _resample_audio_buffer (src/speech_to_text.cpp:16-43) -> src_simple(SRC_SINC_FASTEST | SRC_SINC_MEDIUM_QUALITY,
 // 1 channel) of libsamplerate (thirdparty/libsamplerate/src/samplerate.c:469-483, src_sinc.c:283-427, 1166-1239).
@@ -18,6 +18,11 @@
 // runs the recurrence once in double, as index bookkeeping, and the kernel reads the (pos, frac) table.
 // How many outputs libsamplerate emits depends on its ring-buffer refills and on a termination test evaluated in buffer
 // coordinates in double; plan() replays exactly that index state machine (refill to refill, not sample by sample).
+//
+// SRC_ZERO_ORDER_HOLD and SRC_LINEAR (src_zoh.c:59-126, src_linear.c:61-135) walk the same positions without a ring buffer: output n
+// is in[pos_n - 1] held, or in[pos_n - 1] + frac_n * (in[pos_n] - in[pos_n - 1]) with an f32 difference and a separate f64 multiply
+// and add; while pos_n is still 0 both give in[0] (their last_value).  They stop at the capacity or when the position runs off the
+// input (plan_simple), which is also what keeps every read inside the array.
 
 #include "kernels.h"
 #include <cmath>
@@ -43,9 +48,8 @@ struct ResampleArgs {
     const int * pos_tab; const double * frac_tab;             // or the host's recurrence
 };
 
-__global__ __launch_bounds__(256) void k_resample(const ResampleArgs a) {
-    const long long n = (long long) blockIdx.x * 256 + threadIdx.x;
-    if (n >= a.n_out) return;
+// where output n sits on the input: the host's table, or integer and fractional part of n * m * 2^-sh
+__device__ __forceinline__ void out_position(const ResampleArgs & a, long long n, long long * pos_out, double * frac_out) {
     long long pos; double frac;
     if (a.pos_tab) { pos = a.pos_tab[n]; frac = a.frac_tab[n]; }
     else {
@@ -56,6 +60,14 @@ __global__ __launch_bounds__(256) void k_resample(const ResampleArgs a) {
             frac = (double) (lo & ((1ull << a.sh) - 1ull)) * a.frac_scale;
         }
     }
+    *pos_out = pos; *frac_out = frac;
+}
+
+__global__ __launch_bounds__(256) void k_resample(const ResampleArgs a) {
+    const long long n = (long long) blockIdx.x * 256 + threadIdx.x;
+    if (n >= a.n_out) return;
+    long long pos; double frac;
+    out_position(a, n, &pos, &frac);
     const int increment = a.increment;
     const int start_index = (int) __builtin_rint(frac * a.float_inc * 4096.0);     // double_to_fp, src_sinc.c:71-74
     const int max_index = a.half_len << 12;
@@ -102,6 +114,23 @@ __global__ __launch_bounds__(256) void k_resample(const ResampleArgs a) {
     } while (fi > 0);
 
     a.out[n] = (float) (a.out_scale * (left + right));
+}
+
+// SRC_ZERO_ORDER_HOLD (LINEAR = false, src_zoh.c:80, :99) and SRC_LINEAR (src_linear.c:82-83, :107-108).  The plan emits output n only
+// while pos_n - 1 (and pos_n for LINEAR) are frames of the input; the clamp keeps a wrong plan from reading outside it.
+template <bool LINEAR>
+__global__ __launch_bounds__(256) void k_resample_simple(const ResampleArgs a) {
+    const long long n = (long long) blockIdx.x * 256 + threadIdx.x;
+    if (n >= a.n_out) return;
+    long long pos; double frac;
+    out_position(a, n, &pos, &frac);
+    const long long last = a.n_in - 1;
+    const long long i0 = pos <= 0 ? 0 : (pos - 1 > last ? last : pos - 1);     // pos 0: last_value = in[0]
+    const float v0 = a.in[i0];
+    if (!LINEAR) { a.out[n] = v0; return; }
+    const long long i1 = pos <= 0 ? 0 : (pos > last ? last : pos);
+    const float d = a.in[i1] - v0;                                               // float difference, then double multiply and add
+    a.out[n] = (float) ((double) v0 + frac * (double) d);
 }
 
 double frac_one(double x) {                                   // thirdparty/libsamplerate/src/common.h:149-158
@@ -222,16 +251,54 @@ static long long plan(long long N, long long cap, double ratio, int half_len, in
     return n;
 }
 
+// src_zoh.c:59-126 / src_linear.c:61-135 for one channel, one call, a constant ratio: the number of frames emitted (and consumed).
+// Output n is emitted while n < cap and its position is still on the input: with pos_n == 0 (the converters' first loop)
+// ZOH goes on while frac_n < N and LINEAR while 1.0 + frac_n < N; after that ZOH while pos_n + frac_n <= N, LINEAR while
+// pos_n + frac_n < N.  Both sums grow with n, so the first output that fails is found by bisection in either part.
+// LINEAR leaving its first loop for lack of input enters the second with pos 0 and reads data_in[-1] (one input frame and a
+// ratio above 1): nothing to reproduce, answered -31.
+static long long plan_simple(long long N, long long cap, bool linear, const Stepper & P, long long * used) {
+    *used = 0;
+    if (N <= 0) return 0;                                                        // src_zoh.c:44-45, src_linear.c:46-47
+    auto first_off = [&](long long lo, long long hi, auto off) {               // first k in [lo, hi) that is off the input (hi if none)
+        while (lo < hi) {
+            const long long mid = lo + (hi - lo) / 2;
+            long long p; double f; P.at(mid, &p, &f);
+            if (off(p, f)) hi = mid; else lo = mid + 1;
+        }
+        return lo;
+    };
+    const double dN = (double) N;
+    const long long head = P.first_at_or_past(1, 0, cap);                        // outputs [0, head) sit before the first input sample
+    long long n = first_off(0, head, [&](long long, double f) { return linear ? 1.0 + f >= dN : f >= dN; });
+    if (n < head) { if (linear) return -31; }
+    else n = first_off(head, cap, [&](long long p, double f) { return linear ? !((double) p + f < dN) : !((double) p + f <= dN); });
+    long long p; double f; P.at(n, &p, &f);
+    *used = std::min(p, N);
+    return n;
+}
+
 // One call of src_simple on the device.  d_in / d_out: device pointers (n_in frames in, room for out_cap frames out).
 // d_coeffs: the converter's table on the device.  d_pos / d_frac: device scratch for the (pos, frac) table, filled here when
 // the recurrence is not exact (may be null when `need_table` comes back false from resample_plan).
 ResamplePlan resample_plan(long long n_in, long long out_cap, double ratio, int converter) {
     ResamplePlan pl;
+    pl.converter = converter;
+    const bool simple = converter == 3 || converter == 4;                                       // SRC_ZERO_ORDER_HOLD, SRC_LINEAR: no table
     const float * coeffs; int count, table_inc;
-    if (!sinc_table(converter, &coeffs, &count, &table_inc)) { pl.error = -10; return pl; }     // SRC_ERR_BAD_CONVERTER
+    if (!simple && !sinc_table(converter, &coeffs, &count, &table_inc)) { pl.error = -10; return pl; }     // SRC_ERR_BAD_CONVERTER
     if (ratio < 1.0 / 256 || ratio > 256.0) { pl.error = -6; return pl; }
     if (n_in < 0) n_in = 0;
     if (out_cap < 0) out_cap = 0;
+    if (simple) {
+        pl.stepper = std::make_shared<Stepper>();
+        pl.stepper->init(1.0 / ratio, out_cap);
+        long long used = 0;
+        const long long gen = plan_simple(n_in, out_cap, converter == 4, *pl.stepper, &used);
+        if (gen < 0) { pl.error = (int) gen; return pl; }
+        pl.n_out = gen; pl.n_used = used; pl.need_table = !pl.stepper->closed;
+        return pl;
+    }
     pl.half_len = count - 2; pl.index_inc = table_inc;
     int b_len = 3 * (int) lrint((pl.half_len + 2.0) / table_inc * 256 + 1);                    // src_sinc.c:213-216
     b_len = std::max(b_len, 4096) + 1;
@@ -267,7 +334,10 @@ void resample_launch(const ResamplePlan & pl, const float * d_in, long long n_in
     a.float_inc = pl.float_inc; a.out_scale = pl.out_scale; a.increment = pl.increment;
     a.m = pl.stepper->m; a.sh = pl.stepper->sh; a.frac_scale = ldexp(1.0, -pl.stepper->sh);
     a.pos_tab = pl.need_table ? d_pos : nullptr; a.frac_tab = pl.need_table ? d_frac : nullptr;
-    hipLaunchKernelGGL(k_resample, dim3((unsigned) ((pl.n_out + 255) / 256)), dim3(256), 0, st, a);
+    const dim3 grid((unsigned) ((pl.n_out + 255) / 256));
+    if (pl.converter == 3) hipLaunchKernelGGL(k_resample_simple<false>, grid, dim3(256), 0, st, a);
+    else if (pl.converter == 4) hipLaunchKernelGGL(k_resample_simple<true>, grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(k_resample, grid, dim3(256), 0, st, a);
 }
 
 }}  // namespace wmi::k

@@ -126,15 +126,17 @@ void ts_refine(const float * en, const float * bmin, const float * bmax, int n_s
 void downmix_stereo(const float * frames, int n_frames, float * out, hipStream_t st);
 void vad_window(const float * x, int n, int n_last, float alpha, bool filter, float vad_thold, float * res, hipStream_t st);
 
-// SINC resampler (k_resample.hip): src_simple(SRC_SINC_FASTEST = 2 | SRC_SINC_MEDIUM_QUALITY = 1, one channel) of libsamplerate as the host
-// calls it (src/speech_to_text.cpp:16-43), bit-identical to the sequential CPU code.  resample_plan replays the converter's index
+// Resampler (k_resample.hip): src_simple(SRC_SINC_FASTEST = 2 | SRC_SINC_MEDIUM_QUALITY = 1 | SRC_ZERO_ORDER_HOLD = 3 | SRC_LINEAR = 4,
+// one channel) of libsamplerate as the host calls it (src/speech_to_text.cpp:16-43), bit-identical to the sequential CPU code.  resample_plan replays the converter's index
 // state machine on the host (how many frames come out, whether the position recurrence has a closed form), resample_launch
 // computes every output frame in its own thread.
 struct Stepper;
 struct ResamplePlan {
-    int error = 0;                       // 0, or libsamplerate's error number negated (-6 ratio, -10 converter, -21 length check), -30 ratio unsupported
+    int error = 0;                       // 0, or libsamplerate's error number negated (-6 ratio, -10 converter, -21 length check), -30 ratio unsupported,
+                                         // -31 SRC_LINEAR on one input frame at a ratio above 1 (the library reads data_in[-1])
+    int converter = 2;
     long long n_out = 0, n_used = 0;     // output_frames_gen, input_frames_used
-    int half_len = 0, index_inc = 0, increment = 0;
+    int half_len = 0, index_inc = 0, increment = 0;              // SINC converters only, like float_inc and out_scale
     double float_inc = 0.0, out_scale = 0.0;
     bool need_table = false;             // the (pos, frac) table of resample_table() has to be on the device
     std::shared_ptr<Stepper> stepper;

@@ -143,7 +143,8 @@ class SpeechToText:
 
     # -- resample (src/speech_to_text.cpp:353-376): stereo capture frames at the mix rate -> mono 16 kHz.  The reference goes through
     #    libsamplerate on the CPU; here both steps run on the device (wmi_downmix_stereo, wmi_resample).
-    SRC_SINC_BEST_QUALITY, SRC_SINC_MEDIUM_QUALITY, SRC_SINC_FASTEST = 0, 1, 2        # src/speech_to_text.h:151-155
+    SRC_SINC_BEST_QUALITY, SRC_SINC_MEDIUM_QUALITY, SRC_SINC_FASTEST = 0, 1, 2        # src/speech_to_text.h:151-156
+    SRC_ZERO_ORDER_HOLD, SRC_LINEAR = 3, 4
 
     def resample(self, buffer_xy: np.ndarray, interpolator_type: int = 2, mix_rate: int = 44100) -> np.ndarray:
         xy = np.ascontiguousarray(buffer_xy, dtype=np.float32).reshape(-1, 2)

@@ -56,10 +56,10 @@ public:
     // set_language_model(Ref<WhisperResource>) + _load_model(): the resource's bytes (src/resource_whisper.h)
     void set_language_model(const uint8_t * data, size_t size);
 
-    // src/speech_to_text.h:151-155, :162 — resample(PackedVector2Array buffer, InterpolatorType): stereo capture frames at the mix rate
+    // src/speech_to_text.h:151-156, :162 — resample(PackedVector2Array buffer, InterpolatorType): stereo capture frames at the mix rate
     // -> mono 16 kHz.  The reference folds on the CPU and calls libsamplerate's src_simple; here both steps run on the device
     // (wmi_downmix_stereo, wmi_resample: the same arithmetic frame for frame).  `mix_rate` stands in for AudioServer::get_mix_rate().
-    enum InterpolatorType { SRC_SINC_BEST_QUALITY = 0, SRC_SINC_MEDIUM_QUALITY = 1, SRC_SINC_FASTEST = 2 };
+    enum InterpolatorType { SRC_SINC_BEST_QUALITY = 0, SRC_SINC_MEDIUM_QUALITY = 1, SRC_SINC_FASTEST = 2, SRC_ZERO_ORDER_HOLD = 3, SRC_LINEAR = 4 };
     std::vector<float> resample(const std::vector<float> & interleaved_xy, InterpolatorType interpolator_type, int mix_rate);
     std::string last_resample_error;      // what the reference ERR_PRINTs ("size differ exp: ... res: ...")
 

@@ -103,13 +103,19 @@ WHISPER_API int wmi_downmix_stereo(struct whisper_context * ctx, const float * f
 
 /* The node's 16 kHz resampler on the device.
  *   replaces: _resample_audio_buffer (src/speech_to_text.cpp:16-43) = libsamplerate's src_simple(&data, interpolator_type, 1)
- *             (thirdparty/libsamplerate/src/samplerate.c:469-483; SINC converters thirdparty/libsamplerate/src/src_sinc.c:283-427)
- * converter: the host's InterpolatorType (src/speech_to_text.h:151-155): 2 = SRC_SINC_FASTEST (what capture_stream_to_text.gd:76 asks
- * for), 1 = SRC_SINC_MEDIUM_QUALITY; 0 = SRC_SINC_BEST_QUALITY answers -10: its coefficient table is a missing blob of the reference
- * checkout.  Mono f32 frames at src_rate -> dst (room for dst_capacity >= int(n_frames * dst_rate / src_rate) frames) at dst_rate
+ *             (thirdparty/libsamplerate/src/samplerate.c:469-483; SINC converters thirdparty/libsamplerate/src/src_sinc.c:283-427,
+ *             src_zoh.c:59-126, src_linear.c:61-135)
+ * converter: the host's InterpolatorType (src/speech_to_text.h:151-156), all five values:
+ *   0 = SRC_SINC_BEST_QUALITY    answers -10: its coefficient table is a missing blob of the reference checkout
+ *   1 = SRC_SINC_MEDIUM_QUALITY
+ *   2 = SRC_SINC_FASTEST         (what capture_stream_to_text.gd:76 asks for)
+ *   3 = SRC_ZERO_ORDER_HOLD      each output repeats the input frame before its position
+ *   4 = SRC_LINEAR               f32 difference of the two neighbours, double multiply and add, one rounding.  One frame in at a ratio
+ *                                above 1 has no defined result (the library reads data_in[-1]): logged, 0 frames, no kernel runs
+ * Any other value answers -1 before the device is touched.  Mono f32 frames at src_rate -> dst (room for dst_capacity >= int(n_frames * dst_rate / src_rate) frames) at dst_rate
  * (the host passes WHISPER_SAMPLE_RATE).  Returns the frames written — the host's result_size; equal rates copy — or 0 where
  * src_simple reports an error (ratio outside [1/256, 256]); < 0: -1 arguments, -2 / -3 device, -4 dst_capacity too small.
- * Every output frame equals the sequential CPU code bit for bit (double accumulators, taps in its order). */
+ * Every output frame equals the sequential CPU code bit for bit (SINC: double accumulators, taps in its order). */
 WHISPER_API int wmi_resample(struct whisper_context * ctx, const float * src, int n_frames, int src_rate, int dst_rate, int converter,
                              int on_device, float * dst, int dst_capacity);
 WHISPER_API int wmi_vad(struct whisper_context * ctx, const float * pcm, int n_samples, int on_device, float vad_thold, float freq_thold,
@@ -248,7 +254,8 @@ WHISPER_API int wmi_selftest_filters(struct whisper_context * ctx, struct whispe
 
 /* Host half of wmi_resample on its own (no device needed; CPU-side tests): the frame counts src_simple reports for n_frames
  * mono frames at src_rate -> dst_rate (output capacity int(n_frames * ratio) as the host passes it), and the first n_pos output
- * positions (integer sample, fraction) the kernel would use.  Returns 0, or the converter error as wmi_resample logs it.
+ * positions (integer sample, fraction) the kernel would use.  converter: 1 - 4 as for wmi_resample.  Returns 0, or the converter error as
+ * wmi_resample logs it (-6 ratio, -10 no such converter or table, -31 SRC_LINEAR on one frame at a ratio above 1).
  * closed_form: 1 when the positions come from the exact 128-bit product, 0 when the host ran the double recurrence. */
 /* Test hook for the device form of the token timestamps' envelope side (csrc/k_mel.hip k_ts_refine; opt-in, WMI_TS_DEVICE=1):
  * `envelope` [n] is a host array standing in for the |x| envelope; for each of the n_tok tokens, s0s1[2 t] / s0s1[2 t + 1] are its start / end
