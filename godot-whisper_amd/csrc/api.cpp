@@ -732,7 +732,30 @@ int wmi_batch_select(struct whisper_context * ctx, int chunk) {
     CtxScope lk(ctx);
     if (!ctx->state || !ctx->batch || chunk < 0 || chunk >= (int) ctx->batch->results.size()) return -1;
     ctx->state->result_all = ctx->batch->results[chunk];
+    if (chunk < (int) ctx->batch->lang_id.size() && ctx->batch->lang_id[chunk] >= 0) ctx->state->lang_id = ctx->batch->lang_id[chunk];
     return (int) ctx->state->result_all.size();
+}
+
+int wmi_batch_lang_id(struct whisper_context * ctx, int chunk) {
+    if (!ctx) return -1;
+    CtxScope lk(ctx);
+    if (!ctx->batch || chunk < 0 || chunk >= (int) ctx->batch->lang_id.size()) return -1;
+    return ctx->batch->lang_id[chunk];
+}
+
+int wmi_batch_lang_probs(struct whisper_context * ctx, int chunk, float * probs100) {
+    if (!ctx || !probs100) return -1;
+    CtxScope lk(ctx);
+    if (!ctx->batch || chunk < 0 || chunk >= (int) ctx->batch->lang_id.size()) return -1;
+    const BatchWork & b = *ctx->batch;
+    if ((size_t) (chunk + 1) * k::LANG_HEAD_N > b.lang_probs.size() || !b.lang_detected[chunk]) return -1;
+    memcpy(probs100, b.lang_probs.data() + (size_t) chunk * k::LANG_HEAD_N, k::LANG_HEAD_N * sizeof(float));
+    return 0;
+}
+
+int wmi_selftest_lang_probs(const float * logits100, float * probs100) {
+    if (!logits100) return -1;
+    return lang_probs_from_logits(logits100, probs100);
 }
 
 void wmi_get_batch_timings(struct whisper_context * ctx, int64_t * t4, int32_t * n_steps) {
@@ -1036,9 +1059,13 @@ double wmi_bench_kernel(struct whisper_context * ctx, int which, int iters) {
                 const BatchWork & b = *ctx->batch;
                 k::attn_encoder(b.q, b.k, b.vt, T, b.Tpad, S, H, 0.125f, b.att, s, b.B, nullptr, b.qk_rows);
             } break;
+            case 13:                                   // the language head on the row which = 1 projects (f16 models; into device memory)
+                k::lang_head(d.dx, 1, hp.n_text_state, w.d_ln_g, w.d_ln_b, hp.eps, w.d_te + (size_t) (ctx->model.vocab.sot + 1) * hp.n_text_state, d.logits, s);
+                break;
             default: break;
         }
     };
+    if (which == 13 && (ctx->model.quantised || !k::lang_head_usable(hp.n_text_state))) { (void) hipEventDestroy(e0); (void) hipEventDestroy(e1); return -1.0; }
     if ((which == 4 || which == 5 || which == 9) && (!ctx->batch || ctx->batch->B < 1)) { (void) hipEventDestroy(e0); (void) hipEventDestroy(e1); return -1.0; }
     if (which >= 10 && which <= 12) {                                   // launch-floor probes: chains of trivial dependent kernels
         const int blocks = which == 10 ? 1 : which == 11 ? 32 : 256;

@@ -153,6 +153,12 @@ int whisper_lang_auto_detect_with_state(struct whisper_context * ctx, struct whi
     StateScope sc(ctx, state);
     return lang_auto_detect(*ctx, offset_ms, lang_probs);
 }
+int wmi_lang_detect(struct whisper_context * ctx, int offset_ms, float * lang_probs) {      // the same detection through the language head (wmi_device.h)
+    if (!ctx || !ctx->state) return -1;
+    StateScope sc(ctx, reinterpret_cast<struct whisper_state *>(ctx->state.get()));
+    if (!k::lang_head_usable(ctx->model.hp.n_text_state)) return lang_auto_detect(*ctx, offset_ms, lang_probs);
+    return lang_detect_head(*ctx, offset_ms, lang_probs);
+}
 int whisper_full_with_state(struct whisper_context * ctx, struct whisper_state * state, struct whisper_full_params params, const float * samples, int n_samples) {
     if (!ctx || !state) return -1;
     StateScope sc(ctx, state);

@@ -84,7 +84,8 @@ bool ensure_batch(whisper_context & ctx, int B) {
     if (w.filter_scratch) (void) hipFree(w.filter_scratch);
     if (w.step_host) (void) hipHostFree(w.step_host);
     if (w.sample_host) (void) hipHostFree(w.sample_host);
-    w.step_dev = w.sample_dev = w.filter_scratch = w.step_host = w.sample_host = nullptr;
+    if (w.lang_host) (void) hipHostFree(w.lang_host);
+    w.step_dev = w.sample_dev = w.filter_scratch = w.step_host = w.sample_host = nullptr; w.lang_host = nullptr;
 
     const HParams & hp = ctx.model.hp;
     const size_t S = hp.n_audio_state, T = hp.n_audio_ctx, Lt = hp.n_text_layer, H = hp.n_audio_head, n_ctx = hp.n_text_ctx;
@@ -113,7 +114,8 @@ bool ensure_batch(whisper_context & ctx, int B) {
     ok = ok && HIP_OK(hipMalloc(&w.step_dev, nb * sizeof(k::DecStep))) && HIP_OK(hipMalloc(&w.sample_dev, nb * sizeof(k::SampleOut)))
             && HIP_OK(hipMalloc(&w.filter_scratch, k::filter_scratch_bytes(B)))
             && HIP_OK(hipHostMalloc(&w.step_host, nb * sizeof(k::DecStep), hipHostMallocDefault))
-            && HIP_OK(hipHostMalloc(&w.sample_host, nb * sizeof(k::SampleOut), hipHostMallocDefault));
+            && HIP_OK(hipHostMalloc(&w.sample_host, nb * sizeof(k::SampleOut), hipHostMallocDefault))
+            && HIP_OK(hipHostMalloc((void **) &w.lang_host, nb * k::LANG_HEAD_N * sizeof(float), hipHostMallocDefault));
     if (!ok) { WMI_ERR("%s: device allocation failed (B = %d)\n", __func__, B); w.B = 0; return false; }
     memset(w.sample_host, 0, nb * sizeof(k::SampleOut));
     w.step_seq = 0;
@@ -287,8 +289,10 @@ static bool rows_fronted(whisper_context & ctx, int nb) {
     return true;
 }
 
-static void enqueue_rows_step(whisper_context & ctx, int nb, bool chained = false, int fronted_in = -1) {
-    if (ctx.model.quantised) { enqueue_rows_step_q(ctx, nb); return; }
+// lang_out (the detection step of a call whose language is not known, full_batch): the step ends in the language head — 100 logits per
+// row to lang_out [nb][LANG_HEAD_N] (pinned) — instead of the vocabulary projection, the filters and the pick
+static void enqueue_rows_step(whisper_context & ctx, int nb, bool chained = false, int fronted_in = -1, float * lang_out = nullptr) {
+    if (ctx.model.quantised) { if (lang_out) enqueue_rows_lang_step_q(ctx, nb, lang_out); else enqueue_rows_step_q(ctx, nb); return; }
     BatchWork & b = *ctx.batch; const Weights & w = ctx.w; const HParams & hp = ctx.model.hp;
     const unsigned M = g_rows_mask;
     const int S = hp.n_text_state, H = hp.n_text_head, Lt = hp.n_text_layer, NV = hp.n_vocab, n_ctx = hp.n_text_ctx;
@@ -399,6 +403,7 @@ static void enqueue_rows_step(whisper_context & ctx, int nb, bool chained = fals
             if (M & 256) k::gemv(g, s);
         }
     }
+    if (lang_out) { k::lang_head(b.dx, nb, S, w.d_ln_g, w.d_ln_b, hp.eps, w.d_te + (size_t) (ctx.model.vocab.sot + 1) * S, lang_out, s); return; }
     {
         k::GemvArgs g = glog;
         if (mirror_in_logits) { g.rows_mirror_src = b.step_host; g.rows_mirror_dst = b.step_dev; }
@@ -496,6 +501,7 @@ struct Row {
     int seek = 0, seek_start = 0, seek_end = 0;
     bool live = false;                       // still has windows to decode in lock-step
     bool redo = false;                       // needs the temperature fallback: re-run alone
+    std::vector<int32_t> prompt_init;        // sot, (language, task), (notimestamps): the rows of a call differ in the language token only
     std::vector<int32_t> prompt;
     int n_fed = 0;                           // prompt tokens already through the decoder
     int i = 0;                               // sampled tokens accepted in this window
@@ -598,6 +604,7 @@ void free_batch(whisper_context & ctx) {
     if (w.filter_scratch) (void) hipFree(w.filter_scratch);
     if (w.step_host) (void) hipHostFree(w.step_host);
     if (w.sample_host) (void) hipHostFree(w.sample_host);
+    if (w.lang_host) (void) hipHostFree(w.lang_host);
     for (size_t i = 1; i < w.lanes.size(); ++i) free_lane_state(w.lanes[i]);
     for (whisper_context * r : w.replicas) free_replica(r);
     delete ctx.batch;
@@ -615,6 +622,13 @@ int full_batch(whisper_context & ctx, whisper_full_params params, const float * 
     if (!ctx.batch) ctx.batch = new BatchWork();
     ctx.batch->results.assign(n_chunks, {});
     ctx.batch->redo.assign(n_chunks, 0);
+    ctx.batch->lang_id.assign(n_chunks, -1); ctx.batch->lang_detected.assign(n_chunks, 0); ctx.batch->lang_probs.assign((size_t) n_chunks * k::LANG_HEAD_N, 0.0f);
+    // what whisper_full_lang_id reports after whisper_full on a chunk, and the probabilities if that call detected the language
+    auto keep_lang = [&](int c, const State & st) {
+        BatchWork & bw = *ctx.batch;
+        bw.lang_id[c] = st.lang_id; bw.lang_detected[c] = (int) st.lang_probs.size() >= k::LANG_HEAD_N;
+        if (bw.lang_detected[c]) std::copy(st.lang_probs.begin(), st.lang_probs.begin() + k::LANG_HEAD_N, bw.lang_probs.begin() + (size_t) c * k::LANG_HEAD_N);
+    };
     ctx.batch->t_mel_us = ctx.batch->t_encode_us = ctx.batch->t_decode_us = ctx.batch->t_emit_us = 0; ctx.batch->n_steps = 0; ctx.batch->n_chained = 0;
 
     auto run_alone = [&](int c) -> int {                          // the general driver, one chunk at a time
@@ -623,15 +637,18 @@ int full_batch(whisper_context & ctx, whisper_full_params params, const float * 
         // depend on which chunks were transcribed before it
         for (auto & dec : primary->decoders) dec.rng = std::mt19937(0);
         const int rc = full(ctx, params, on_device ? nullptr : pcm[c], on_device ? pcm[c] : nullptr, n_samples[c]);
-        if (rc == 0) ctx.batch->results[c] = std::move(primary->result_all);
+        if (rc == 0) { ctx.batch->results[c] = std::move(primary->result_all); keep_lang(c, *primary); }
         primary->result_all.clear();
         return rc;
     };
 
     const bool lang_known = params.language && strlen(params.language) > 0 && strcmp(params.language, "auto") != 0 && !params.detect_language;
     const bool distilled = hp.n_text_layer == 2 && !params.no_timestamps;
+    // a language to be detected: multilingual models detect every chunk in one lock-step step (below); English-only models keep the
+    // one-at-a-time path, where full() decides what "auto" means for them
+    const bool lang_ok = lang_known || (v.is_multilingual() && k::lang_head_usable(hp.n_text_state));
     const bool lockstep = params.strategy == WHISPER_SAMPLING_GREEDY && params.temperature < 1e-6f &&
-                          lang_known && !distilled && !params.speed_up && !params.logits_filter_callback && !params.grammar_rules && params.n_grammar_rules == 0 && !params.new_segment_callback &&
+                          lang_ok && !distilled && !params.speed_up && !params.logits_filter_callback && !params.grammar_rules && params.n_grammar_rules == 0 && !params.new_segment_callback &&
                           !params.progress_callback && !params.encoder_begin_callback && !params.abort_callback &&
                           ctx.model.n_loaded > 0 && n_chunks > 1;
     if (!lockstep) {
@@ -665,7 +682,7 @@ int full_batch(whisper_context & ctx, whisper_full_params params, const float * 
                     else {
                         for (auto & dec : wc.state->decoders) dec.rng = std::mt19937(0);
                         rc = full(wc, params, on_device ? nullptr : pcm[c], on_device ? pcm[c] : nullptr, n_samples[c]);
-                        if (rc == 0) ctx.batch->results[c] = std::move(wc.state->result_all);
+                        if (rc == 0) { ctx.batch->results[c] = std::move(wc.state->result_all); keep_lang(c, *wc.state); }
                         wc.state->result_all.clear();
                     }
                     if (rc != 0) { rets[w] = rc; return; }
@@ -706,7 +723,8 @@ int full_batch(whisper_context & ctx, whisper_full_params params, const float * 
         if (G > 1) G = ensure_replicas(ctx, G - 1) + 1;                    // (out of memory: fewer groups)
         if (G > 1) {
             std::vector<std::vector<Segment>> all(n_chunks);
-            std::vector<int> all_redo(n_chunks, 0), rets(G, 0), c0(G + 1, 0);
+            std::vector<int> all_redo(n_chunks, 0), rets(G, 0), c0(G + 1, 0), all_lang(n_chunks, -1);
+            std::vector<char> all_det(n_chunks, 0); std::vector<float> all_probs((size_t) n_chunks * k::LANG_HEAD_N, 0.0f);
             for (int g = 0; g < G; ++g) c0[g + 1] = c0[g] + n_chunks / G + (g < n_chunks % G ? 1 : 0);
             int64_t tm[4] = {0, 0, 0, 0}; int steps = 0, chained = 0;
             std::mutex merge_mu;
@@ -722,7 +740,11 @@ int full_batch(whisper_context & ctx, whisper_full_params params, const float * 
                     rets[g] = rc;
                     if (rc != 0 || !wc.batch) return;
                     std::lock_guard<std::mutex> lk(merge_mu);
-                    for (int i = 0; i < cnt; ++i) { all[c0[g] + i] = std::move(wc.batch->results[i]); all_redo[c0[g] + i] = wc.batch->redo[i]; }
+                    for (int i = 0; i < cnt; ++i) {
+                        all[c0[g] + i] = std::move(wc.batch->results[i]); all_redo[c0[g] + i] = wc.batch->redo[i];
+                        all_lang[c0[g] + i] = wc.batch->lang_id[i]; all_det[c0[g] + i] = wc.batch->lang_detected[i];
+                        std::copy_n(wc.batch->lang_probs.begin() + (size_t) i * k::LANG_HEAD_N, k::LANG_HEAD_N, all_probs.begin() + (size_t) (c0[g] + i) * k::LANG_HEAD_N);
+                    }
                     tm[0] = std::max(tm[0], wc.batch->t_mel_us); tm[1] = std::max(tm[1], wc.batch->t_encode_us);
                     tm[2] = std::max(tm[2], wc.batch->t_decode_us); tm[3] = std::max(tm[3], wc.batch->t_emit_us);
                     steps = std::max(steps, wc.batch->n_steps); chained = std::max(chained, wc.batch->n_chained);
@@ -740,6 +762,7 @@ int full_batch(whisper_context & ctx, whisper_full_params params, const float * 
             for (int g = 0; g < G; ++g) if (rets[g] != 0) return rets[g];
             BatchWork & bw = *ctx.batch;
             bw.results = std::move(all); bw.redo = std::move(all_redo);
+            bw.lang_id = std::move(all_lang); bw.lang_detected = std::move(all_det); bw.lang_probs = std::move(all_probs);
             bw.t_mel_us = tm[0]; bw.t_encode_us = tm[1]; bw.t_decode_us = tm[2]; bw.t_emit_us = tm[3]; bw.n_steps = steps; bw.n_chained = chained;
             bw.groups_last = G;
             return 0;
@@ -764,13 +787,16 @@ int full_batch(whisper_context & ctx, whisper_full_params params, const float * 
     } else if (params.prompt_tokens && params.prompt_n_tokens > 0) {
         prompt_user.assign(params.prompt_tokens, params.prompt_tokens + params.prompt_n_tokens);
     }
-    std::vector<int32_t> prompt_init = { v.sot };
-    if (v.is_multilingual()) {
-        const int lid = lang_id(params.language);
-        prompt_init.push_back(v.sot + 1 + lid);
-        prompt_init.push_back(params.translate ? v.translate : v.transcribe);
-    }
-    if (params.no_timestamps) prompt_init.push_back(v.not_);
+    auto prompt_init_of = [&](int lid) {
+        std::vector<int32_t> pi = { v.sot };
+        if (v.is_multilingual()) {
+            pi.push_back(v.sot + 1 + lid);
+            pi.push_back(params.translate ? v.translate : v.transcribe);
+        }
+        if (params.no_timestamps) pi.push_back(v.not_);
+        return pi;
+    };
+    const int lid_known = lang_known && v.is_multilingual() ? lang_id(params.language) : 0;
     int space_id = -1;
     { auto sp = v.token_to_id.find(" "); if (sp != v.token_to_id.end()) space_id = sp->second; }
     const int n_max = hp.n_text_ctx / 2 - 4;
@@ -778,6 +804,8 @@ int full_batch(whisper_context & ctx, whisper_full_params params, const float * 
     const int group = std::min(b.B, max_lanes);
     for (int g0 = 0; g0 < n_chunks; g0 += group) {
         const int ng = std::min(group, n_chunks - g0);
+        // a chunk without samples has nothing to detect a language from: whisper_full's "failed to auto-detect language", before any device work
+        if (!lang_known) for (int r = 0; r < ng; ++r) if (n_samples[g0 + r] <= 0) { WMI_ERR("%s: failed to auto-detect language (chunk %d is empty)\n", __func__, g0 + r); return -3; }
         std::vector<Row> rows(ng);
         // The envelopes of a lock-step call stay in HBM and the window sums + walks of the token timestamps run there (device.cpp
         // ts_refine_device, k_ts_refine: one workgroup per token, the window sum as order-free integer sums per binade over eight wavefronts —
@@ -807,7 +835,8 @@ int full_batch(whisper_context & ctx, whisper_full_params params, const float * 
             ls.ts_failed = false;
             ls.prompt_past = prompt_user;                     // every chunk is an independent transcription (no_context semantics)
             ls.exp_n_audio_ctx = params.audio_ctx;
-            if (v.is_multilingual()) ls.lang_id = lang_id(params.language);
+            if (v.is_multilingual() && lang_known) ls.lang_id = lid_known;
+            ls.lang_probs.clear();
             const int64_t tm0 = time_us();
             // kernels of all chunks are queued back to back; one synchronisation after the loop
             if (n_samples[row.chunk] > 0 && !mel_batched) {
@@ -845,6 +874,46 @@ int full_batch(whisper_context & ctx, whisper_full_params params, const float * 
             row.live = row.seek_end >= row.seek_start + 100;   // < 1 s of audio: nothing to do
         }
 
+        // ---- language detection in lock-step (the head of full() again): the encoder over every chunk of the group at seek 0 and the
+        // full audio context — each chunk is whisper_full on a fresh context, whose detection runs before the call's audio_ctx takes
+        // effect (W/whisper.cpp:5102) —, ONE step that feeds <sot> at position 0 to every row and ends in the language head (plain
+        // launches: no in-launch hand-off, its status would have no pick kernel to travel with), one wait, the host soft-max per row.
+        bool enc_at_0 = false;                                 // the cross K/V of b hold rows 0 .. ng - 1 at seek 0, full length
+        if (!lang_known) {
+            std::vector<int> lanes(ng), seeks(ng, 0);
+            for (int r = 0; r < ng; ++r) {
+                lanes[r] = r;
+                if (b.lanes[r]->mel.n_len_org <= 0) { WMI_ERR("%s: failed to auto-detect language\n", __func__); return -3; }      // (offset 0 is past the end of the audio)
+            }
+            if (!encode_rows(ctx, lanes, seeks, 0)) { WMI_ERR("%s: failed to encode\n", __func__); return -3; }
+            const int64_t td0 = time_us();
+            k::DecStep * hs = (k::DecStep *) b.step_host;
+            ++b.step_seq;
+            for (int r = 0; r < ng; ++r) {
+                memset(&hs[r], 0, sizeof(k::DecStep));
+                hs[r].token = v.sot; hs[r].pos = 0; hs[r].n_kv = 1; hs[r].kv_head = 0; hs[r].seq = b.step_seq;
+                hs[r].space_id = space_id; hs[r].eot = v.eot; hs[r].beg = v.beg; hs[r].n_vocab = v.n_vocab;
+                hs[r].ts_floor_end = v.beg; hs[r].ts_initial_start = v.n_vocab;
+            }
+            b.chain_valid = false;
+            enqueue_rows_step(ctx, ng, false, 0, b.lang_host);
+            if (!HIP_OK(hipStreamSynchronize(primary->dev.stream)) || !HIP_OK(hipGetLastError())) { WMI_ERR("%s: failed to decode\n", __func__); return -3; }
+            b.chain_valid = false;                             // (no pick ran: nothing was prepared for a next step)
+            for (int r = 0; r < ng; ++r) {
+                State & ls = *b.lanes[r];
+                ls.lang_probs.assign(k::LANG_HEAD_N, 0.0f);
+                ls.lang_id = lang_probs_from_logits(b.lang_host + (size_t) r * k::LANG_HEAD_N, ls.lang_probs.data());
+            }
+            b.t_decode_us += time_us() - td0; b.n_steps++;
+            enc_at_0 = true;
+        }
+        for (int r = 0; r < ng; ++r) {
+            const State & ls = *b.lanes[r];
+            keep_lang(g0 + r, ls);
+            rows[r].prompt_init = prompt_init_of(ls.lang_id);
+        }
+        if (params.detect_language) continue;                  // (full() returns behind the detection: no segments)
+
         // ---- windows in lock-step
         // (chunks too short for a window never reach the encoder: their envelopes are not needed either — emission only reads them for
         //  decoded tokens)
@@ -856,7 +925,10 @@ int full_batch(whisper_context & ctx, whisper_full_params params, const float * 
             {
                 std::vector<int> lanes(nb), seeks(nb);
                 for (int r = 0; r < nb; ++r) { lanes[r] = rows[act[r]].lane; seeks[r] = rows[act[r]].seek; }
-                if (!encode_rows(ctx, lanes, seeks, params.audio_ctx)) { WMI_ERR("%s: failed to encode\n", __func__); return -6; }
+                // the detection has encoded these very windows (same rows in the same order, seek 0, same length): its cross K/V are still there
+                const bool encoded = enc_at_0 && params.audio_ctx == 0 && params.offset_ms == 0 && nb == ng;
+                enc_at_0 = false;
+                if (!encoded && !encode_rows(ctx, lanes, seeks, params.audio_ctx)) { WMI_ERR("%s: failed to encode\n", __func__); return -6; }
                 b.chain_valid = false;                             // new windows, possibly other chunks in the rows: every row restarts at cell 0
             }
             for (int r = 0; r < nb; ++r) {
@@ -875,7 +947,7 @@ int full_batch(whisper_context & ctx, whisper_full_params params, const float * 
                     row.prompt.push_back(v.prev);
                     row.prompt.insert(row.prompt.end(), ls.prompt_past.end() - n_take, ls.prompt_past.end());
                 }
-                row.prompt.insert(row.prompt.end(), prompt_init.begin(), prompt_init.end());
+                row.prompt.insert(row.prompt.end(), row.prompt_init.begin(), row.prompt_init.end());
                 row.n_fed = 0; row.i = 0; row.done = false;
             }
 
@@ -965,7 +1037,7 @@ int full_batch(whisper_context & ctx, whisper_full_params params, const float * 
                 const int64_t te0 = time_us();
                 auto emit_row = [&](int ri) {
                     Row & row = rows[ri]; State & ls = *b.lanes[row.lane];
-                    emit_window(ctx, ls, params, row.seek, row.prompt, prompt_init.size(), ls.decoders[0]);
+                    emit_window(ctx, ls, params, row.seek, row.prompt, row.prompt_init.size(), ls.decoders[0]);
                     row.seek += ls.decoders[0].seek_delta;
                 };
                 // token times refined on the device (envelopes in HBM): the chunks' pending segments go in ONE launch behind the per-chunk work

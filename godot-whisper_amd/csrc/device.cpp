@@ -529,8 +529,10 @@ bool encode(whisper_context & ctx, int mel_offset, bool defer) {
 }
 
 // ------------------------------------------------------------------------------------------------ decoder
-bool decode(whisper_context & ctx, const Batch & batch) {
+bool decode(whisper_context & ctx, const Batch & batch, float * lang_logits) {
     if (!compute_ready(ctx, __func__)) return false;
+    // lang_logits: the language head in place of the vocabulary projection (one token, kernels.h: lang_head) — 100 logits, st.logits untouched
+    if (lang_logits && (batch.n_tokens != 1 || !k::lang_head_usable(ctx.model.hp.n_text_state))) return false;
     State & st = *ctx.state; DeviceState & d = st.dev; const Weights & w = ctx.w; const HParams & hp = ctx.model.hp;
     const int64_t t0 = time_us();
     d.chain_valid = false;                                  // this path overwrites the activation row a chained greedy step would start from
@@ -561,10 +563,15 @@ bool decode(whisper_context & ctx, const Batch & batch) {
     d.d_pos = d.d_tokens + n; d.d_rows = d.d_pos + n; d.d_mask = (float *) (d.d_rows + n);
     HIP_TRY(hipMemcpyAsync(d.d_tokens, p_tok, ((size_t) 3 * n + (size_t) n * n_kv) * 4, hipMemcpyHostToDevice, s));
 
+    // the language head stores its 400 bytes straight into the tail of the pinned block (the staging above uses its first bytes)
+    constexpr size_t LANG_PINNED_TAIL = 512;                // >= LANG_HEAD_N floats, kept clear of the staging block's head and of a logits copy's 16-byte pieces
+    static_assert(LANG_PINNED_TAIL >= k::LANG_HEAD_N * sizeof(float), "the language head's logits fit the tail");
+    float * const lang_pinned = lang_logits ? (float *) ((char *) d.pinned + d.pinned_bytes - LANG_PINNED_TAIL) : nullptr;
     if (ctx.model.quantised) {
-        if (!decode_layers_q(ctx, n, n_kv, kv_head, Tc, rows)) return false;
+        if (!decode_layers_q(ctx, n, n_kv, kv_head, Tc, rows, lang_pinned)) return false;
         HIP_TRY(hipStreamSynchronize(s));
         if (!HIP_OK(hipGetLastError())) return false;
+        if (lang_logits) memcpy(lang_logits, lang_pinned, k::LANG_HEAD_N * sizeof(float));
         int64_t dtq = time_us() - t0;
         { const int64_t done = phase_settle(st, false); if (done > t0) dtq = std::max<int64_t>(0, dtq - (done - t0)); }
         if (n == 1)      { st.t_decode_us += dtq; st.n_decode++; }
@@ -615,8 +622,9 @@ bool decode(whisper_context & ctx, const Batch & batch) {
 
     // final LN + logits = d_te . x for the rows that asked for them (the reference computes all rows
     // and copies out the flagged ones, W/whisper.cpp:2498, 2566-2572)
-    st.logits.resize((size_t) n * NV);
-    for (size_t r0 = 0; r0 < rows.size(); r0 += 8) {
+    if (lang_logits) k::lang_head(d.dx, 1, S, w.d_ln_g, w.d_ln_b, hp.eps, w.d_te + (size_t) (ctx.model.vocab.sot + 1) * S, lang_pinned, s);
+    else st.logits.resize((size_t) n * NV);
+    for (size_t r0 = 0; r0 < rows.size() && !lang_logits; r0 += 8) {
         const int nr = (int) std::min<size_t>(8, rows.size() - r0);
         k::GemvArgs g{};
         g.x32 = d.dx; g.ln_g = w.d_ln_g; g.ln_b = w.d_ln_b; g.eps = hp.eps; g.n = nr; g.K = S; g.N = NV; g.W = w.d_te;
@@ -630,6 +638,7 @@ bool decode(whisper_context & ctx, const Batch & batch) {
     }
     HIP_TRY(hipStreamSynchronize(s));
     if (!HIP_OK(hipGetLastError())) return false;
+    if (lang_logits) memcpy(lang_logits, lang_pinned, k::LANG_HEAD_N * sizeof(float));
 
     int64_t dt = time_us() - t0;                                  // timing buckets, W/whisper.cpp:2583-2592
     { const int64_t done = phase_settle(st, false); if (done > t0) dt = std::max<int64_t>(0, dt - (done - t0)); }      // (the part of this call spent waiting for a deferred log-mel / encoder)

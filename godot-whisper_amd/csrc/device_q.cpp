@@ -44,6 +44,20 @@ bool fc2_ksplit(k::GemvArgs & g, float * kpart) {
 
 } // namespace
 
+// The language head of a block-quantised model (kernels.h: lang_head, lang_gather): the vocabulary projection's own row kernel over the
+// 32-row tiles that cover te[sot + 1 .. sot + 100] — g is that projection's launch (rows, LayerNorm, pending K-split partial), `scratch`
+// takes rows x (<= 160) floats — and a gather of the hundred values into out [rows][LANG_HEAD_N].
+static void lang_head_q(whisper_context & ctx, k::GemvArgs g, float * scratch, float * out, hipStream_t s) {
+    const Weights & w = ctx.w; const HParams & hp = ctx.model.hp;
+    const int S = hp.n_text_state, first = ctx.model.vocab.sot + 1, tn0 = first / 32, tn1 = (first + k::LANG_HEAD_N - 1) / 32;
+    k::QMat view = w.q_te;
+    view.tiles += (size_t) tn0 * (size_t) (S / 64) * k::q_tile_bytes(view.qtype);
+    g.N = std::min((tn1 - tn0 + 1) * 32, hp.n_vocab - tn0 * 32);
+    g.C = scratch; g.ldc = g.N;
+    k::qrows(g, nullptr, view, s);
+    k::lang_gather(scratch, g.N, first - tn0 * 32, g.n, out, s);
+}
+
 bool encode_layers_q(whisper_context & ctx, int T) {
     DeviceState & d = ctx.state->dev; const int S = ctx.model.hp.n_audio_state;
     EncBufsQ e{};
@@ -106,7 +120,7 @@ bool encode_layers_q_on(whisper_context & ctx, const EncBufsQ & e, hipStream_t s
     return true;
 }
 
-bool decode_layers_q(whisper_context & ctx, int n, int n_kv, int kv_head, int Tc, const std::vector<int> & rows) {
+bool decode_layers_q(whisper_context & ctx, int n, int n_kv, int kv_head, int Tc, const std::vector<int> & rows, float * lang_out) {
     State & st = *ctx.state; DeviceState & d = st.dev; const Weights & w = ctx.w; const HParams & hp = ctx.model.hp;
     KVCache & kv = st.kv_self;
     const int S = hp.n_text_state, H = hp.n_text_head, Lt = hp.n_text_layer, NV = hp.n_vocab, n_ctx = (int) kv.size;
@@ -189,6 +203,12 @@ bool decode_layers_q(whisper_context & ctx, int n, int n_kv, int kv_head, int Tc
         proj(k::EPI_F32_BIAS_RESID, hh, 4 * S, S, l.q_fc2, l.b_fc2, d.dx, S, d.dx, nullptr, 0, nullptr, 0, 0.f, true);
     }
 
+    if (lang_out) {                                         // (decode(): one token) the language rows only
+        k::GemvArgs g{};
+        g.x32 = d.dx; g.ln_g = w.d_ln_g; g.ln_b = w.d_ln_b; g.eps = hp.eps; g.n = 1; g.K = S; g.epi = k::EPI_LOGITS; g.rows = d.d_rows; g.pend = pend;
+        lang_head_q(ctx, g, d.logits, lang_out, s);
+        return true;
+    }
     // final LN + logits for the flagged rows
     st.logits.resize((size_t) n * NV);
     for (size_t r0 = 0; r0 < rows.size(); r0 += 8) {
@@ -273,7 +293,10 @@ void enqueue_greedy_step_q(whisper_context & ctx, int Tc) {
 
 // One lock-step greedy step of a block-quantised model: nb chunk rows through the same launches (batch.cpp: enqueue_rows_step is
 // the f16 form).  Row r has its own self cache (+ r * cache_stride), cross-cache slice and step record.
-void enqueue_rows_step_q(whisper_context & ctx, int nb) {
+static void enqueue_rows_step_q_(whisper_context & ctx, int nb, float * lang_out);
+void enqueue_rows_step_q(whisper_context & ctx, int nb) { enqueue_rows_step_q_(ctx, nb, nullptr); }
+void enqueue_rows_lang_step_q(whisper_context & ctx, int nb, float * out) { enqueue_rows_step_q_(ctx, nb, out); }
+static void enqueue_rows_step_q_(whisper_context & ctx, int nb, float * lang_out) {
     BatchWork & b = *ctx.batch; const Weights & w = ctx.w; const HParams & hp = ctx.model.hp;
     const int S = hp.n_text_state, H = hp.n_text_head, Lt = hp.n_text_layer, NV = hp.n_vocab, n_ctx = hp.n_text_ctx;
     const int Tc = b.enc_T;
@@ -337,6 +360,10 @@ void enqueue_rows_step_q(whisper_context & ctx, int nb) {
         k::qrows(rows(k::EPI_F32_BIAS_RESID, hh, 4 * S, S, l.q_fc2, l.b_fc2, b.dx, S, b.dx, nullptr, nullptr, 0.f, nullptr), nullptr, l.q_fc2, s);
     }
     Src lnf; lnf.x32 = b.dx; lnf.ln_g = w.d_ln_g; lnf.ln_b = w.d_ln_b;
+    if (lang_out) {                                         // detection step: the language rows instead of the vocabulary, no filters, no pick
+        lang_head_q(ctx, rows(k::EPI_LOGITS, lnf, S, NV, w.q_te, nullptr, b.logits, NV, nullptr, nullptr, nullptr, 0.f, nullptr), b.logits, lang_out, s);
+        return;
+    }
     k::qrows(rows(k::EPI_LOGITS, lnf, S, NV, w.q_te, nullptr, b.logits, NV, nullptr, nullptr, nullptr, 0.f, nullptr), nullptr, w.q_te, s);
     k::filter_argmax(b.logits, ctx.state->dev.ban_dev, stp, (k::SampleOut *) b.sample_dev, b.filter_scratch, s, (k::SampleOut *) b.sample_host, nb);
 }

@@ -63,6 +63,7 @@ int full(whisper_context & ctx, whisper_full_params params, const float * sample
     const HParams & hp = ctx.model.hp;
     st.result_all.clear();
     st.ts_failed = false;
+    st.lang_probs.clear();
     // the envelope kernel reads the caller's samples on a side stream: never return while it is in flight
     struct EnvelopeGuard { State & st; ~EnvelopeGuard() { (void) signal_energy_wait(st); } } envelope_guard{st};
     static const bool defer_phases = getenv("WMI_PHASE_SYNC") == nullptr;
@@ -75,10 +76,18 @@ int full(whisper_context & ctx, whisper_full_params params, const float * sample
         if (!ok_mel) { WMI_ERR("%s: failed to compute log mel spectrogram\n", __func__); return -2; }
     }
 
+    // > 0: the cross K/V in the state are the encoder's output for the window at seek 0 at this length (the detection's pass)
+    int enc_at_0 = 0;
     if (params.language == nullptr || strlen(params.language) == 0 || strcmp(params.language, "auto") == 0 || params.detect_language) {
         std::vector<float> probs(lang_max_id() + 1, 0.0f);
-        const int lid = lang_auto_detect(ctx, 0, probs.data());
+        // through the language head (host_logic.cpp: lang_detect_head): the <sot> step ends in the 100 language logits instead of the
+        // vocabulary's, and the log-mel / encoder in front of it are not waited for on their own.  The encoder runs at the audio context
+        // of the PREVIOUS call (exp_n_audio_ctx is set below, as in the reference: W/whisper.cpp:5102)
+        const bool head = k::lang_head_usable(hp.n_text_state);
+        const int lid = head ? lang_detect_head(ctx, 0, probs.data(), defer_phases) : lang_auto_detect(ctx, 0, probs.data());
         if (lid < 0) { WMI_ERR("%s: failed to auto-detect language\n", __func__); return -3; }
+        enc_at_0 = st.enc_n_ctx;
+        st.lang_probs = probs;
         st.lang_id = lid;
         params.language = lang_str(lid);
         WMI_INFO("%s: auto-detected language: %s (p = %f)\n", __func__, params.language, probs[lid]);
@@ -164,7 +173,10 @@ int full(whisper_context & ctx, whisper_full_params params, const float * sample
             WMI_ERR("%s: encoder_begin_callback returned false - aborting\n", __func__);
             break;
         }
-        if (!encode(ctx, seek, defer_phases) || (params.abort_callback && params.abort_callback(params.abort_callback_user_data))) {
+        // the detection has encoded this very window (seek 0, same length): the encoder is deterministic, its output is still in the state
+        const bool encoded = enc_at_0 > 0 && seek == 0 && enc_at_0 == (st.exp_n_audio_ctx > 0 ? st.exp_n_audio_ctx : hp.n_audio_ctx);
+        enc_at_0 = 0;
+        if ((!encoded && !encode(ctx, seek, defer_phases)) || (params.abort_callback && params.abort_callback(params.abort_callback_user_data))) {
             WMI_ERR("%s: failed to encode\n", __func__);
             return -6;
         }

@@ -100,6 +100,7 @@ const Lang k_langs[] = {
 constexpr int k_n_langs = (int) (sizeof(k_langs) / sizeof(k_langs[0]));
 } // namespace
 
+static_assert(k_n_langs == k::LANG_HEAD_N, "the language head computes one logit per entry of this table");
 int lang_count()  { return k_n_langs; }
 int lang_max_id() { return k_n_langs - 1; }
 int lang_id(const char * lang) {
@@ -321,8 +322,31 @@ int lang_auto_detect(whisper_context & ctx, int offset_ms, float * lang_probs) {
     st.batch.prep_legacy(&sot, 1, 0, 0);
     kv_seq_rm(st.kv_self, 0, 0, -1);
     if (!decode(ctx, st.batch)) { WMI_ERR("%s: failed to decode\n", __func__); return -7; }
+    return lang_probs_from_logits(st.logits.data() + sot + 1, lang_probs);
+}
+
+// The same detection through the language head (k::lang_head): the <sot> step's decoder layers, then the final LayerNorm and the 100 rows
+// te[sot + 1 .. sot + 100] only — 400 bytes come back instead of the vocabulary's logits, which are not defined afterwards.  defer: no host
+// wait behind the log-mel / encoder (full()).  The 100 logits equal the full projection's entries bit for bit, so do the results.
+int lang_detect_head(whisper_context & ctx, int offset_ms, float * lang_probs, bool defer) {
+    State & st = *ctx.state;
+    const int seek = offset_ms / 10;
+    if (seek < 0) { WMI_ERR("%s: offset %dms is before the start of the audio\n", __func__, offset_ms); return -1; }
+    if (seek >= st.mel.n_len_org) { WMI_ERR("%s: offset %dms is past the end of the audio (%dms)\n", __func__, offset_ms, st.mel.n_len_org * 10); return -2; }
+    if (!encode(ctx, seek, defer)) { WMI_ERR("%s: failed to encode\n", __func__); return -6; }
+    const int32_t sot = ctx.model.vocab.sot;
+    st.batch.prep_legacy(&sot, 1, 0, 0);
+    kv_seq_rm(st.kv_self, 0, 0, -1);
+    float logits[k::LANG_HEAD_N];
+    if (!decode(ctx, st.batch, logits)) { WMI_ERR("%s: failed to decode\n", __func__); return -7; }
+    return lang_probs_from_logits(logits, lang_probs);
+}
+
+// 100 f32 logits (entries sot + 1 .. sot + 100 of the <sot> step) -> language id and probabilities (W/whisper.cpp:3600-3641): the one
+// definition behind every detection route
+int lang_probs_from_logits(const float * logits, float * lang_probs) {
     std::vector<std::pair<double, int>> cand;
-    for (int i = 0; i < lang_count(); ++i) cand.emplace_back((double) st.logits[sot + 1 + i], i);
+    for (int i = 0; i < lang_count(); ++i) cand.emplace_back((double) logits[i], i);
     // the reference sorts a std::map iteration (keyed by language code) with std::sort; ties are
     // broken by that order, so reproduce it: sort ids by code first, then stable-sort by logit
     std::sort(cand.begin(), cand.end(), [](const std::pair<double, int> & a, const std::pair<double, int> & b) {

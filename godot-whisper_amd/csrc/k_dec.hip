@@ -1727,7 +1727,81 @@ void launch_gemv(const GemvArgs & a, hipStream_t st) {
     else                        launch_gemv_t<R, 4>(a, st);
 }
 
+// ------------------------------------------------------------------------------------------------ language head
+// The 100 language logits of a decoder row (kernels.h: lang_head): what k_gemv1's LayerNorm prologue + EPI_LOGITS computes for the rows
+// te[sot + 1 .. sot + 100], without the other 51 765 rows of the matrix (256 KB instead of 133 MB on large-v3).  Row = grid.y; a wavefront
+// owns four weight rows: 25 wavefronts hold the hundred, the grid's other three (7 workgroups of 4) re-read row 99 and store nothing.  Per value the operations and their order are k_gemv1's: ln_row_compute on the row
+// (chunks past K are exact zeros), one fmaf chain per lane over (chunk, element), the 64-lane sum in the xor order 32, 16, .. 1 (k_gemv1
+// folds its row tile by halving exchange — the same pairs, and addition commutes).  Independent workgroups, no atomics; every load is
+// unconditional from a clamped address and issued before the first wait.
+template <int NCH>
+__global__ __launch_bounds__(256) void k_lang_head(const float * __restrict__ x, const float * __restrict__ ln_g, const float * __restrict__ ln_b,
+                                                   float eps, int K, const __half * __restrict__ W, float * __restrict__ out) {
+    constexpr int RIF = 4;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int o0 = ((int) blockIdx.x * 4 + wave) * RIF;
+    const int y = blockIdx.y;
+    float xv[NCH][8], gv[NCH][8], bv[NCH][8], av[NCH][8];
+    ln_row_load<NCH>(x + (size_t) y * K, K, lane, xv);
+    ln_row_load<NCH>(ln_g, K, lane, gv);
+    ln_row_load<NCH>(ln_b, K, lane, bv);
+    uint4 w[NCH][RIF];
+#pragma unroll
+    for (int t = 0; t < NCH; ++t) {
+        const int c = lane * 8 + 512 * t, cc = c < K ? c : 0;    // (columns past K: the activation there is exactly 0)
+#pragma unroll
+        for (int u = 0; u < RIF; ++u) {
+            int o = o0 + u; if (o > LANG_HEAD_N - 1) o = LANG_HEAD_N - 1;
+            w[t][u] = *(const uint4 *) (W + (size_t) o * K + cc);
+        }
+    }
+    ln_row_mask<NCH>(xv, K, lane); ln_row_mask<NCH>(gv, K, lane); ln_row_mask<NCH>(bv, K, lane);
+    ln_row_compute<NCH>(xv, gv, bv, K, eps, lane, av);
+    float acc[RIF];
+#pragma unroll
+    for (int u = 0; u < RIF; ++u) acc[u] = 0.0f;
+#pragma unroll
+    for (int t = 0; t < NCH; ++t)
+#pragma unroll
+        for (int u = 0; u < RIF; ++u) {
+            const __half2 * h = (const __half2 *) &w[t][u];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float2 f = __half22float2(h[e]);
+                acc[u] = fmaf(f.x, av[t][2 * e], acc[u]);
+                acc[u] = fmaf(f.y, av[t][2 * e + 1], acc[u]);
+            }
+        }
+    _Pragma("unroll") for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+        for (int u = 0; u < RIF; ++u) acc[u] += WMI_SHX(acc[u], o);
+    }
+    // lane u writes row o0 + u (every lane holds every total)
+    float v = acc[0];
+#pragma unroll
+    for (int u = 1; u < RIF; ++u) v = lane == u ? acc[u] : v;
+    if (lane < RIF && o0 + lane < LANG_HEAD_N) out[(size_t) y * LANG_HEAD_N + o0 + lane] = v;
+}
+
+__global__ void k_lang_gather(const float * __restrict__ src, int ld, int off, float * __restrict__ out) {
+    const int i = threadIdx.x, r = blockIdx.x;
+    if (i < LANG_HEAD_N) out[(size_t) r * LANG_HEAD_N + i] = src[(size_t) r * ld + off + i];
+}
+
 } // namespace
+
+bool lang_head_usable(int S) { return S >= 8 && S <= 1536 && (S % 8) == 0; }
+void lang_head(const float * x, int rows, int S, const float * ln_g, const float * ln_b, float eps, const __half * te_lang, float * out, hipStream_t st) {
+    const dim3 grid((LANG_HEAD_N + 15) / 16, rows), block(256);
+    switch ((S + 511) / 512) {
+        case 1: hipLaunchKernelGGL(k_lang_head<1>, grid, block, 0, st, x, ln_g, ln_b, eps, S, te_lang, out); break;
+        case 2: hipLaunchKernelGGL(k_lang_head<2>, grid, block, 0, st, x, ln_g, ln_b, eps, S, te_lang, out); break;
+        default: hipLaunchKernelGGL(k_lang_head<3>, grid, block, 0, st, x, ln_g, ln_b, eps, S, te_lang, out); break;
+    }
+}
+void lang_gather(const float * src, int ld, int off, int rows, float * out, hipStream_t st) {
+    hipLaunchKernelGGL(k_lang_gather, dim3(rows), dim3(128), 0, st, src, ld, off, out);
+}
 
 void dec_embed(const int32_t * tokens, const int32_t * pos, int n, int S, const __half * te, const float * pe,
                float * x, hipStream_t st) {

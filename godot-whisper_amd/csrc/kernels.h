@@ -302,6 +302,17 @@ void attn_cross_combine(const float * part_o, const float * part_l, const float 
                         float * out32 = nullptr);
 enum { EPI_LOGITS = 100 };                    // C f32 [n][N] = acc
 void gemv(const GemvArgs & a, hipStream_t st);
+// The language head (k_lang_head): the logits of the 100 language tokens behind <sot> and nothing else of the vocabulary —
+// out[r][i] = te_lang[i] . f16(LN(x[r])), r < rows (grid.y, the lock-step convention), te_lang = te + (sot + 1) S.  Always LANG_HEAD_N rows,
+// whatever the vocabulary holds there (W/whisper.cpp:3603-3606).  Every value equals, bit for bit, the entry the one-row vocabulary
+// projection (gemv, EPI_LOGITS) writes for the same row: ln_row_compute's LayerNorm, the activation rounded to f16 at the same point, the
+// same per-lane fmaf chain over the columns and the same 64-lane butterfly.  out may be pinned host memory.  S <= 1536, S % 8 == 0.
+constexpr int LANG_HEAD_N = 100;
+bool lang_head_usable(int S);
+void lang_head(const float * x, int rows, int S, const float * ln_g, const float * ln_b, float eps, const __half * te_lang, float * out, hipStream_t st);
+// block-quantised models: the language rows are cut out of the row kernel's output over the 32-row tiles that cover them (k_qrows'
+// per-row results do not depend on the rows that share a launch): out[r][i] = src[r * ld + off + i], i < LANG_HEAD_N
+void lang_gather(const float * src, int ld, int off, int rows, float * out, hipStream_t st);
 
 // One decoder MLP of the one-row step as ONE launch: x += W2 . gelu(W1 . LN(x) + b1) + b2 (k_mlp_pair, k_dec.hip).  The hidden row goes
 // from the workgroups that produce it to every workgroup of the same launch through data-tagged 8-byte granules ({two f16, tag}, written

@@ -269,6 +269,7 @@ struct State {
     std::vector<Segment> result_all;
     std::vector<int32_t> prompt_past;
     int     lang_id = 0;
+    std::vector<float> lang_probs;                // the language probabilities of the last full() that detected its language (empty: it did not)
     int64_t t_beg = 0, t_last = 0; int32_t tid_last = 0;
     const float * energy = nullptr; int energy_n = 0;   // |x| envelope of the last PCM (view of dev.energy_host)
     const float * energy_bmin = nullptr, * energy_bmax = nullptr;   // its per-256-sample block extrema
@@ -313,6 +314,9 @@ struct BatchWork {
     std::vector<State *> lanes;                               // lanes[0] is the context's own state (not owned)
     std::vector<std::vector<Segment>> results;                // per chunk of the last wmi_full_batch call
     std::vector<int> redo;                                    // per chunk: 1 if it was re-run alone (temperature fallback)
+    // per chunk: the language id whisper_full would report, whether it was detected, and the detection's probabilities [chunk][LANG_HEAD_N]
+    std::vector<int> lang_id; std::vector<char> lang_detected; std::vector<float> lang_probs;
+    float  * lang_host = nullptr;                             // pinned: the language head's logits of a detection step [B][LANG_HEAD_N]
     // chunks that cannot advance in lock-step (beam search, t > 0, quantised beams ...) run through the general driver on replica
     // contexts: own state and stream, the weight arena borrowed from this context — see full_batch
     std::vector<whisper_context *> replicas; int replicas_wanted = -1;      // -1: default (WMI_BATCH_REPLICAS, 3)
@@ -401,7 +405,8 @@ bool set_mel(whisper_context & ctx, const float * data, int n_len, int n_mel);
 bool encode(whisper_context & ctx, int mel_offset, bool defer = false);
 // lock-step chunks (batch.cpp): rows[r] = lane whose mel feeds chunk row r, seek[r] = its mel frame offset
 bool encode_rows(whisper_context & ctx, const std::vector<int> & rows, const std::vector<int> & seek, int audio_ctx);
-bool decode(whisper_context & ctx, const Batch & batch);
+// lang_logits (one token): the language head instead of the vocabulary projection — k::LANG_HEAD_N logits go to lang_logits, st.logits is left alone
+bool decode(whisper_context & ctx, const Batch & batch, float * lang_logits = nullptr);
 // block-quantised models (device_q.cpp): the layer loops of encode() / decode() with the quantised kernels
 template <typename BUFS> inline k::Q8Rows q8_rows(const BUFS & d, int K) {
     return k::Q8Rows{d.aq, d.ads, d.ads + (size_t) (K / 32) * d.aq_rows, d.aq_rows, d.aq16, d.wq16, d.wq16_elems};
@@ -416,7 +421,8 @@ struct EncBufsQ {
 };
 bool encode_layers_q_on(whisper_context & ctx, const EncBufsQ & e, hipStream_t s);
 void enqueue_rows_step_q(whisper_context & ctx, int nb);
-bool decode_layers_q(whisper_context & ctx, int n, int n_kv, int kv_head, int Tc, const std::vector<int> & rows);
+void enqueue_rows_lang_step_q(whisper_context & ctx, int nb, float * out);      // the same step ending in the language head (batch.cpp: detection)
+bool decode_layers_q(whisper_context & ctx, int n, int n_kv, int kv_head, int Tc, const std::vector<int> & rows, float * lang_out = nullptr);
 void enqueue_greedy_step_q(whisper_context & ctx, int Tc);
 // greedy fast path: decode ONE token of sequence 0 at position `pos` and pick the next token on the device
 struct StepFilter { bool ban_blank, last_ts, penult_ts; int ts_floor_end, ts_initial_start; };
@@ -482,6 +488,8 @@ void grammar_penalise(const whisper_context & ctx, const Grammar & g, float pena
 void grammar_accept_token(const whisper_context & ctx, Grammar & g, int32_t token);
 std::vector<int32_t> tokenize(const Vocab & vocab, const std::string & text);
 int  lang_auto_detect(whisper_context & ctx, int offset_ms, float * lang_probs);
+int  lang_detect_head(whisper_context & ctx, int offset_ms, float * lang_probs, bool defer = false);     // the same through the language head
+int  lang_probs_from_logits(const float * logits, float * lang_probs);       // k::LANG_HEAD_N logits -> id, probabilities (lang_probs may be null)
 int  full(whisper_context & ctx, whisper_full_params params, const float * samples, const float * d_samples, int n_samples);
 // several independent chunks in lock-step (batch.cpp); results per chunk in ctx.batch->results
 int  full_batch(whisper_context & ctx, whisper_full_params params, const float * const * pcm, const int * n_samples, int n_chunks, bool on_device);

@@ -135,9 +135,11 @@ class SpeechToText:
             return []
         out = []
         self.last_modes = []
+        self.last_langs = []                                          # per chunk: the language id whisper_full would report (detected with "auto")
         for c in range(n):
             assert self.lib.wmi_batch_select(self.ctx, c) >= 0
             self.last_modes.append(self.lib.wmi_batch_chunk_mode(self.ctx, c))
+            self.last_langs.append(self.lib.wmi_batch_lang_id(self.ctx, c))
             out.append(self.collect())
         return out
 

@@ -114,6 +114,7 @@ std::vector<Transcription> SpeechToText::transcribe_batch(const std::vector<std:
         fprintf(stderr, "ERROR: Context instance is null\n");
         return out;
     }
+    last_langs.clear();
     std::vector<const float *> ptrs; std::vector<int> lens;
     for (const auto & b : buffers) { ptrs.push_back(b.data()); lens.push_back((int) b.size()); }
     const int ret = wmi_full_batch(context_instance, whisper_params, ptrs.data(), lens.data(), (int) buffers.size(), 0);
@@ -124,6 +125,7 @@ std::vector<Transcription> SpeechToText::transcribe_batch(const std::vector<std:
     }
     for (int c = 0; c < (int) buffers.size(); ++c) {
         wmi_batch_select(context_instance, c);
+        last_langs.push_back(wmi_batch_lang_id(context_instance, c));
         out.push_back(collect());
     }
     return out;

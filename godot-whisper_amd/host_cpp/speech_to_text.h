@@ -72,6 +72,7 @@ public:
 
     whisper_context * context() { return context_instance; }
     int last_return = 0;          // whisper_full's code of the last transcribe()
+    std::vector<int> last_langs;  // transcribe_batch: per chunk the language id whisper_full would report (the detected one with Language "auto")
 
 protected:
     whisper_full_params make_params(const std::string & initial_prompt, int audio_ctx) const;

@@ -27,6 +27,10 @@ DEVICE_API = [
     ("wmi_set_lockstep_exact", None, [C.c_int]),
     ("wmi_batch_select", C.c_int, [C.c_void_p, C.c_int]),
     ("wmi_batch_chunk_mode", C.c_int, [C.c_void_p, C.c_int]),
+    ("wmi_batch_lang_id", C.c_int, [C.c_void_p, C.c_int]),
+    ("wmi_batch_lang_probs", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float)]),
+    ("wmi_lang_detect", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float)]),
+    ("wmi_selftest_lang_probs", C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     ("wmi_set_batch_replicas", C.c_int, [C.c_void_p, C.c_int]),
     ("wmi_set_lockstep_groups", C.c_int, [C.c_void_p, C.c_int]),
     ("wmi_selftest_pool", C.c_int64, [C.c_int, C.c_int]),

@@ -128,8 +128,16 @@ WHISPER_API int wmi_vad(struct whisper_context * ctx, const float * pcm, int n_s
  * one decode step = one token for every chunk.  Up to 16 chunks advance together; more are processed in groups of 16.
  * replaces: the per-worker loop of whisper_full_parallel (W/whisper.cpp:5809-5935: shared model, one
  * whisper_state per worker) — workers are rows of the same kernels instead of threads.
- * Lock-step needs greedy sampling at temperature 0 without callbacks and a known language; otherwise, and for
- * any chunk that triggers the temperature fallback, the chunk is run alone through the whisper_full driver.
+ * Lock-step needs greedy sampling at temperature 0 without callbacks; otherwise, and for any chunk that triggers the
+ * temperature fallback, the chunk is run alone through the whisper_full driver.  The language need not be known: with
+ * params.language "auto" / empty / NULL (or params.detect_language) a multilingual model detects every chunk's language in ONE
+ * lock-step step in front of the windows — the encoder over all chunks at seek 0 and the full audio context (each chunk is
+ * whisper_full on a fresh context), <sot> through the decoder layers, the language head (100 logits per chunk) — after which the
+ * chunks' prompts differ in their language token only, which the per-row step records carry anyway.  The first window reuses that
+ * encoder pass when params.audio_ctx and params.offset_ms are 0.  Chunks shorter than 1 s are detected too and report their
+ * language without segments; an empty chunk makes the call return -3 (as whisper_full does) before any device work of its group;
+ * with params.detect_language the call ends after the detection.  English-only models with "auto" keep the one-at-a-time path.
+ * wmi_batch_lang_id / wmi_batch_lang_probs read the results.
  * pcm[c] are host pointers, or device pointers when pcm_on_device != 0.  Returns whisper_full's codes. */
 WHISPER_API int wmi_full_batch(struct whisper_context * ctx, struct whisper_full_params params, const float * const * pcm,
                                const int * n_samples, int n_chunks, int pcm_on_device);
@@ -139,10 +147,28 @@ WHISPER_API int wmi_full_batch(struct whisper_context * ctx, struct whisper_full
  * then agree bit for bit (used by the parity tests; process-wide debug switch, set it before both calls). */
 WHISPER_API void wmi_set_lockstep_exact(int on);
 /* Make the whisper_full_n_segments / whisper_full_get_* accessors (W/whisper.h:541-575) read chunk `chunk` of the
- * last wmi_full_batch call.  Returns its segment count, -1 for a bad index. */
+ * last wmi_full_batch call; whisper_full_lang_id(ctx) is that chunk's language id from then on.  Returns its segment count, -1 for a
+ * bad index. */
 WHISPER_API int wmi_batch_select(struct whisper_context * ctx, int chunk);
 /* 0: chunk `chunk` was decoded in lock-step; 1: it was run alone (fallback, see above); -1: bad index. */
 WHISPER_API int wmi_batch_chunk_mode(struct whisper_context * ctx, int chunk);
+/* Language of chunk `chunk` of the last wmi_full_batch call: the id whisper_full_lang_id would report after whisper_full on that chunk
+ * (detected, or params.language's; a chunk that left lock-step reports what its own whisper_full run detected).  -1: bad index. */
+WHISPER_API int wmi_batch_lang_id(struct whisper_context * ctx, int chunk);
+/* The 100 language probabilities of that chunk's detection (whisper_lang_auto_detect's lang_probs) into probs100.  0, or -1 for a bad
+ * index / a chunk whose language was not detected (known language, English-only model). */
+WHISPER_API int wmi_batch_lang_probs(struct whisper_context * ctx, int chunk, float * probs100);
+
+/* whisper_lang_auto_detect (W/whisper.cpp:3569-3650) through the language head: the encoder at offset_ms, <sot> through the decoder
+ * layers, then the final LayerNorm and the 100 token-embedding rows behind <sot> only (k_lang_head) instead of the vocabulary
+ * projection — 400 bytes cross PCIe instead of the logits.  Same ids, same probabilities (the 100 logits equal the projection's entries
+ * bit for bit and both routes share the host soft-max), same return codes (-1 offset before the audio, -2 past its end, -6 encode, -7
+ * decode); lang_probs may be NULL.  Unlike after whisper_lang_auto_detect, whisper_get_logits is NOT defined afterwards.  whisper_full
+ * detects this way ("auto"), and skips its first encoder pass when the detection has encoded that window.
+ * How the 400 bytes arrive: the kernel stores them straight into pinned host memory and the host takes them behind ONE stream
+ * synchronisation at the end of the step — not by polling a tag as the greedy step's SampleOut is polled (100 floats are 25 separate
+ * 16-byte stores; a tag per piece was not built).  There is no separate wait behind the log-mel / encoder either way. */
+WHISPER_API int wmi_lang_detect(struct whisper_context * ctx, int offset_ms, float * lang_probs);
 /* Lock-step calls in GROUPS side by side: wmi_full_batch deals its lock-step chunks to `n` contiguous ranges, each a lock-step call of its
  * own — range 0 on this context, the others on replica contexts (own state, stream and work set; the weights are borrowed) on host threads
  * of their own.
@@ -192,7 +218,10 @@ WHISPER_API int wmi_mel_dims(struct whisper_context * ctx, int * n_len, int * n_
  * calls whisper_pcm_to_mel / whisper_encode / whisper_decode, block-quantised models, lock-step calls, WMI_PHASE_SYNC=1) waits behind each
  * phase and records host wall time.  A consequence for errors: a device fault inside the deferred encoder surfaces at the first decode
  * step's wait, i.e. as whisper_full's "failed to decode" (-7 / -8) rather than "failed to encode" (-6); a faulted device fails every later
- * call either way. */
+ * call either way.
+ * n_encode counts the encoder passes that actually ran: whisper_full with language "auto" on one window reports ONE (the detection's pass
+ * is the first window's when offset_ms is 0 and the audio context in effect at detection time — the previous call's, 0 on a fresh
+ * state — is the one the call asks for), two otherwise. */
 WHISPER_API void wmi_get_timings(struct whisper_context * ctx, int64_t * t6, int32_t * n5);
 
 /* The context's HIP stream (as void*), so a caller can order its own work / events against the hot path. */
@@ -293,6 +322,9 @@ WHISPER_API int wmi_selftest_quant(int device, int qtype, int mode, const void *
  *   which = 6  the logits projection over a rotating set of copies of the matrix (> 256 MiB in total): an HBM figure, where
  *              which = 1 re-streams one matrix that the 256 MiB Infinity Cache holds
  *   which = 10..12  chains of trivial dependent kernels on 1 / 32 / 256 workgroups (launch floor)
+ *   which = 13  the language head (k_lang_head: final LayerNorm + the 100 language rows of the token embedding) on the row which = 1
+ *               projects — what a detection step runs instead of which = 1 (f16 models; -1 on a block-quantised model, whose
+ *               language head is the row kernel over a slice of the matrix)
  *   which = 20  the kernels of the last greedy decode step back to back, no host in the loop (microseconds per step);
  *               the environment variable WMI_STEP_MASK selects kernel kinds (bit 0 embed, 1 q|k|v, 2 self-attention + out,
  *               3 cross scores, 4 cross combine + out, 5 mlp.0, 6 mlp.2, 7 logits, 8 filters)
@@ -335,6 +367,10 @@ WHISPER_API int wmi_encoder_gemm_stamps(struct whisper_context * ctx, int chunks
  * (W/whisper.cpp:6506-6515), evaluated in blocks as integer additions wherever that is exact (csrc/full.cpp: seq_sum_f32).
  * out_blocked = that routine's result for x[0..n), out_plain = the plain loop's; they must have the same bits.  Returns 0. */
 WHISPER_API int wmi_selftest_seqsum(const float * x, int n, float * out_blocked, float * out_plain);
+/* Test hook, host only: the soft-max and tie order every language detection route ends in (100 f32 logits -> probs100, optional;
+ * returns the language id: sorted by language code, stable-sorted by logit, exp in double relative to the maximum, summed in that order
+ * — W/whisper.cpp:3600-3641).  -1: logits100 is NULL. */
+WHISPER_API int wmi_selftest_lang_probs(const float * logits100, float * probs100);
 
 /* Host worker pool self-test (no device needed): `reps` jobs of `n_tasks` tasks; returns reps * n_tasks * (n_tasks + 1) / 2
  * when every task of every job ran exactly once. */
