@@ -611,31 +611,65 @@ int wmi_selftest_resample_plan(int n_frames, int src_rate, int dst_rate, int con
     } catch (...) { return -3; }
 }
 
+// alpha exactly as the host computes it (src/speech_to_text.cpp:54-56): Math_PI is a double constant, rc is rounded to float
+static float vad_alpha(float freq_thold, int sample_rate) {
+    const float rc = (float) (1.0f / (2.0f * 3.14159265358979323846 * freq_thold));
+    const float dt = 1.0f / (float) sample_rate;
+    return dt / (rc + dt);
+}
+
+// _vad_simple on a window of n samples, `win` a host or a device pointer.  form 0: k_vad, the definition (one lane, sample order);
+// form 1: the filter in blocks with the hand-over check (k_vad_blocks / k_vad_finish), the same bits.  One wait: the kernel stores its
+// results straight into pinned host memory.  stats2 (optional): {blocks, blocks re-run}, 0 0 for form 0.
+static int vad_run(whisper_context * ctx, const float * win, int n, int n_last, int on_device, float alpha, bool filter, float vad_thold,
+                   int form, int warm, float * energies, int32_t * stats2) {
+    hipStream_t s = ctx->state->dev.stream;
+    if (!ctx->vad_res && !HIP_OK(hipHostMalloc((void **) &ctx->vad_res, 32, hipHostMallocDefault))) return -3;
+    const size_t scratch_bytes = form == 1 ? k::vad_scratch_bytes(n) : 0;
+    float * d = nullptr;
+    if (scratch_bytes || !on_device) {
+        d = dsp_scratch(ctx, scratch_bytes + (on_device ? 0 : (size_t) n * 4));
+        if (!d) return -3;
+    }
+    bool ok = true;
+    if (!on_device) {
+        float * d_win = (float *) ((char *) d + scratch_bytes);
+        ok = HIP_OK(hipMemcpyAsync(d_win, win, (size_t) n * 4, hipMemcpyHostToDevice, s));
+        win = d_win;
+    }
+    volatile float * res = ctx->vad_res;
+    ((volatile int32_t *) res)[4] = 0; ((volatile int32_t *) res)[5] = 0;
+    if (ok) {
+        if (form == 1) k::vad_window_blocks(win, n, n_last, alpha, filter, vad_thold, warm, d, ctx->vad_res, s);
+        else k::vad_window(win, n, n_last, alpha, filter, vad_thold, ctx->vad_res, s);
+    }
+    ok = ok && HIP_OK(hipGetLastError()) && HIP_OK(hipStreamSynchronize(s));
+    if (!ok) return -3;
+    if (energies) { energies[0] = res[1]; energies[1] = res[2]; }
+    if (stats2) { stats2[0] = ((volatile int32_t *) res)[4]; stats2[1] = ((volatile int32_t *) res)[5]; }
+    return res[0] != 0.0f ? 1 : 0;
+}
+
 int wmi_vad(struct whisper_context * ctx, const float * pcm, int n_samples, int on_device, float vad_thold, float freq_thold, float * energies) {
     if (!ctx || !ctx->state || ctx->host_only || !pcm || n_samples < 0) return -1;
     const int n_win = WHISPER_SAMPLE_RATE * 3, n_last = (WHISPER_SAMPLE_RATE * 500) / 1000;      // src/speech_to_text.cpp:381-386
     if (n_samples < n_win) return 0;                                                              // not enough accumulated audio
     CtxScope lk(ctx);
     if (!HIP_OK(hipSetDevice(ctx->device))) return -2;
-    hipStream_t s = ctx->state->dev.stream;
-    // alpha exactly as the host computes it (:54-56): Math_PI is a double constant, rc is rounded to float
-    const float rc = (float) (1.0f / (2.0f * 3.14159265358979323846 * freq_thold));
-    const float dt = 1.0f / (float) WHISPER_SAMPLE_RATE;
-    const float alpha = dt / (rc + dt);
-    if (!ctx->vad_res && !HIP_OK(hipHostMalloc((void **) &ctx->vad_res, 16, hipHostMallocDefault))) return -3;
-    bool ok = true;
-    const float * win = pcm + (n_samples - n_win);
-    if (!on_device) {
-        float * d_win = dsp_scratch(ctx, (size_t) n_win * 4);
-        ok = d_win && HIP_OK(hipMemcpyAsync(d_win, win, (size_t) n_win * 4, hipMemcpyHostToDevice, s));
-        win = d_win;
-    }
-    volatile float * res = ctx->vad_res;                              // the kernel stores its three results straight into pinned host memory
-    if (ok) k::vad_window(win, n_win, n_last, alpha, freq_thold > 0.0f, vad_thold, ctx->vad_res, s);
-    ok = ok && HIP_OK(hipStreamSynchronize(s));
-    if (!ok) return -3;
-    if (energies) { energies[0] = res[1]; energies[1] = res[2]; }
-    return res[0] != 0.0f ? 1 : 0;
+    return vad_run(ctx, pcm + (n_samples - n_win), n_win, n_last, on_device, vad_alpha(freq_thold, WHISPER_SAMPLE_RATE), freq_thold > 0.0f,
+                   vad_thold, 1, -1, energies, nullptr);
+}
+
+int wmi_selftest_vad(struct whisper_context * ctx, const float * pcm, int n, int sample_rate, int last_ms, float vad_thold, float freq_thold,
+                     int form, int warm, float * energies, int32_t * stats2) {
+    if (!ctx || !ctx->state || ctx->host_only || !pcm || n <= 0 || n > (1 << 24) || sample_rate <= 0 || last_ms < 0 || form < 0 || form > 1 ||
+        warm > k::VAD_BLOCK) return -1;
+    if (stats2) { stats2[0] = 0; stats2[1] = 0; }
+    const long long n_last = (long long) sample_rate * last_ms / 1000;
+    if (n_last >= n) return 0;                                                                    // _vad_simple: "not enough samples"
+    CtxScope lk(ctx);
+    if (!HIP_OK(hipSetDevice(ctx->device))) return -2;
+    return vad_run(ctx, pcm, n, (int) n_last, 0, vad_alpha(freq_thold, sample_rate), freq_thold > 0.0f, vad_thold, form, warm, energies, stats2);
 }
 
 int wmi_pcm_to_mel_device(struct whisper_context * ctx, const float * d_samples, int n_samples) {

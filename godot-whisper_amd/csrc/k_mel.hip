@@ -695,6 +695,139 @@ __global__ __launch_bounds__(TS_W * 64) void k_ts_refine(const float * __restric
         out[blockIdx.x] = o;
     }
 }
+// ---------------------------------------------------------------- the energy VAD in blocks (the parallel form of k_vad, same bits)
+// The filter y_i = alpha * ((y_{i-1} + x_i) - y_{i-1}) depends on y_{i-1} through the ROUNDING of the inner add only, so chains started from
+// different states usually coincide after a few samples and are identical from then on.  k_vad_blocks cuts the window into blocks of
+// VAD_BLOCK samples, one lane each: block 0 starts as the reference does (y = x[0]); every other lane starts `warm` samples in front of its
+// block from y = 0, records the BITS of its state at the sample before the block (entry) and at the block's last sample (exit), and writes
+// its y values to scratch.  Nothing rests on the chains having merged: k_vad_finish compares entry[b] with exit[b - 1] as integers — block b
+// is right if block b - 1 is and the two words are equal — and where a pair disagrees it walks the blocks in order and runs block b again
+// from its predecessor's true exit state (one wavefront, the chain evaluated uniformly).  With warm = 0 practically every block is re-run
+// and the answer is still k_vad's.  Then the two energies: the reference's left-to-right f32 sums of |y|, by ts_trip_exact (integer
+// additions inside a binade, the plain loop across ties, binade crossings, NaN / Inf and the tail), one wavefront per sum.
+// One workgroup of k_vad_blocks stages 64 blocks (+ the block in front, for the warm-up) through LDS in rows of 65 words, so that the
+// lanes' strided reads and writes fall on different banks.
+constexpr int VB_ROW = VAD_BLOCK + 1;
+__device__ __forceinline__ float vad_step(float alpha, float y, float v) { return __fmul_rn(alpha, __fsub_rn(__fadd_rn(y, v), y)); }
+
+__global__ __launch_bounds__(64) void k_vad_blocks(const float * __restrict__ x, int n, float alpha, int warm, float * __restrict__ ys,
+                                                   uint32_t * __restrict__ entry, uint32_t * __restrict__ exit_) {
+    __shared__ float sx[65 * VB_ROW];                       // row r = samples t0 + 64 (r - 1) ..: row 0 is the block in front of the tile
+    __shared__ float sy[64 * VB_ROW];
+    const int lane = threadIdx.x;
+    const int t0 = blockIdx.x * (64 * VAD_BLOCK);
+    for (int k = lane; k < 65 * VAD_BLOCK; k += 64) {
+        const int s = t0 - VAD_BLOCK + k;
+        sx[(k >> 6) * VB_ROW + (k & 63)] = (s >= 0 && s < n) ? x[s] : 0.0f;
+    }
+    __syncthreads();
+    const int g = blockIdx.x * 64 + lane;                   // this lane's block of the window
+    const int i0 = t0 + lane * VAD_BLOCK;
+    if (i0 < n) {
+        const int cnt = min(VAD_BLOCK, n - i0);
+        const float * own = sx + (lane + 1) * VB_ROW, * prev = sx + lane * VB_ROW;
+        float * out = sy + lane * VB_ROW;
+        float y; int j0 = 0;
+        if (g == 0) { y = own[0]; out[0] = y; j0 = 1; }     // the filter starts from the first sample itself
+        else {
+            y = 0.0f;
+            for (int j = VAD_BLOCK - warm; j < VAD_BLOCK; ++j) y = vad_step(alpha, y, prev[j]);
+            entry[g] = __float_as_uint(y);
+        }
+        for (int j = j0; j < cnt; ++j) { y = vad_step(alpha, y, own[j]); out[j] = y; }
+        exit_[g] = __float_as_uint(y);
+    }
+    __syncthreads();
+    for (int k = lane; k < 64 * VAD_BLOCK; k += 64) {
+        const int s = t0 + k;
+        if (s < n) ys[s] = sy[(k >> 6) * VB_ROW + (k & 63)];
+    }
+}
+
+// sum_{i < n} |p[i]| as the loop `s = 0; for (i) s += fabsf(p[i])` in f32, by one wavefront
+__device__ __forceinline__ float vad_abs_sum(const float * __restrict__ p, int n, int lane) {
+    auto fetch = [&](float (&dst)[16], int base) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) { const int e = base + r * 64 + lane; dst[r] = e < n ? fabsf(p[e]) : 0.0f; }
+    };
+    float acc = 0.0f, x[16], nx[16];
+    if (n > 0) fetch(x, 0);
+    for (int i = 0; i < n; i += 1024) {
+        const bool more = i + 1024 < n;
+        if (more) fetch(nx, i + 1024);                       // in flight while this trip is added
+        acc = ts_trip_exact(acc, x, n - i, lane);
+        if (more) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) x[r] = nx[r];
+        }
+    }
+    return acc;
+}
+
+// n_blocks = 0: no filter ran, ys is the window itself.  res: see kernels.h vad_window_blocks
+__global__ __launch_bounds__(128) void k_vad_finish(const float * __restrict__ x, float * __restrict__ ys, int n, int n_last, float alpha,
+                                                    int n_blocks, const uint32_t * __restrict__ entry, const uint32_t * __restrict__ exit_,
+                                                    float vad_thold, float * __restrict__ res) {
+    __shared__ float s_last;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int bad = 0;
+    for (int b = 1 + tid; b < n_blocks; b += 128) bad |= entry[b] != exit_[b - 1];
+    int rerun = 0;
+    if (__syncthreads_or(bad)) {
+        if (wave == 0) {
+            uint32_t state = exit_[0];                      // block 0 has no guess in it
+            for (int b = 1; b < n_blocks; ++b) {
+                if (entry[b] == state) { state = exit_[b]; continue; }
+                const int i0 = b * VAD_BLOCK, cnt = min(VAD_BLOCK, n - i0);
+                const float xv = lane < cnt ? x[i0 + lane] : 0.0f;
+                float y = __uint_as_float(state), mine = 0.0f;
+                for (int j = 0; j < cnt; ++j) {              // every lane evaluates the same chain; lane j keeps sample j
+                    y = vad_step(alpha, y, __shfl(xv, j));
+                    if (lane == j) mine = y;
+                }
+                if (lane < cnt) ys[i0 + lane] = mine;
+                state = __float_as_uint(y);
+                rerun += 1;
+            }
+        }
+        __threadfence();
+        __syncthreads();                                    // wavefront 1 sums what wavefront 0 has just rewritten
+    }
+    float e = 0.0f;
+    if (wave == 0) e = vad_abs_sum(ys, n, lane);
+    else e = vad_abs_sum(ys + (n - n_last), n_last, lane);
+    if (tid == 64) s_last = e;
+    __syncthreads();
+    if (tid == 0) {
+        float e_all = e, e_last = s_last;
+        e_all /= (float) n;
+        if (n_last != 0) e_last /= (float) n_last;
+        const bool quiet = !(!(e_all < 0.0001f && e_last < 0.0001f) || e_last > vad_thold * e_all);
+        res[0] = quiet ? 1.0f : 0.0f; res[1] = e_all; res[2] = e_last;
+        ((int32_t *) res)[4] = n_blocks; ((int32_t *) res)[5] = rerun;
+    }
+}
+
+size_t vad_scratch_bytes(int n) {
+    const size_t nb = ((size_t) std::max(n, 0) + VAD_BLOCK - 1) / VAD_BLOCK;
+    return ((size_t) std::max(n, 0) + 2 * nb + 4) * 4;
+}
+void vad_window_blocks(const float * x, int n, int n_last, float alpha, bool filter, float vad_thold, int warm, void * scratch, float * res,
+                       hipStream_t st) {
+    if (n <= 0) return;
+    if (!filter) {                                          // no filter, only the sums over the window itself
+        hipLaunchKernelGGL(k_vad_finish, dim3(1), dim3(128), 0, st, x, const_cast<float *>(x), n, n_last, alpha, 0, nullptr, nullptr, vad_thold, res);
+        return;
+    }
+    if (warm < 0) warm = VAD_WARM_DEFAULT;
+    if (warm > VAD_BLOCK) warm = VAD_BLOCK;
+    const int nb = (n + VAD_BLOCK - 1) / VAD_BLOCK;
+    float * ys = (float *) scratch;
+    uint32_t * entry = (uint32_t *) (ys + n), * exit_ = entry + nb;
+    hipLaunchKernelGGL(k_vad_blocks, dim3((nb + 63) / 64), dim3(64), 0, st, x, n, alpha, warm, ys, entry, exit_);
+    hipLaunchKernelGGL(k_vad_finish, dim3(1), dim3(128), 0, st, x, ys, n, n_last, alpha, nb, entry, exit_, vad_thold, res);
+}
+
 void ts_refine(const float * en, const float * bmin, const float * bmax, int n_samples, const TsTok * in, TsOut * out, int n_tok, hipStream_t st) {
     if (n_tok > 0) hipLaunchKernelGGL(k_ts_refine, dim3(n_tok), dim3(TS_W * 64), 0, st, en, bmin, bmax, n_samples, in, out);
 }

@@ -46,7 +46,17 @@ struct ResampleArgs {
     int increment;
     unsigned long long m; int sh; double frac_scale;          // closed form: position n = (n * m) >> sh, fraction = low bits * 2^-sh
     const int * pos_tab; const double * frac_tab;             // or the host's recurrence
+    const float2 * in2;                                       // STEREO forms: the capture frames themselves (in is unused)
+    long long n0;                                             // the launch computes outputs [n0, n_out)
 };
+
+// input frame i: the mono sample, or the capture frame folded exactly as k_downmix folds it (a float add, then an exact halving) —
+// the same bits as a mono buffer written first, without writing one
+template <bool STEREO>
+__device__ __forceinline__ float in_frame(const ResampleArgs & a, long long i) {
+    if (STEREO) { const float2 f = a.in2[i]; return (float) ((double) (f.x + f.y) / 2.0); }
+    return a.in[i];
+}
 
 // where output n sits on the input: the host's table, or integer and fractional part of n * m * 2^-sh
 __device__ __forceinline__ void out_position(const ResampleArgs & a, long long n, long long * pos_out, double * frac_out) {
@@ -63,8 +73,9 @@ __device__ __forceinline__ void out_position(const ResampleArgs & a, long long n
     *pos_out = pos; *frac_out = frac;
 }
 
+template <bool STEREO>
 __global__ __launch_bounds__(256) void k_resample(const ResampleArgs a) {
-    const long long n = (long long) blockIdx.x * 256 + threadIdx.x;
+    const long long n = a.n0 + (long long) blockIdx.x * 256 + threadIdx.x;
     if (n >= a.n_out) return;
     long long pos; double frac;
     out_position(a, n, &pos, &frac);
@@ -73,7 +84,6 @@ __global__ __launch_bounds__(256) void k_resample(const ResampleArgs a) {
     const int max_index = a.half_len << 12;
     const long long last = a.n_in - 1;
     const float * __restrict__ c = a.coeffs;
-    const float * __restrict__ x = a.in;
 
     // left half: taps from the far end towards the centre sample, src_sinc.c:293-314
     int fi = start_index;
@@ -87,7 +97,7 @@ __global__ __launch_bounds__(256) void k_resample(const ResampleArgs a) {
         const float c0 = c[ix], c1 = c[ix + 1];
         const double ic = (double) c0 + fraction * (double) (c1 - c0);
         const long long dc = di < 0 ? 0 : (di > last ? last : di);
-        float v = x[dc];
+        float v = in_frame<STEREO>(a, dc);
         v = (di < 0 || di > last) ? 0.0f : v;                 // zero history before the first sample, zero tail after the last
         left += ic * (double) v;
         fi -= increment;
@@ -106,7 +116,7 @@ __global__ __launch_bounds__(256) void k_resample(const ResampleArgs a) {
         const float c0 = c[ix], c1 = c[ix + 1];
         const double ic = (double) c0 + fraction * (double) (c1 - c0);
         const long long dc = di > last ? last : di;
-        float v = x[dc];
+        float v = in_frame<STEREO>(a, dc);
         v = di > last ? 0.0f : v;
         right += ic * (double) v;
         fi -= increment;
@@ -118,18 +128,18 @@ __global__ __launch_bounds__(256) void k_resample(const ResampleArgs a) {
 
 // SRC_ZERO_ORDER_HOLD (LINEAR = false, src_zoh.c:80, :99) and SRC_LINEAR (src_linear.c:82-83, :107-108).  The plan emits output n only
 // while pos_n - 1 (and pos_n for LINEAR) are frames of the input; the clamp keeps a wrong plan from reading outside it.
-template <bool LINEAR>
+template <bool LINEAR, bool STEREO>
 __global__ __launch_bounds__(256) void k_resample_simple(const ResampleArgs a) {
-    const long long n = (long long) blockIdx.x * 256 + threadIdx.x;
+    const long long n = a.n0 + (long long) blockIdx.x * 256 + threadIdx.x;
     if (n >= a.n_out) return;
     long long pos; double frac;
     out_position(a, n, &pos, &frac);
     const long long last = a.n_in - 1;
     const long long i0 = pos <= 0 ? 0 : (pos - 1 > last ? last : pos - 1);     // pos 0: last_value = in[0]
-    const float v0 = a.in[i0];
+    const float v0 = in_frame<STEREO>(a, i0);
     if (!LINEAR) { a.out[n] = v0; return; }
     const long long i1 = pos <= 0 ? 0 : (pos > last ? last : pos);
-    const float d = a.in[i1] - v0;                                               // float difference, then double multiply and add
+    const float d = in_frame<STEREO>(a, i1) - v0;                                               // float difference, then double multiply and add
     a.out[n] = (float) ((double) v0 + frac * (double) d);
 }
 
@@ -325,19 +335,53 @@ void resample_positions(const ResamplePlan & pl, long long n, long long * pos, d
     for (long long i = 0; i < n; ++i) pl.stepper->at(i, pos + i, frac + i);
 }
 
-void resample_launch(const ResamplePlan & pl, const float * d_in, long long n_in, float * d_out, const float * d_coeffs,
-                     const int * d_pos, const double * d_frac, hipStream_t st) {
-    if (pl.n_out <= 0) return;
+static void launch(const ResamplePlan & pl, const float * d_in, const float * d_frames_xy, long long n_in, float * d_out, const float * d_coeffs,
+                   const int * d_pos, const double * d_frac, long long first, hipStream_t st) {
+    if (first < 0) first = 0;
+    if (pl.n_out <= first) return;
     ResampleArgs a;
-    a.in = d_in; a.n_in = n_in; a.out = d_out; a.n_out = pl.n_out;
+    a.in = d_in; a.in2 = (const float2 *) d_frames_xy; a.n_in = n_in; a.out = d_out; a.n_out = pl.n_out; a.n0 = first;
     a.coeffs = d_coeffs; a.half_len = pl.half_len;
     a.float_inc = pl.float_inc; a.out_scale = pl.out_scale; a.increment = pl.increment;
     a.m = pl.stepper->m; a.sh = pl.stepper->sh; a.frac_scale = ldexp(1.0, -pl.stepper->sh);
     a.pos_tab = pl.need_table ? d_pos : nullptr; a.frac_tab = pl.need_table ? d_frac : nullptr;
-    const dim3 grid((unsigned) ((pl.n_out + 255) / 256));
-    if (pl.converter == 3) hipLaunchKernelGGL(k_resample_simple<false>, grid, dim3(256), 0, st, a);
-    else if (pl.converter == 4) hipLaunchKernelGGL(k_resample_simple<true>, grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(k_resample, grid, dim3(256), 0, st, a);
+    const dim3 grid((unsigned) ((pl.n_out - first + 255) / 256));
+    const bool stereo = d_frames_xy != nullptr;
+    if (pl.converter == 3) {
+        if (stereo) hipLaunchKernelGGL((k_resample_simple<false, true>), grid, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((k_resample_simple<false, false>), grid, dim3(256), 0, st, a);
+    } else if (pl.converter == 4) {
+        if (stereo) hipLaunchKernelGGL((k_resample_simple<true, true>), grid, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((k_resample_simple<true, false>), grid, dim3(256), 0, st, a);
+    } else {
+        if (stereo) hipLaunchKernelGGL((k_resample<true>), grid, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((k_resample<false>), grid, dim3(256), 0, st, a);
+    }
+}
+
+void resample_launch(const ResamplePlan & pl, const float * d_in, long long n_in, float * d_out, const float * d_coeffs,
+                     const int * d_pos, const double * d_frac, hipStream_t st) {
+    launch(pl, d_in, nullptr, n_in, d_out, d_coeffs, d_pos, d_frac, 0, st);
+}
+
+void resample_launch_stereo(const ResamplePlan & pl, const float * d_frames_xy, long long n_in, float * d_out, const float * d_coeffs,
+                            const int * d_pos, const double * d_frac, long long first, hipStream_t st) {
+    launch(pl, nullptr, d_frames_xy, n_in, d_out, d_coeffs, d_pos, d_frac, first, st);
+}
+
+// Output k of a plan does not depend on the input length as long as every frame it reads exists: its position comes from k alone and the
+// input is zero-extended, so only a tap past the last frame can change when frames are appended.  The furthest frame output k reads is
+// pos_k + 1 + cnt for the SINC converters (the right half starts cnt = (max_index - (increment - start_index)) / increment taps out, bounded
+// by max_index / increment + 1) and pos_k for ZOH / LINEAR.  first_dirty = the first output whose reach is not inside the old input, or that
+// the old plan had not emitted; a bound, not the exact index (recomputing an unchanged output writes the same bits again).
+long long resample_first_dirty(const ResamplePlan & old_pl, long long n_old, const ResamplePlan & new_pl) {
+    if (old_pl.error || new_pl.error || !old_pl.stepper || !new_pl.stepper || old_pl.need_table || new_pl.need_table ||
+        old_pl.converter != new_pl.converter || old_pl.n_out <= 0) return 0;
+    const long long reach = old_pl.converter <= 2 ? ((long long) old_pl.half_len << 12) / std::max(old_pl.increment, 1) + 3 : 1;
+    const long long limit = n_old - reach;                                       // outputs with pos_k < limit read existing frames only
+    if (limit <= 0) return 0;
+    const long long k = new_pl.stepper->first_at_or_past(limit, 0, old_pl.n_out);
+    return std::min(std::min(k, old_pl.n_out), new_pl.n_out);
 }
 
 }}  // namespace wmi::k

@@ -125,6 +125,13 @@ void ts_refine(const float * en, const float * bmin, const float * bmax, int n_s
 // (src/speech_to_text.cpp:45-51, 53-104).  res = {no-activity decision, energy_all, energy_last}
 void downmix_stereo(const float * frames, int n_frames, float * out, hipStream_t st);
 void vad_window(const float * x, int n, int n_last, float alpha, bool filter, float vad_thold, float * res, hipStream_t st);
+// The same answer bit for bit with the filter cut into blocks of VAD_BLOCK samples, one lane each (k_mel.hip: k_vad_blocks, k_vad_finish).
+// warm: samples a block's lane runs ahead of its block (0 .. VAD_BLOCK; < 0: VAD_WARM_DEFAULT).  scratch: vad_scratch_bytes(n) of device
+// memory.  res: 8 words — {decision, energy_all, energy_last} as floats, then {blocks, blocks re-run} as int32 at res[4], res[5].
+constexpr int VAD_BLOCK = 64, VAD_WARM_DEFAULT = 32;
+size_t vad_scratch_bytes(int n);
+void vad_window_blocks(const float * x, int n, int n_last, float alpha, bool filter, float vad_thold, int warm, void * scratch, float * res,
+                       hipStream_t st);
 
 // Resampler (k_resample.hip): src_simple(SRC_SINC_FASTEST = 2 | SRC_SINC_MEDIUM_QUALITY = 1 | SRC_ZERO_ORDER_HOLD = 3 | SRC_LINEAR = 4,
 // one channel) of libsamplerate as the host calls it (src/speech_to_text.cpp:16-43), bit-identical to the sequential CPU code.  resample_plan replays the converter's index
@@ -147,6 +154,12 @@ void resample_table(const ResamplePlan & pl, const int ** pos, const double ** f
 void resample_positions(const ResamplePlan & pl, long long n, long long * pos, double * frac);   // first n positions (tests)
 void resample_launch(const ResamplePlan & pl, const float * d_in, long long n_in, float * d_out, const float * d_coeffs,
                      const int * d_pos, const double * d_frac, hipStream_t st);
+// The capture session's form (capture.cpp): the input is the interleaved stereo capture frames, folded per tap as downmix_stereo folds them
+// (no mono buffer), and only outputs [first, pl.n_out) are computed.  resample_first_dirty: the outputs below it are the same in both plans
+// (n_old = the frames old_pl was made for); 0 = recompute everything (table positions, an error in either plan).
+void resample_launch_stereo(const ResamplePlan & pl, const float * d_frames_xy, long long n_in, float * d_out, const float * d_coeffs,
+                            const int * d_pos, const double * d_frac, long long first, hipStream_t st);
+long long resample_first_dirty(const ResamplePlan & old_pl, long long n_old, const ResamplePlan & new_pl);
 
 // ---------------------------------------------------------------- GEMM (k_gemm.hip)
 enum Epi : int {

@@ -215,6 +215,64 @@ def vad_simple(pcm: np.ndarray, sample_rate: int, last_ms: int, vad_thold: float
     return True
 
 
+class CaptureSession:
+    """include/wmi_device.h wmi_capture_*: the accumulated capture frames of one node and their 16 kHz PCM, resident on the device."""
+
+    def __init__(self, node: SpeechToText, mix_rate: int, converter: int = 2, frames_hint: int = 0):
+        self.lib, self.node = node.lib, node
+        self.cap = self.lib.wmi_capture_init(node.ctx, int(mix_rate), int(converter), int(frames_hint))
+        if not self.cap:
+            raise RuntimeError("wmi_capture_init failed (context cannot compute, or bad mix rate / converter)")
+
+    def close(self):
+        if self.cap:
+            self.lib.wmi_capture_free(self.cap)
+        self.cap = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def push(self, frames_xy: np.ndarray) -> int:
+        xy = np.ascontiguousarray(frames_xy, dtype=np.float32).reshape(-1, 2)
+        r = self.lib.wmi_capture_push(self.cap, xy.ctypes.data_as(C.c_void_p), int(xy.shape[0]), 0)
+        assert r >= 0, r
+        return r
+
+    def push_device(self, d_ptr, n_frames: int) -> int:
+        return self.lib.wmi_capture_push(self.cap, C.c_void_p(d_ptr), int(n_frames), 1)
+
+    def keep_last(self, n_frames: int) -> int:
+        return self.lib.wmi_capture_keep_last(self.cap, int(n_frames))
+
+    def resample(self):
+        """-> (result_size, expected), src/speech_to_text.cpp:356-370"""
+        exp = C.c_int(0)
+        return self.lib.wmi_capture_resample(self.cap, C.byref(exp)), exp.value
+
+    def read_pcm(self) -> np.ndarray:
+        n, _ = self.resample()
+        out = np.empty(max(n, 1), np.float32)
+        got = self.lib.wmi_capture_read_pcm(self.cap, out.ctypes.data_as(C.c_void_p), int(out.size))
+        assert got == max(n, 0), (got, n)
+        return out[:max(got, 0)].copy()
+
+    def vad(self, vad_thold: float, freq_thold: float, energies: np.ndarray | None = None) -> int:
+        return self.lib.wmi_capture_vad(self.cap, float(vad_thold), float(freq_thold),
+                                        energies.ctypes.data_as(C.c_void_p) if energies is not None else None)
+
+    def full(self, params) -> int:
+        return self.lib.wmi_capture_full(self.cap, params)
+
+    def stats(self) -> tuple:
+        """(bytes copied host -> device, outputs computed, outputs reused, 1 if everything was recomputed)"""
+        out = (C.c_int64 * 4)()
+        assert self.lib.wmi_capture_stats(self.cap, out) == 0
+        return tuple(int(v) for v in out)
+
+
 class AudioStreamToText(SpeechToText):
     """addon/audio_stream_to_text.gd: one-shot "transcribe this WAV" node."""
 
@@ -240,10 +298,11 @@ def remove_special_characters(message: str) -> str:
 
 
 class CaptureStreamToText(SpeechToText):
-    """addon/capture_stream_to_text.gd: the streaming loop, restated over a pre-recorded 16 kHz
-    buffer instead of AudioEffectCapture (resampling stays with libsamplerate in the host and is
-    out of scope).  Every `interval` seconds of simulated time the whole accumulated buffer is
-    re-transcribed with audio_ctx = total_s*50 + 128 (:84)."""
+    """addon/capture_stream_to_text.gd: the streaming loop.  `stream` restates it over a pre-recorded 16 kHz buffer instead of
+    AudioEffectCapture: every `interval` seconds of simulated time the whole accumulated buffer is re-transcribed with
+    audio_ctx = total_s*50 + 128 (:84).  `stream_capture` is the node's own loop over stereo capture frames at the mix rate —
+    append, resample, VAD, transcribe (:69-120) — on a capture session (include/wmi_device.h wmi_capture_*: the frames and their
+    16 kHz PCM stay on the device) or, for comparison, over resample() / voice_activity_detection() / transcribe() on host arrays."""
 
     def __init__(self, lib, settings=None, transcribe_interval: float = 0.3, minimum_sentence_ms: int = 3000,
                  maximum_sentence_ms: int = 15000, punctuation_characters: str = ".!?;。；？！"):
@@ -289,3 +348,68 @@ class CaptureStreamToText(SpeechToText):
                 last_tokens = -1
             if max_calls is not None and calls >= max_calls:
                 return
+
+    def stream_capture(self, frames_xy: np.ndarray, mix_rate: int, interpolator_type: int = 2, max_calls: int | None = None,
+                       use_session: bool = True, minimum_sentence_time: float = 3, maximum_sentence_time: float = 15,
+                       hallucinating_count: int = 1):
+        """transcribe_thread (addon/capture_stream_to_text.gd:69-120) over pre-recorded stereo capture frames at `mix_rate`: every pass
+        appends `interval` seconds of frames, resamples the whole accumulation, runs the VAD and transcribes with the node's
+        parameters and audio_ctx = total_time * 1500 / 30 + 128.  Yields, per transcribe call,
+        (finish_sentence, text, n_samples_used, audio_ctx, token dicts, no_activity); as in the node, a pass with no_activity neither
+        ends the sentence nor updates the token count, and a finished sentence keeps the last 0.2 * mix_rate frames.
+        use_session: the capture session (device-resident frames and PCM), else the same loop over resample() /
+        voice_activity_detection() / transcribe() on host arrays — the same tuples either way."""
+        xy = np.ascontiguousarray(frames_xy, dtype=np.float32).reshape(-1, 2)
+        sr = abi.WHISPER_SAMPLE_RATE
+        step = max(int(round(self.interval * mix_rate)), 1)
+        vad_thold = float(self.settings["audio/input/transcribe/vad_treshold"])
+        freq_thold = float(self.settings["audio/input/transcribe/freq_treshold"])
+        sess = CaptureSession(self, mix_rate, interpolator_type, frames_hint=int(maximum_sentence_time * mix_rate)) if use_session else None
+        try:
+            start, pos, calls, last_token_count = 0, 0, 0, 0
+            while pos < xy.shape[0]:
+                new = xy[pos:pos + step]
+                pos += new.shape[0]
+                if sess:
+                    sess.push(new)                                                  # _accumulated_frames.append_array(...) (:73)
+                    size, _ = sess.resample()
+                else:
+                    resampled = self.resample(xy[start:pos], interpolator_type, mix_rate)
+                    size = int(resampled.size)
+                if size <= 0:
+                    continue
+                if sess:
+                    no_activity = bool(sess.vad(vad_thold, freq_thold))
+                else:
+                    no_activity = self.voice_activity_detection(resampled)
+                total_time = size / sr
+                audio_ctx = min(int(total_time * 1500 / 30 + 128), 1500)            # :84
+                if sess:
+                    self.last_ret = sess.full(self.full_params("", audio_ctx))
+                    tokens = self.collect() if self.last_ret == 0 else []
+                else:
+                    tokens = self.transcribe(resampled, "", audio_ctx)
+                calls += 1
+                if not tokens:
+                    return                                                          # push_warning("No tokens generated") (:88-90)
+                full_text = tokens.pop(0).decode("utf-8", errors="replace")
+                finish = total_time > maximum_sentence_time
+                text = remove_special_characters("".join(t["text"].decode("utf-8", errors="replace") for t in tokens))
+                if any(ch in text for ch in self.punct) or no_activity:
+                    finish = True
+                if total_time < minimum_sentence_time or abs(len(tokens) - last_token_count) > hallucinating_count:
+                    finish = False
+                yield finish, full_text, size, audio_ctx, list(tokens), no_activity
+                if not no_activity:                                                 # `if no_activity: continue` (:108-109)
+                    if finish:                                                      # :110-113
+                        keep = int(0.2 * mix_rate)
+                        if sess:
+                            sess.keep_last(keep)
+                        else:
+                            start = max(pos - keep, start)
+                    last_token_count = len(tokens)
+                if max_calls is not None and calls >= max_calls:
+                    return
+        finally:
+            if sess:
+                sess.close()

@@ -2,6 +2,8 @@
 //   wmi_host_demo <model.ggml> <pcm.f32> <mode> [language] [initial_prompt] [audio_ctx]
 // mode: transcribe | vad | stream | batch (pcm file = several buffers, see below) | resample (pcm file = interleaved stereo frames;
 //       language = mix rate, prompt = interpolator type: prints the frame count, an FNV-1a hash of the frames' bits and the error string)
+//       | capture (pcm file = interleaved stereo frames; language = mix rate, prompt = "session" or "calls", audio_ctx = the largest number of
+//       transcribe calls: the node's own loop, CaptureStreamToText::stream_capture)
 // Prints one JSON document on stdout.  pcm.f32: raw little-endian float32 mono 16 kHz; for `batch` the file starts with
 // int32 n, then n x int32 lengths, then the buffers back to back.
 #include "speech_to_text.h"
@@ -63,6 +65,23 @@ int main(int argc, char ** argv) {
         printf("[");
         for (size_t i = 0; i < ups.size(); ++i) {
             printf("%s{\"finish\": %s, \"n_samples\": %zu, \"audio_ctx\": %d, \"text\": ", i ? ", " : "", ups[i].finish ? "true" : "false", ups[i].n_samples, ups[i].audio_ctx);
+            json_string(ups[i].text);
+            printf(", \"ids\": [");
+            for (size_t j = 0; j < ups[i].tokens.size(); ++j) printf("%s%d", j ? ", " : "", ups[i].tokens[j].id);
+            printf("]}");
+        }
+        printf("]\n");
+        return 0;
+    }
+    if (mode == "capture") {
+        std::vector<float> xy((const float *) raw.data(), (const float *) raw.data() + raw.size() / 4);
+        CaptureStreamToText node;
+        node.set_language_model(model.data(), model.size());
+        const auto ups = node.stream_capture(xy, language, SpeechToText::SRC_SINC_FASTEST, audio_ctx > 0 ? audio_ctx : -1, prompt != "calls");
+        printf("[");
+        for (size_t i = 0; i < ups.size(); ++i) {
+            printf("%s{\"finish\": %s, \"no_activity\": %s, \"n_samples\": %zu, \"audio_ctx\": %d, \"text\": ", i ? ", " : "", ups[i].finish ? "true" : "false",
+                   ups[i].no_activity ? "true" : "false", ups[i].n_samples, ups[i].audio_ctx);
             json_string(ups[i].text);
             printf(", \"ids\": [");
             for (size_t j = 0; j < ups[i].tokens.size(); ++j) printf("%s%d", j ? ", " : "", ups[i].tokens[j].id);

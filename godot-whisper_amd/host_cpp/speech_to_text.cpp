@@ -233,4 +233,72 @@ std::vector<CaptureStreamToText::Update> CaptureStreamToText::stream(const std::
     return out;
 }
 
+static bool contains_any_codepoint(const std::string & text, const std::string & set) {     // _has_terminating_characters (:124-128)
+    for (size_t k = 0; k < set.size();) {
+        size_t n = 1;
+        const unsigned char c = (unsigned char) set[k];
+        if (c >= 0xF0) n = 4; else if (c >= 0xE0) n = 3; else if (c >= 0xC0) n = 2;
+        if (text.find(set.substr(k, n)) != std::string::npos) return true;
+        k += n;
+    }
+    return false;
+}
+
+std::vector<CaptureStreamToText::Update> CaptureStreamToText::stream_capture(const std::vector<float> & interleaved_xy, int mix_rate,
+                                                                             InterpolatorType interpolator_type, int max_calls, bool use_session) {
+    std::vector<Update> out;
+    if (!context_instance || mix_rate <= 0) return out;
+    const int sr = WHISPER_SAMPLE_RATE;
+    const size_t n_frames = interleaved_xy.size() / 2;
+    const size_t step = std::max<size_t>((size_t) std::lround(transcribe_interval * mix_rate), 1);
+    wmi_capture * cap = use_session ? wmi_capture_init(context_instance, mix_rate, (int) interpolator_type, (int) (maximum_sentence_ms / 1000.0 * mix_rate)) : nullptr;
+    if (use_session && !cap) { fprintf(stderr, "ERROR: wmi_capture_init failed\n"); return out; }
+    size_t start = 0, pos = 0; int calls = 0, last_token_count = 0;
+    std::vector<float> resampled;
+    while (pos < n_frames) {
+        const size_t take = std::min(step, n_frames - pos);
+        int size = 0;
+        if (cap) {
+            if (wmi_capture_push(cap, interleaved_xy.data() + 2 * pos, (int) take, 0) < 0) break;      // _accumulated_frames.append_array(...) (:73)
+            pos += take;
+            size = wmi_capture_resample(cap, nullptr);
+        } else {
+            pos += take;
+            resampled = resample(std::vector<float>(interleaved_xy.begin() + 2 * start, interleaved_xy.begin() + 2 * pos), interpolator_type, mix_rate);
+            size = (int) resampled.size();
+        }
+        if (size <= 0) continue;
+        const bool no_activity = cap ? wmi_capture_vad(cap, settings.vad_treshold, settings.freq_treshold, nullptr) > 0 : voice_activity_detection(resampled);
+        const double total_time = (double) size / sr;
+        const int audio_ctx = std::min((int) (total_time * 1500 / 30 + 128), 1500);                    // :84
+        Transcription t;
+        if (cap) {
+            const std::string prompt;
+            last_return = wmi_capture_full(cap, make_params(prompt, audio_ctx));
+            if (last_return == 0) t = collect();
+            else fprintf(stderr, "ERROR: Failed to process audio, returned %d\n", last_return);
+        } else t = transcribe(resampled, "", audio_ctx);
+        ++calls;
+        if (!t.ok) break;                                                                              // "No tokens generated" (:88-90)
+        bool finish = total_time * 1000 > maximum_sentence_ms;
+        std::string text;
+        for (const Token & tok : t.tokens) text += tok.text;
+        text = remove_special_characters(text);
+        if (contains_any_codepoint(text, punctuation_characters) || no_activity) finish = true;
+        if (total_time * 1000 < minimum_sentence_ms || std::abs((int) t.tokens.size() - last_token_count) > hallucinating_count) finish = false;
+        out.push_back(Update{finish, t.full_text, (size_t) size, audio_ctx, t.tokens, no_activity});
+        if (!no_activity) {                                                                            // `if no_activity: continue` (:108-109)
+            if (finish) {                                                                              // :110-113
+                const size_t keep = (size_t) (0.2 * mix_rate);
+                if (cap) wmi_capture_keep_last(cap, (int) keep);
+                else start = std::max(start, pos > keep ? pos - keep : 0);
+            }
+            last_token_count = (int) t.tokens.size();
+        }
+        if (max_calls >= 0 && calls >= max_calls) break;
+    }
+    wmi_capture_free(cap);
+    return out;
+}
+
 } // namespace godot_whisper

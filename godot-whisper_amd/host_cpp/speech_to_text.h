@@ -92,15 +92,24 @@ public:
 };
 std::string remove_special_characters(std::string message);          // addon/audio_stream_to_text.gd:64-88
 
-// addon/capture_stream_to_text.gd: the streaming loop over a pre-recorded 16 kHz buffer (capture frames go through resample() first)
+// addon/capture_stream_to_text.gd: the streaming loop — stream() over a pre-recorded 16 kHz buffer, stream_capture() the node's own loop
+// over stereo capture frames at the mix rate
 class CaptureStreamToText : public SpeechToText {
 public:
     using SpeechToText::SpeechToText;
     float transcribe_interval = 0.3f;
     int   minimum_sentence_ms = 3000, maximum_sentence_ms = 15000;
+    int   hallucinating_count = 1;
     std::string punctuation_characters = ".!?;\xe3\x80\x82\xef\xbc\x9b\xef\xbc\x9f\xef\xbc\x81";
-    struct Update { bool finish; std::string text; size_t n_samples; int audio_ctx; std::vector<Token> tokens; };
+    struct Update { bool finish; std::string text; size_t n_samples; int audio_ctx; std::vector<Token> tokens; bool no_activity = false; };
     std::vector<Update> stream(const std::vector<float> & pcm16k, int max_calls = -1);
+    // transcribe_thread (addon/capture_stream_to_text.gd:69-120) over pre-recorded capture frames: every pass appends transcribe_interval
+    // seconds of frames, resamples the whole accumulation, runs the VAD and transcribes with audio_ctx = total_time * 1500 / 30 + 128; a
+    // pass with no_activity neither ends the sentence nor updates the token count, a finished sentence keeps the last 0.2 * mix_rate frames.
+    // use_session: on a capture session (include/wmi_device.h wmi_capture_*: frames and PCM stay on the device), else the same loop over
+    // resample() / voice_activity_detection() / transcribe() on host vectors — the same updates either way.
+    std::vector<Update> stream_capture(const std::vector<float> & interleaved_xy, int mix_rate, InterpolatorType interpolator_type = SRC_SINC_FASTEST,
+                                       int max_calls = -1, bool use_session = true);
 };
 
 // src/speech_to_text.cpp:53-104

@@ -70,6 +70,20 @@ DEVICE_API = [
     ("wmi_selftest_resample_plan", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                              C.c_void_p]),
     ("wmi_resample", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]),
+    ("wmi_capture_init", C.c_void_p, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    ("wmi_capture_free", None, [C.c_void_p]),
+    ("wmi_capture_push", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+    ("wmi_capture_keep_last", C.c_int, [C.c_void_p, C.c_int]),
+    ("wmi_capture_resample", C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    ("wmi_capture_pcm", C.c_void_p, [C.c_void_p, C.POINTER(C.c_int)]),
+    ("wmi_capture_read_pcm", C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    ("wmi_capture_vad", C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_void_p]),
+    ("wmi_capture_full", C.c_int, [C.c_void_p, abi.whisper_full_params]),
+    ("wmi_capture_stats", C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    ("wmi_selftest_capture_plan", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong),
+                                            C.POINTER(C.c_longlong)]),
+    ("wmi_selftest_vad", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.c_void_p,
+                                   C.c_void_p]),
     ("wmi_model_header", C.c_size_t, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
     ("wmi_arena_ptr", C.c_void_p, [C.c_void_p]),
     ("wmi_init_from_header", C.c_void_p, [C.c_void_p, C.c_size_t, C.c_int]),

@@ -67,8 +67,8 @@ WHISPER_API size_t wmi_weights_bytes(struct whisper_context * ctx, int which);
 WHISPER_API int wmi_pcm_to_mel_device(struct whisper_context * ctx, const float * d_samples, int n_samples);
 
 /* whisper_full over device-resident PCM: identical control flow and results, minus the H2D copy.
- * `h_samples_for_timestamps` may be NULL unless params.token_timestamps is set (the timestamp
- * heuristics read the waveform on the host, W/whisper.cpp:5003-5010). */
+ * `h_samples_for_timestamps` may always be NULL: the |x| envelope of the token timestamps (W/whisper.cpp:5003-5010) is computed on the
+ * device from the samples the log-mel stage has just staged, the host pointer is never read (kept for source compatibility). */
 WHISPER_API int wmi_full_device_pcm(struct whisper_context * ctx, struct whisper_full_params params,
                                     const float * d_samples, int n_samples, const float * h_samples_for_timestamps);
 
@@ -97,7 +97,8 @@ WHISPER_API int64_t wmi_pool_device_time_us(struct wmi_pool * pool, int i);
  *                        replaces: _vector2_array_to_float_array, src/speech_to_text.cpp:45-51
  *   wmi_vad              SpeechToText::voice_activity_detection (src/speech_to_text.cpp:53-104, 378-399) on the last 3 s of
  *                        `pcm` (16 kHz mono): 1 = no voice activity in the last 500 ms, 0 = activity or fewer than 3 s of audio.
- *                        energies (optional, 2 floats) receives energy_all, energy_last.
+ *                        energies (optional, 2 floats) receives energy_all, energy_last.  The filter runs in blocks of 64 samples
+ *                        side by side with a bitwise hand-over check between neighbours (wmi_selftest_vad): the sequential code's bits.
  * `on_device` != 0: the input (and `mono_out`) are device pointers on the context's device, else host pointers. */
 WHISPER_API int wmi_downmix_stereo(struct whisper_context * ctx, const float * frames, int n_frames, int on_device, float * mono_out);
 
@@ -120,6 +121,54 @@ WHISPER_API int wmi_resample(struct whisper_context * ctx, const float * src, in
                              int on_device, float * dst, int dst_capacity);
 WHISPER_API int wmi_vad(struct whisper_context * ctx, const float * pcm, int n_samples, int on_device, float vad_thold, float freq_thold,
                         float * energies);
+
+/* Capture session: the streaming node's step (bin/addons/godot_whisper/capture_stream_to_text.gd:69-120 — append the new capture frames,
+ * resample the whole accumulation, VAD, transcribe) on frames that STAY in HBM.  The accumulated stereo frames and their 16 kHz PCM live
+ * on the context's device for the life of the session and grow geometrically (frames_hint sizes the first allocation, there is no cap); a
+ * push uploads the new frames only, through a pinned staging buffer of the session; the resampler reads the stereo frames directly,
+ * folding each tap's frame as wmi_downmix_stereo does, and computes only the outputs a push can have changed.  Every value is what the
+ * one-shot calls give on the whole accumulation, bit for bit.  Everything is queued on the state's stream; a call waits only where it
+ * returns device results to the host (wmi_capture_vad once, wmi_capture_read_pcm, wmi_capture_full as whisper_full; a push of DEVICE frames
+ * waits for its copy so that the caller's buffer is free on return).  The calls take the context's lock; free the session before its context.
+ *   wmi_capture_init      NULL: bad arguments, a host-only / weights-pending context, converter 0 (no table) or outside 1 - 4
+ *   wmi_capture_push      append [n_frames][2] f32 frames (host pointer, or device pointer with on_device != 0); returns the frames held,
+ *                         < 0 on error (-1 arguments, -2 / -3 device); n_frames = 0 is a no-op
+ *   wmi_capture_keep_last the node's `_accumulated_frames.slice(size - 0.2 * mix_rate)` (:111): keep the last n_frames; returns the frames held
+ *   wmi_capture_resample  bring the PCM up to date.  Returns result_size exactly as wmi_downmix_stereo + wmi_resample on the whole
+ *                         accumulation would (0 where src_simple errors; the frame count at equal rates, where only the fold runs);
+ *                         *expected = frames * 16000 / mix_rate (src/speech_to_text.cpp:356).  Does not wait: the count comes from the
+ *                         host-side plan.  The calls below bring the PCM up to date themselves when frames were pushed since.
+ *   wmi_capture_pcm       device pointer to the PCM and its length (NULL, 0 when empty); valid until the next push / keep_last / free
+ *   wmi_capture_read_pcm  copy of the PCM to the host; returns the samples written, -4 when capacity is too small
+ *   wmi_capture_vad       wmi_vad's answer on the session's PCM; 0, without device work, with fewer than 3 s
+ *   wmi_capture_full      whisper_full on the session's PCM; results through the whisper_full_* accessors of the context
+ *   wmi_capture_stats     of the pushes since the previous resample and the last resample: out4 = { bytes copied host -> device, outputs
+ *                         computed, outputs reused, 1 if everything was recomputed }.  Everything is recomputed on the first resample,
+ *                         after keep_last dropped frames, after a converter error, and at rates whose positions come from the host's
+ *                         table (closed_form = 0 of wmi_selftest_resample_plan, e.g. 22.05 kHz; the table is uploaded and counted too). */
+struct wmi_capture;
+WHISPER_API struct wmi_capture * wmi_capture_init(struct whisper_context * ctx, int mix_rate, int converter, int frames_hint);
+WHISPER_API void          wmi_capture_free(struct wmi_capture * cap);
+WHISPER_API int           wmi_capture_push(struct wmi_capture * cap, const float * frames_xy, int n_frames, int on_device);
+WHISPER_API int           wmi_capture_keep_last(struct wmi_capture * cap, int n_frames);
+WHISPER_API int           wmi_capture_resample(struct wmi_capture * cap, int * expected);
+WHISPER_API const float * wmi_capture_pcm(struct wmi_capture * cap, int * n_samples);
+WHISPER_API int           wmi_capture_read_pcm(struct wmi_capture * cap, float * dst, int capacity);
+WHISPER_API int           wmi_capture_vad(struct wmi_capture * cap, float vad_thold, float freq_thold, float * energies);
+WHISPER_API int           wmi_capture_full(struct wmi_capture * cap, struct whisper_full_params params);
+WHISPER_API int           wmi_capture_stats(struct wmi_capture * cap, int64_t * out4);
+/* Host half of the session's incremental resample (no device needed): for an accumulation that grew from n_old to n_new frames at
+ * src_rate -> 16 kHz, the first output the session recomputes (outputs below it are the same bytes for both inputs; 0 = everything, e.g.
+ * at rates without a closed form) and the frame counts of both plans.  Returns 0, -1 bad arguments, or the converter error of the new plan. */
+WHISPER_API int wmi_selftest_capture_plan(int n_old, int n_new, int src_rate, int converter, long long * first_dirty,
+                                          long long * n_out_old, long long * n_out_new);
+/* Test hook for the two forms of the energy VAD on a host window of n samples (_vad_simple, src/speech_to_text.cpp:68-104, with the
+ * host's high-pass filter): form 0 = the sequential kernel (one lane, sample order: the definition), form 1 = the filter in blocks of 64
+ * samples, a lane each, started `warm` samples early (0 .. 64; < 0: the default, 32) with the bitwise hand-over check and re-run, which is
+ * what wmi_vad and the session run.  Same decision and energy bits.  stats2 (optional) = { blocks, blocks re-run } (0 0 for form 0).
+ * Returns the decision; 0 without device work when sample_rate * last_ms / 1000 >= n; -1 arguments, -2 / -3 device. */
+WHISPER_API int wmi_selftest_vad(struct whisper_context * ctx, const float * pcm, int n, int sample_rate, int last_ms, float vad_thold,
+                                 float freq_thold, int form, int warm, float * energies, int32_t * stats2);
 
 /* Several independent chunks on one GPU in lock-step (BASELINE config 4: 8 chunks per GPU).  Every chunk is
  * transcribed as by whisper_full(ctx, params, pcm[c], n_samples[c]) on a freshly initialised context
