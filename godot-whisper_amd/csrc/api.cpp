@@ -725,7 +725,7 @@ int wmi_get_tensor(struct whisper_context * ctx, const char * name, float * dst,
     else if (nm == "cross_v")   { src = d.kvc_v; count = (size_t) Lt * T * S; is_half = true; }
     else if (nm == "self_k")    { src = st.kv_self.k; count = (size_t) Lt * st.kv_self.size * S; is_half = true; }
     else if (nm == "self_v")    { src = st.kv_self.v; count = (size_t) Lt * st.kv_self.size * S; is_half = true; }
-    // lock-step work buffers of the last wmi_full_batch group (debug / tests): [L][rows*T][S] and [rows*T][S]
+    // lock-step work buffers of the last batched encoder pass (debug / tests): [L][rows*P][S] and [rows*P][S], P = the row period (wmi_batch_enc_dims; T for rows of one length)
     else if (nm == "batch_cross_k" && ctx->batch) { src = ctx->batch->kvc_k; count = (size_t) Lt * ctx->batch->enc_rows * ctx->batch->enc_T * S; is_half = true; }
     else if (nm == "batch_cross_v" && ctx->batch) { src = ctx->batch->kvc_v; count = (size_t) Lt * ctx->batch->enc_rows * ctx->batch->enc_T * S; is_half = true; }
     else if (nm == "batch_enc_x" && ctx->batch)   { src = ctx->batch->x; count = (size_t) ctx->batch->enc_rows * ctx->batch->enc_T * S; }
@@ -757,6 +757,29 @@ int wmi_full_batch(struct whisper_context * ctx, struct whisper_full_params para
     (void) hipSetDevice(ctx->device);
     params.no_context = true;                 // chunks are independent transcriptions
     return full_batch(*ctx, params, pcm, n_samples, n_chunks, pcm_on_device != 0);
+}
+
+int wmi_full_batch_ctx(struct whisper_context * ctx, struct whisper_full_params params, const float * const * pcm, const int * n_samples,
+                       const int * audio_ctx, int n_chunks, int pcm_on_device) {
+    if (!audio_ctx) return wmi_full_batch(ctx, params, pcm, n_samples, n_chunks, pcm_on_device);
+    if (!ctx || !ctx->state || !pcm || !n_samples || n_chunks < 0) return -1;
+    CtxScope lk(ctx);
+    // the lengths are checked before anything touches the device (and before the question whether there is one)
+    if (const int bad = check_audio_ctxs(*ctx, audio_ctx, n_chunks, __func__)) return bad;
+    (void) hipSetDevice(ctx->device);
+    params.no_context = true;
+    return full_batch(*ctx, params, pcm, n_samples, n_chunks, pcm_on_device != 0, audio_ctx);
+}
+
+int wmi_batch_enc_dims(struct whisper_context * ctx, int * rows, int * row_period, int * row_T) {
+    if (!ctx) return -1;
+    CtxScope lk(ctx);
+    if (!ctx->batch || ctx->batch->enc_rows <= 0) return -1;
+    const BatchWork & b = *ctx->batch;
+    if (rows) *rows = b.enc_rows;
+    if (row_period) *row_period = b.enc_T;
+    for (int r = 0; row_T && r < b.enc_rows && r < 16; ++r) row_T[r] = b.enc_row_T[r];
+    return 0;
 }
 
 void wmi_set_lockstep_exact(int on) { k::set_rows_valu(on != 0); k::set_attn_one_group(on != 0); }
@@ -1216,7 +1239,7 @@ int wmi_encoder_gemm_stamps(struct whisper_context * ctx, int chunks, double * o
         for (int r = 0; r < ctx->batch->enc_rows; ++r) { rows.push_back(r); seek.push_back(0); }
     } else if (d.mel == nullptr) return -1;
     const int saved = st.exp_n_audio_ctx;
-    auto pass = [&]() { return chunks > 1 ? encode_rows(*ctx, rows, seek, ctx->batch->enc_T) : encode(*ctx, 0); };
+    auto pass = [&]() { return chunks > 1 ? encode_rows(*ctx, rows, seek, ctx->batch->enc_Tmax) : encode(*ctx, 0); };
     k::GemmLog log;
     log.cap_words = (size_t) 4 << 20;
     if (!HIP_OK(hipMalloc((void **) &log.buf, log.cap_words * 8))) return -1;

@@ -93,11 +93,12 @@ bool ensure_batch(whisper_context & ctx, int B) {
     w.mel_rows = 2 * T + 8;
     const size_t nb = (size_t) B;
     // LN1's output and q / k keep every chunk on a 16-row boundary (encode_rows: the q|k|v GEMM's V^T epilogue): T rounded up to 16 rows per chunk
+    // — and so does every other image of the encoder when the chunks of a pass have lengths of their own (encode_rows: TP)
     const size_t TP = (T + 15) & ~(size_t) 15;
     bool ok = dalloc(w.mel_t, nb * w.mel_rows * hp.n_mels + 1024) && dalloc(w.conv1, nb * (2 * T + 8) * S + 4 * S)
-           && dalloc(w.x, nb * T * S) && dalloc(w.xn, nb * TP * S) && dalloc(w.q, nb * TP * S) && dalloc(w.k, nb * TP * S)
-           && dalloc(w.att, nb * T * S) && dalloc(w.vt, nb * S * w.Tpad) && dalloc(w.h, nb * T * 4 * S) && dalloc(w.enc_out_h, nb * T * S)
-           && dalloc(w.kvc_k, Lt * nb * T * S) && dalloc(w.kvc_v, Lt * nb * T * S)
+           && dalloc(w.x, nb * TP * S) && dalloc(w.xn, nb * TP * S) && dalloc(w.q, nb * TP * S) && dalloc(w.k, nb * TP * S)
+           && dalloc(w.att, nb * TP * S) && dalloc(w.vt, nb * S * w.Tpad) && dalloc(w.h, nb * TP * 4 * S) && dalloc(w.enc_out_h, nb * TP * S)
+           && dalloc(w.kvc_k, Lt * nb * TP * S) && dalloc(w.kvc_v, Lt * nb * TP * S)
            && dalloc(w.self_k, nb * Lt * n_ctx * S) && dalloc(w.self_v, nb * Lt * n_ctx * S)
            && dalloc(w.dx, nb * S) && dalloc(w.dq, nb * S) && dalloc(w.datt, nb * S) && dalloc(w.dh, nb * 4 * S) && dalloc(w.logits, nb * hp.n_vocab)
            && dalloc(w.xattn, k::attn_cross_scratch_floats(B, (int) H, (int) T));
@@ -121,12 +122,15 @@ bool ensure_batch(whisper_context & ctx, int B) {
     w.step_seq = 0;
     k::fill_zero(w.vt, nb * S * w.Tpad * sizeof(__half), s);
     k::fill_zero(w.xn, nb * TP * S * sizeof(__half), s);            // (the chunks' padding rows are GEMM operands: finite)
+    k::fill_zero(w.x, nb * TP * S * sizeof(float), s);              // (likewise where the chunks have lengths of their own: rows behind a chunk's
+    k::fill_zero(w.att, nb * TP * S * sizeof(__half), s);           //  length are operands of the stacked GEMMs and are not written by every pass:
+                                                                    //  the attention never writes att rows >= T_r, so w_o multiplies what earlier passes left — finite)
     k::fill_zero(w.conv1, (nb * (2 * T + 8) * S + 4 * S) * sizeof(__half), s);
     k::fill_zero(w.mel_t, (nb * w.mel_rows * hp.n_mels + 1024) * sizeof(__half), s);
     k::fill_zero(w.self_k, nb * Lt * n_ctx * S * sizeof(__half), s);
     k::fill_zero(w.self_v, nb * Lt * n_ctx * S * sizeof(__half), s);
-    k::fill_zero(w.kvc_k, Lt * nb * T * S * sizeof(__half), s);
-    k::fill_zero(w.kvc_v, Lt * nb * T * S * sizeof(__half), s);
+    k::fill_zero(w.kvc_k, Lt * nb * TP * S * sizeof(__half), s);
+    k::fill_zero(w.kvc_v, Lt * nb * TP * S * sizeof(__half), s);
     HIP_TRY(hipStreamSynchronize(s));
     if (w.lanes.empty()) w.lanes.push_back(ctx.state);
     while ((int) w.lanes.size() < B) {
@@ -142,14 +146,41 @@ bool ensure_batch(whisper_context & ctx, int B) {
 
 // ---------------------------------------------------------------------------------------------- batched encoder
 // rows[r] = lane whose mel feeds chunk row r; seek[r] = its mel frame offset  (declared in wmi.h: the in-situ GEMM probe replays it)
-bool encode_rows(whisper_context & ctx, const std::vector<int> & rows, const std::vector<int> & seek, int audio_ctx) {
+// row_ctx (optional): an audio_ctx per row (0 = the model's) instead of the common one.  Rows of different lengths share every launch:
+// T below is the largest of them, the rows' own lengths travel by value (k::RowLens) to the kernels that must know them.
+bool encode_rows(whisper_context & ctx, const std::vector<int> & rows, const std::vector<int> & seek, int audio_ctx, const int * row_ctx) {
     BatchWork & b = *ctx.batch; const Weights & w = ctx.w; const HParams & hp = ctx.model.hp;
     const int64_t t0 = time_us();
     const int nb = (int) rows.size();
-    const int T = audio_ctx > 0 ? audio_ctx : hp.n_audio_ctx;
+    int T = audio_ctx > 0 ? audio_ctx : hp.n_audio_ctx;
+    k::RowLens lens{};
+    bool ragged = false;
+    if (row_ctx && nb >= 2 && nb <= 16) {
+        T = 0;
+        for (int r = 0; r < nb; ++r) { lens.t[r] = row_ctx[r] > 0 ? row_ctx[r] : hp.n_audio_ctx; T = std::max(T, lens.t[r]); }
+        for (int r = 0; r < nb; ++r) ragged = ragged || lens.t[r] != T;
+    } else if (row_ctx && nb == 1) T = row_ctx[0] > 0 ? row_ctx[0] : hp.n_audio_ctx;
+    if (T > hp.n_audio_ctx || (row_ctx && nb > 16)) { WMI_ERR("%s: encoder length %d of %d rows is not served\n", __func__, T, nb); return false; }
+    if (ragged && ctx.model.quantised) { WMI_ERR("%s: rows of different lengths on a block-quantised model (full_batch partitions them)\n", __func__); return false; }
+    // the rows step can give every row its own keys only in the one-launch cross-attention (full_batch cuts other calls into sets of one length)
+    if (ragged && (hp.n_text_state > 1536 || !k::attn_cross_takes_row_lens(hp.n_text_head, T))) {
+        WMI_ERR("%s: rows of different lengths need the one-launch cross-attention (not at S = %d, T = %d, WMI_XATTN_TWO_PASS)\n", __func__, hp.n_text_state, T);
+        return false;
+    }
+    lens.n = ragged ? nb : 0;
     const int S = hp.n_audio_state, H = hp.n_audio_head, La = hp.n_audio_layer, Lt = hp.n_text_layer, nm = hp.n_mels;
     hipStream_t s = ctx.state->dev.stream;
-    const int M = nb * T;
+    // TP: the row period of a pass whose rows have lengths of their own = the largest of them rounded up to 16 — rows between consecutive
+    // chunks in EVERY image of the pass (x, xn, q, k, att, h, enc_out_h, cross K / V; V^T keeps its Tpad columns).  Row t of chunk r:
+    //   t < T_r        valid: per element the arithmetic of the one-chunk pass at T_r (the GEMMs, LayerNorms and epilogues are row-wise;
+    //                  the attention stops at T_r for queries and keys alike)
+    //   T_r <= t < T   written by this pass in x (conv2 of zero mel frames: finite), xn, q, k, V^T, h, enc_out_h, cross K / V; kept from
+    //                  earlier passes (finite: zeroed at allocation, only ever written with finite values) in att; never read for a valid row
+    //                  except as V^T columns of a chunk's last key tile, where their soft-max weight is exactly 0 — hence finite, not junk
+    //   T <= t < TP    x zeroed below, the rest as above
+    // A pass whose rows all have one length keeps its period T (xn / q / k: T rounded up to 16), as before.
+    const int P = ragged ? (T + 15) & ~15 : T;
+    const int M = nb * P;
 
     // conv front-end.  The overlapping-row implicit GEMM needs each chunk's zero guard rows, so the chunks are STACKED with a period of
     // R = 2 T + 8 rows in both images — mel slice rows c R .. (row 0 and the rows behind the 2 T frames are zero) and conv1 rows c R ..
@@ -165,7 +196,7 @@ bool encode_rows(whisper_context & ctx, const std::vector<int> & rows, const std
     if (nb >= 2 && nb <= 16) {
         const int R = 2 * T + 8;
         k::MelSliceBatch mb{};
-        for (int r = 0; r < nb; ++r) { State & ls = *b.lanes[rows[r]]; mb.mel[r] = ls.dev.mel; mb.n_len[r] = ls.mel.n_len; mb.offset[r] = seek[r]; }
+        for (int r = 0; r < nb; ++r) { State & ls = *b.lanes[rows[r]]; mb.mel[r] = ls.dev.mel; mb.n_len[r] = ls.mel.n_len; mb.offset[r] = seek[r]; mb.n_frames[r] = ragged ? 2 * lens.t[r] : 0; }
         k::mel_slice_batch(mb, nb, nm, 2 * T, b.mel_t, nm, R, s);
         {
             k::GemmArgs a{};
@@ -173,13 +204,19 @@ bool encode_rows(whisper_context & ctx, const std::vector<int> & rows, const std
             a.bias = w.conv1_b; a.C = b.conv1 + S; a.ldc = S;
             k::gemm(k::EPI_F16_BIAS_GELU, a, s);
         }
+        if (ragged) {      // chunk r: its conv1 row 2 T_r + 1 and everything behind it, up to and including the next chunk's guard row
+            k::RowLens first{}; first.n = nb;
+            for (int r = 0; r < nb; ++r) first.t[r] = 2 * lens.t[r] + 1;
+            k::fill_zero_tails(b.conv1, first, (size_t) S * sizeof(__half), (size_t) (R + 1) * S * sizeof(__half), (size_t) R * S * sizeof(__half), nb, s);
+        } else
         k::fill_zero_strided(b.conv1 + (size_t) (2 * T + 1) * S, (size_t) 8 * S * sizeof(__half), (size_t) R * S * sizeof(__half), nb, s);
         {
             k::GemmArgs a{};
             a.A = b.conv1; a.lda = 2 * S; a.W = w.conv2_w; a.ldw = w.conv2_k; a.M = nb * (R / 2) - 1; a.N = S; a.K = w.conv2_k;
-            a.bias = w.conv2_b; a.C = b.x; a.ldc = S; a.resid = w.e_pe; a.ldr = S; a.rows_per_chunk = R / 2;
+            a.bias = w.conv2_b; a.C = b.x; a.ldc = S; a.resid = w.e_pe; a.ldr = S; a.rows_per_chunk = R / 2; a.conv2_out_rows = ragged ? P : 0;
             k::gemm(k::EPI_CONV2, a, s);
         }
+        if (P != T) k::fill_zero_strided(b.x + (size_t) T * S, (size_t) (P - T) * S * sizeof(float), (size_t) P * S * sizeof(float), nb, s);
     } else
     for (int r = 0; r < nb; ++r) {
         State & ls = *b.lanes[rows[r]];
@@ -208,21 +245,22 @@ bool encode_rows(whisper_context & ctx, const std::vector<int> & rows, const std
         if (!encode_layers_q_on(ctx, e, s)) return false;
         HIP_TRY(hipStreamSynchronize(s));
         if (!HIP_OK(hipGetLastError())) return false;
-        b.enc_rows = nb; b.enc_T = T;
+        b.enc_rows = nb; b.enc_T = T; b.enc_Tmax = T; b.enc_ragged = false;
+        for (int r = 0; r < 16; ++r) b.enc_row_T[r] = r < nb ? T : 0;
         b.t_encode_us += time_us() - t0;
         return true;
     }
     const float kq_scale = 1.0f / sqrtf((float) S / H);
     // Rows per chunk of LN1's output, q and k: T rounded up to 16 (1500 -> 1504), so that every 16-row MFMA fragment of the q|k|v GEMM lies
     // inside one chunk at a 16-step offset — its V^T third then leaves in whole 128-byte lines (gemm_epi.h: epilogue_vt_wide) instead of 32-byte
-    // pieces (what the launch cost over a plain epilogue: 41 against 29.5 us at 8 chunks).  The padding rows are zero in xn (never written),
+    // pieces (what the launch cost over a plain epilogue: 41 against 29.5 us at 8 chunks).  The padding rows of xn are finite (zero, or what an earlier pass with another row period left there),
     // finite junk in q / k / V^T (never read as queries or keys: the attention stops at T).
-    const int TP = (nb >= 2 && (T & 15) != 0 && ((T + 15) & ~15) <= b.Tpad) ? (T + 15) & ~15 : T;
+    const int TP = ragged ? P : (nb >= 2 && (T & 15) != 0 && ((T + 15) & ~15) <= b.Tpad) ? (T + 15) & ~15 : T;
     const int MP = nb * TP;
     b.qk_rows = TP;
     for (int il = 0; il < La; ++il) {
         const EncLayerW & l = w.enc[il];
-        if (TP != T) k::layernorm(b.x, M, S, l.ln1_g, l.ln1_b, hp.eps, b.xn, nullptr, s, T, TP);
+        if (TP != P) k::layernorm(b.x, M, S, l.ln1_g, l.ln1_b, hp.eps, b.xn, nullptr, s, T, TP);
         else         k::layernorm(b.x, M, S, l.ln1_g, l.ln1_b, hp.eps, b.xn, nullptr, s);
         {
             k::GemmArgs a{};
@@ -231,7 +269,7 @@ bool encode_rows(whisper_context & ctx, const std::vector<int> & rows, const std
             a.rows_per_chunk = TP; a.chunk_stride_aux2 = (int64_t) S * b.Tpad;
             k::gemm(k::EPI_QKV_ENC, a, s);
         }
-        k::attn_encoder(b.q, b.k, b.vt, T, b.Tpad, S, H, kq_scale, b.att, s, nb, nullptr, TP);
+        k::attn_encoder(b.q, b.k, b.vt, T, b.Tpad, S, H, kq_scale, b.att, s, nb, nullptr, TP, ragged ? &lens : nullptr, P);
         {
             k::GemmArgs a{};
             a.A = b.att; a.lda = S; a.W = l.w_o; a.ldw = S; a.M = M; a.N = S; a.K = S; a.bias = l.b_o;
@@ -262,7 +300,8 @@ bool encode_rows(whisper_context & ctx, const std::vector<int> & rows, const std
     }
     HIP_TRY(hipStreamSynchronize(s));
     if (!HIP_OK(hipGetLastError())) return false;
-    b.enc_rows = nb; b.enc_T = T;
+    b.enc_rows = nb; b.enc_T = P; b.enc_Tmax = T; b.enc_ragged = ragged;
+    for (int r = 0; r < 16; ++r) b.enc_row_T[r] = r >= nb ? 0 : ragged ? lens.t[r] : T;
     b.t_encode_us += time_us() - t0;
     return true;
 }
@@ -296,13 +335,18 @@ static void enqueue_rows_step(whisper_context & ctx, int nb, bool chained = fals
     BatchWork & b = *ctx.batch; const Weights & w = ctx.w; const HParams & hp = ctx.model.hp;
     const unsigned M = g_rows_mask;
     const int S = hp.n_text_state, H = hp.n_text_head, Lt = hp.n_text_layer, NV = hp.n_vocab, n_ctx = hp.n_text_ctx;
-    const int Tc = b.enc_T;
+    // Tc: the keys of the longest row (layout of the partials, grid); TPc: rows between the chunks' cross K / V.  Rows with lengths of their
+    // own: each attends its own keys in its own slices (k::RowLens by value: a captured step is keyed on them, decode_rows_step)
+    const int Tc = b.enc_Tmax, TPc = b.enc_T;
+    k::RowLens xlens{};
+    if (b.enc_ragged) { xlens.n = nb; for (int r = 0; r < nb; ++r) xlens.t[r] = b.enc_row_T[r]; }
+    const k::RowLens * xl = b.enc_ragged ? &xlens : nullptr;
     hipStream_t s = ctx.state->dev.stream;
     const k::DecStep * stp = (const k::DecStep *) b.step_dev;
     const float kq_scale = powf((float) S / H, -0.25f);
     const int step_stride = (int) (sizeof(k::DecStep) / sizeof(int32_t));
     const int64_t cache_stride = (int64_t) Lt * n_ctx * S;             // between the chunks' self caches
-    const int64_t cross_layer = (int64_t) b.enc_rows * Tc * S;
+    const int64_t cross_layer = (int64_t) b.enc_rows * TPc * S;
 
     // where the chained form mirrors the rest of the host's records: beside the vocabulary projection when that launch is the
     // matrix-core rows kernel, else beside the last layer's self-attention
@@ -317,7 +361,9 @@ static void enqueue_rows_step(whisper_context & ctx, int nb, bool chained = fals
     // step-record mirror has to ride in the last layer's self-attention launch, not for a probe of single kernel kinds
     const bool fronted = (fronted_in < 0 ? rows_fronted(ctx, nb) : fronted_in != 0) && (M & 2) && (M & 4) && (M & 8) && (!chained || mirror_in_logits);
     // ... and the back of the cross-attention the same way where its launch fits (k::xback_usable: 4 - 8 key slices, S <= 512, residency)
-    const bool backed = fronted && (M & 16) && (M & 64) && !k::knobs().no_xback && k::xback_usable(S, H, Tc, nb);
+    // (rows of ONE length only: k::xback combines a head's slices inside the launch with the launch's slice plan; rows with lengths of their
+    //  own take the partials + out-projection form below)
+    const bool backed = fronted && (M & 16) && (M & 64) && !k::knobs().no_xback && !b.enc_ragged && k::xback_usable(S, H, Tc, nb);
     if ((M & 1) && !chained) k::dec_embed_step((const k::DecStep *) b.step_host, (k::DecStep *) b.step_dev, S, w.d_te, w.d_pe, b.dx, s, nb);
     auto base = [&](int K, int N, const __half * W, const float * bias, int epi, void * C, int ldc) {
         k::GemvArgs g{};
@@ -370,7 +416,7 @@ static void enqueue_rows_step(whisper_context & ctx, int nb, bool chained = fals
                 g.x32 = b.dx; g.ln_g = l.ln2_g; g.ln_b = l.ln2_b; g.scale = kq_scale;
                 k::gemv(g, s);
                 k::attn_cross_split_partials(b.dq, nb, S, H, b.kvc_k + (size_t) il * cross_layer, b.kvc_v + (size_t) il * cross_layer, Tc,
-                                             b.xattn, &po, &pl, &pm, &ns, s, (int64_t) Tc * S);
+                                             b.xattn, &po, &pl, &pm, &ns, s, (int64_t) TPc * S, xl);
             } else if (backed) {   // LN2 + cross query + key slices, the combine (once per head) and the out projection of every row as ONE launch (k::xback, rows on grid.z)
                 k::XbackArgs xb{};
                 xb.x = b.dx; xb.xout = b.dx; xb.ln_g = l.ln2_g; xb.ln_b = l.ln2_b; xb.eps = hp.eps; xb.S = S; xb.wq = l.w_cq; xb.bq = l.b_cq; xb.qscale = kq_scale;
@@ -379,13 +425,13 @@ static void enqueue_rows_step(whisper_context & ctx, int nb, bool chained = fals
                 xb.gp = (unsigned long long *) (base + 64); xb.ga = xb.gp + 8 * 8 * 66;
                 xb.epoch = (uint32_t *) base + 6; xb.par = il & 1; xb.fault = (uint32_t *) base + 4;
                 xb.spin_cap = k::knobs().pair_spin_cap; xb.withhold = k::knobs().xback_withhold;
-                xb.kv_row_stride = (int64_t) Tc * S; xb.rows = nb;
+                xb.kv_row_stride = (int64_t) TPc * S; xb.rows = nb;
                 k::xback(xb, H, b.xattn, s);
                 goto mlp_rows;
             } else
             k::attn_cross_qsplit_partials(b.dx, l.ln2_g, l.ln2_b, hp.eps, l.w_cq, l.b_cq, kq_scale, nb, S, H,
                                           b.kvc_k + (size_t) il * cross_layer, b.kvc_v + (size_t) il * cross_layer, Tc,
-                                          b.xattn, &po, &pl, &pm, &ns, s, (int64_t) Tc * S);
+                                          b.xattn, &po, &pl, &pm, &ns, s, (int64_t) TPc * S, xl);
             // the out projection combines the key-slice partials in its prologue (all row kernels do): no combine launch
             k::GemvArgs g = base(S, S, l.w_co, l.b_co, k::EPI_F32_BIAS_RESID, b.dx, S);
             g.comb_o = po; g.comb_l = pl; g.comb_m = pm; g.comb_ns = ns; g.resid = b.dx;
@@ -438,14 +484,20 @@ bool decode_rows_step(whisper_context & ctx, int nb) {
         // the key includes the epoch of the run-time kernel switches (wmi_set_lockstep_exact: VALU rows / one-group attention):
         // a step captured under the other mode would keep replaying that mode's kernels
         const int epoch = k::mode_epoch();
-        if (rg.nb != nb || rg.T != b.enc_T || rg.rows != b.enc_rows || rg.epoch != epoch) {
+        // ... and the rows' own encoder lengths: they are kernel arguments of the captured cross-attention launches
+        auto keyed = [&](const BatchWork::RowsGraph & g) {
+            return g.nb == nb && g.T == b.enc_T && g.rows == b.enc_rows && g.epoch == epoch && g.ragged == b.enc_ragged &&
+                   memcmp(g.row_T, b.enc_row_T, sizeof(g.row_T)) == 0;
+        };
+        if (!keyed(rg)) {
             if (rg.exec) (void) hipGraphExecDestroy(rg.exec);
             if (rg.graph) (void) hipGraphDestroy(rg.graph);
-            rg = BatchWork::RowsGraph{}; rg.nb = nb; rg.T = b.enc_T; rg.rows = b.enc_rows; rg.epoch = epoch;
+            rg = BatchWork::RowsGraph{}; rg.nb = nb; rg.T = b.enc_T; rg.rows = b.enc_rows; rg.epoch = epoch; rg.ragged = b.enc_ragged;
+            memcpy(rg.row_T, b.enc_row_T, sizeof(rg.row_T));
         }
         ++rg.seen;                                                // (counted over both forms: the embedding form runs once per window)
         const BatchWork::RowsGraph & og = b.rows_graph[(chained ? 0 : 1) | (fronted ? 2 : 0)];
-        const int seen_other = (og.nb == nb && og.T == b.enc_T && og.rows == b.enc_rows && og.epoch == epoch) ? og.seen : 0;
+        const int seen_other = keyed(og) ? og.seen : 0;
         if (use_graph && !rg.exec && !rg.failed && rg.seen + seen_other > 24) {
             if (hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess) {
                 enqueue_rows_step(ctx, nb, chained, fronted ? 1 : 0);
@@ -611,8 +663,21 @@ void free_batch(whisper_context & ctx) {
     ctx.batch = nullptr;
 }
 
+int check_audio_ctxs(const whisper_context & ctx, const int * audio_ctx, int n, const char * who) {
+    for (int c = 0; audio_ctx && c < n; ++c) if (audio_ctx[c] < 0) return -1;
+    for (int c = 0; audio_ctx && c < n; ++c) if (audio_ctx[c] > ctx.model.hp.n_audio_ctx) {
+        WMI_ERR("%s: audio_ctx is larger than the maximum allowed (%d > %d)\n", who, audio_ctx[c], ctx.model.hp.n_audio_ctx);
+        return -5;
+    }
+    return 0;
+}
+
+// audio_ctx (wmi_full_batch_ctx): an encoder length per chunk.  The call orders the lock-step chunks by length (below), so the nested
+// calls it makes for that see `ordered` chunks
+static thread_local bool t_ordered = false;
+
 int full_batch(whisper_context & ctx, whisper_full_params params, const float * const * pcm, const int * n_samples, int n_chunks,
-               bool on_device) {
+               bool on_device, const int * audio_ctx) {
     if (!compute_ready(ctx, __func__)) return -2;
     if (n_chunks <= 0) return 0;
     BusyScope busy(ctx.device);                                    // (a lock-step call owns the GPU as much as a transcription does: wmi.h)
@@ -620,6 +685,10 @@ int full_batch(whisper_context & ctx, whisper_full_params params, const float * 
     const HParams & hp = ctx.model.hp;
     State * primary = ctx.state;
     if (!ctx.batch) ctx.batch = new BatchWork();
+    // chunk c's own audio_ctx, and the parameters whisper_full would get for it
+    auto actx = [&](int c) { return audio_ctx ? audio_ctx[c] : params.audio_ctx; };
+    auto params_of = [&](int c) { whisper_full_params p = params; p.audio_ctx = actx(c); return p; };
+    auto eff_T = [&](int c) { return actx(c) > 0 ? actx(c) : hp.n_audio_ctx; };
     ctx.batch->results.assign(n_chunks, {});
     ctx.batch->redo.assign(n_chunks, 0);
     ctx.batch->lang_id.assign(n_chunks, -1); ctx.batch->lang_detected.assign(n_chunks, 0); ctx.batch->lang_probs.assign((size_t) n_chunks * k::LANG_HEAD_N, 0.0f);
@@ -636,7 +705,7 @@ int full_batch(whisper_context & ctx, whisper_full_params params, const float * 
         // decoders' generators start from their initial seed (W/whisper.cpp:3077), so a chunk's result does not
         // depend on which chunks were transcribed before it
         for (auto & dec : primary->decoders) dec.rng = std::mt19937(0);
-        const int rc = full(ctx, params, on_device ? nullptr : pcm[c], on_device ? pcm[c] : nullptr, n_samples[c]);
+        const int rc = full(ctx, params_of(c), on_device ? nullptr : pcm[c], on_device ? pcm[c] : nullptr, n_samples[c]);
         if (rc == 0) { ctx.batch->results[c] = std::move(primary->result_all); keep_lang(c, *primary); }
         primary->result_all.clear();
         return rc;
@@ -650,7 +719,7 @@ int full_batch(whisper_context & ctx, whisper_full_params params, const float * 
     const bool lockstep = params.strategy == WHISPER_SAMPLING_GREEDY && params.temperature < 1e-6f &&
                           lang_ok && !distilled && !params.speed_up && !params.logits_filter_callback && !params.grammar_rules && params.n_grammar_rules == 0 && !params.new_segment_callback &&
                           !params.progress_callback && !params.encoder_begin_callback && !params.abort_callback &&
-                          ctx.model.n_loaded > 0 && n_chunks > 1;
+                          ctx.model.n_loaded > 0 && (n_chunks > 1 || audio_ctx != nullptr || t_ordered);
     if (!lockstep) {
         // Chunks the lock-step rows cannot carry (beam search, t > 0, callbacks ...): the general driver, chunk by chunk — and, where
         // nothing observable depends on the order, on several REPLICA contexts at once: worker w takes the chunks c = w (mod workers),
@@ -681,7 +750,7 @@ int full_batch(whisper_context & ctx, whisper_full_params params, const float * 
                     if (w == 0) rc = run_alone(c);
                     else {
                         for (auto & dec : wc.state->decoders) dec.rng = std::mt19937(0);
-                        rc = full(wc, params, on_device ? nullptr : pcm[c], on_device ? pcm[c] : nullptr, n_samples[c]);
+                        rc = full(wc, params_of(c), on_device ? nullptr : pcm[c], on_device ? pcm[c] : nullptr, n_samples[c]);
                         if (rc == 0) { ctx.batch->results[c] = std::move(wc.state->result_all); keep_lang(c, *wc.state); }
                         wc.state->result_all.clear();
                     }
@@ -702,9 +771,53 @@ int full_batch(whisper_context & ctx, whisper_full_params params, const float * 
         for (int w = 0; w < workers; ++w) if (rets[w] != 0) return rets[w];
         return 0;
     }
-    if (params.audio_ctx > hp.n_audio_ctx) {
+    if (!audio_ctx && params.audio_ctx > hp.n_audio_ctx) {        // (with lengths per chunk params.audio_ctx is not used)
         WMI_ERR("%s: audio_ctx is larger than the maximum allowed (%d > %d)\n", __func__, params.audio_ctx, hp.n_audio_ctx);
         return -5;
+    }
+    if (const int bad = check_audio_ctxs(ctx, audio_ctx, n_chunks, __func__)) return bad;
+    // ---- chunks with lengths of their own: longest first, so that the chunks that share a group of 16 rows (and a range of the groups below)
+    // have neighbouring lengths and the rows behind a chunk's own length (encode_rows: TP) stay few.  Results go back in the caller's order.
+    // A chunk's result does not depend on the order in exact mode (per-row arithmetic); in the default mode as it depends on the grouping.
+    // Where the rows cannot carry a length each — block-quantised models (encode_layers_q_on has one length), the two-launch form of the
+    // cross-attention — the ordered chunks are cut into sets of one length, each a lock-step call of its own with that length.
+    if (audio_ctx && !t_ordered) {
+        bool uniform = true;
+        for (int c = 1; c < n_chunks; ++c) uniform = uniform && eff_T(c) == eff_T(0);
+        const bool per_row = !ctx.model.quantised && k::attn_cross_takes_row_lens(hp.n_text_head, hp.n_audio_ctx) && hp.n_text_state <= 1536;
+        std::vector<int> order(n_chunks);
+        for (int c = 0; c < n_chunks; ++c) order[c] = c;
+        if (!uniform) std::stable_sort(order.begin(), order.end(), [&](int a, int b2) { return eff_T(a) > eff_T(b2); });
+        std::vector<const float *> o_pcm(n_chunks); std::vector<int> o_n(n_chunks), o_ctx(n_chunks);
+        for (int i = 0; i < n_chunks; ++i) { o_pcm[i] = pcm[order[i]]; o_n[i] = n_samples[order[i]]; o_ctx[i] = audio_ctx[order[i]]; }
+        BatchWork & bw = *ctx.batch;
+        std::vector<std::vector<Segment>> all(n_chunks);
+        std::vector<int> all_redo(n_chunks, 0), all_lang(n_chunks, -1); std::vector<char> all_det(n_chunks, 0);
+        std::vector<float> all_probs((size_t) n_chunks * k::LANG_HEAD_N, 0.0f);
+        int64_t tm[4] = {0, 0, 0, 0}; int steps = 0, chained = 0, groups = 1;
+        struct Flag { Flag() { t_ordered = true; } ~Flag() { t_ordered = false; } } flag;
+        for (int i0 = 0; i0 < n_chunks; ) {
+            int i1 = n_chunks;
+            if (!per_row && !uniform) { i1 = i0 + 1; while (i1 < n_chunks && eff_T(order[i1]) == eff_T(order[i0])) ++i1; }
+            whisper_full_params ps = params;
+            if (!per_row || uniform) ps.audio_ctx = o_ctx[i0];          // one length: the call wmi_full_batch makes
+            const int rc = full_batch(ctx, ps, o_pcm.data() + i0, o_n.data() + i0, i1 - i0, on_device, per_row && !uniform ? o_ctx.data() + i0 : nullptr);
+            if (rc != 0) return rc;
+            for (int i = i0; i < i1; ++i) {
+                const int c = order[i];
+                all[c] = std::move(bw.results[i - i0]); all_redo[c] = bw.redo[i - i0];
+                all_lang[c] = bw.lang_id[i - i0]; all_det[c] = bw.lang_detected[i - i0];
+                std::copy_n(bw.lang_probs.begin() + (size_t) (i - i0) * k::LANG_HEAD_N, k::LANG_HEAD_N, all_probs.begin() + (size_t) c * k::LANG_HEAD_N);
+            }
+            tm[0] += bw.t_mel_us; tm[1] += bw.t_encode_us; tm[2] += bw.t_decode_us; tm[3] += bw.t_emit_us; steps += bw.n_steps; chained += bw.n_chained;
+            groups = std::max(groups, bw.groups_last);
+            i0 = i1;
+        }
+        bw.results = std::move(all); bw.redo = std::move(all_redo);
+        bw.lang_id = std::move(all_lang); bw.lang_detected = std::move(all_det); bw.lang_probs = std::move(all_probs);
+        bw.t_mel_us = tm[0]; bw.t_encode_us = tm[1]; bw.t_decode_us = tm[2]; bw.t_emit_us = tm[3]; bw.n_steps = steps; bw.n_chained = chained;
+        bw.groups_last = groups;
+        return 0;
     }
     // ---- lock-step GROUPS side by side (round 6).  The chunks are dealt to `groups` contiguous ranges, each a lock-step call of its own — range
     // 0 on this context, the others on replica contexts (own state, stream and work set, the weights borrowed) on host threads of their own.
@@ -736,7 +849,8 @@ int full_batch(whisper_context & ctx, whisper_full_params params, const float * 
                     t_in_group = true;
                     struct Off { ~Off() { t_in_group = false; } } off;
                     const int cnt = c0[g + 1] - c0[g];
-                    const int rc = full_batch(wc, params, pcm + c0[g], n_samples + c0[g], cnt, on_device);
+                    struct Ordered { bool was; Ordered() : was(t_ordered) { t_ordered = true; } ~Ordered() { t_ordered = was; } } ordered;   // (the ranges are cut from ordered chunks: the nested call, on a thread of its own for g > 0, must not order or cut again)
+                    const int rc = full_batch(wc, params, pcm + c0[g], n_samples + c0[g], cnt, on_device, audio_ctx ? audio_ctx + c0[g] : nullptr);
                     rets[g] = rc;
                     if (rc != 0 || !wc.batch) return;
                     std::lock_guard<std::mutex> lk(merge_mu);
@@ -834,7 +948,7 @@ int full_batch(whisper_context & ctx, whisper_full_params params, const float * 
             ls.result_all.clear();
             ls.ts_failed = false;
             ls.prompt_past = prompt_user;                     // every chunk is an independent transcription (no_context semantics)
-            ls.exp_n_audio_ctx = params.audio_ctx;
+            ls.exp_n_audio_ctx = actx(row.chunk);
             if (v.is_multilingual() && lang_known) ls.lang_id = lid_known;
             ls.lang_probs.clear();
             const int64_t tm0 = time_us();
@@ -926,9 +1040,13 @@ int full_batch(whisper_context & ctx, whisper_full_params params, const float * 
                 std::vector<int> lanes(nb), seeks(nb);
                 for (int r = 0; r < nb; ++r) { lanes[r] = rows[act[r]].lane; seeks[r] = rows[act[r]].seek; }
                 // the detection has encoded these very windows (same rows in the same order, seek 0, same length): its cross K/V are still there
-                const bool encoded = enc_at_0 && params.audio_ctx == 0 && params.offset_ms == 0 && nb == ng;
+                // (every chunk at the model's full length, which is what the detection ran at)
+                bool all_full = true;
+                std::vector<int> row_ctx(nb);
+                for (int r = 0; r < nb; ++r) { row_ctx[r] = actx(rows[act[r]].chunk); all_full = all_full && eff_T(rows[act[r]].chunk) == hp.n_audio_ctx; }
+                const bool encoded = enc_at_0 && (audio_ctx ? all_full : params.audio_ctx == 0) && params.offset_ms == 0 && nb == ng;
                 enc_at_0 = false;
-                if (!encoded && !encode_rows(ctx, lanes, seeks, params.audio_ctx)) { WMI_ERR("%s: failed to encode\n", __func__); return -6; }
+                if (!encoded && !encode_rows(ctx, lanes, seeks, params.audio_ctx, audio_ctx ? row_ctx.data() : nullptr)) { WMI_ERR("%s: failed to encode\n", __func__); return -6; }
                 b.chain_valid = false;                             // new windows, possibly other chunks in the rows: every row restarts at cell 0
             }
             for (int r = 0; r < nb; ++r) {

@@ -14,6 +14,7 @@
 #include <climits>
 #include <cstring>
 #include <mutex>
+#include <vector>
 #include "wmi.h"
 #include "kernels.h"
 
@@ -279,6 +280,26 @@ int wmi_capture_full(struct wmi_capture * c, struct whisper_full_params params) 
         if (n < 0) return n;
         return wmi_full_device_pcm(c->ctx, params, c->d_pcm, n, nullptr);
     } catch (...) { return -3; }
+}
+
+int wmi_capture_full_batch(struct wmi_capture * const * caps, int n, struct whisper_full_params params, const int * audio_ctx) {
+    if (!caps || n <= 0) return -1;
+    for (int i = 0; i < n; ++i) if (!caps[i] || caps[i]->ctx != caps[0]->ctx) return -1;
+    whisper_context * ctx = caps[0]->ctx;
+    try {
+        Scope lk(ctx);                                                  // once, for the refreshes and the transcription alike
+        if (const int bad = check_audio_ctxs(*ctx, audio_ctx, n, __func__)) return bad;      // wmi_full_batch_ctx's checks, before any device work here too
+        for (int i = 0; i < n; ++i) if (caps[i]->count <= 0) return -3; // an empty session: wmi_full_batch's empty chunk
+        if (!HIP_OK(hipSetDevice(ctx->device))) return -2;
+        std::vector<const float *> pcm(n); std::vector<int> ns(n);
+        for (int i = 0; i < n; ++i) {
+            const int r = refresh(caps[i]);
+            if (r < 0) return r;
+            if (r == 0) return -3;
+            pcm[i] = caps[i]->d_pcm; ns[i] = r;                         // the sessions' own device buffers: nothing is copied
+        }
+        return wmi_full_batch_ctx(ctx, params, pcm.data(), ns.data(), audio_ctx, n, 1);
+    } catch (...) { WMI_ERR("wmi_capture_full_batch: out of memory\n"); return -3; }
 }
 
 int wmi_capture_stats(struct wmi_capture * c, int64_t * out4) {

@@ -57,13 +57,13 @@ __device__ __forceinline__ half2v gelu16_pair(float2v x) {
 }
 
 // EPI_CONV2 over several lock-step chunks in one launch (GemmArgs::rows_per_chunk = P > 0): the implicit-GEMM rows of chunk c are
-// c P .. c P + P - 1 (P = T + 4: the chunk's T output frames and the rows that straddle its guard rows), output row c T + t, positional
-// row t; rows t >= T are not stored.  P = 0: one chunk, row m is both.
+// c P .. c P + P - 1 (P = T + 4: the chunk's T output frames and the rows that straddle its guard rows), output row c T + t (c O + t with
+// GemmArgs::conv2_out_rows = O > 0), positional row t; rows t >= T are not stored.  P = 0: one chunk, row m is both.
 struct Conv2Row { int out, pe; bool valid; };
 __device__ __forceinline__ Conv2Row conv2_row(const GemmArgs & a, int m) {
     if (a.rows_per_chunk <= 0) return Conv2Row{m, m, true};
     const int P = a.rows_per_chunk, c = m / P, t = m - c * P;
-    return Conv2Row{c * (P - 4) + t, t < P - 4 ? t : 0, t < P - 4};
+    return Conv2Row{c * (a.conv2_out_rows > 0 ? a.conv2_out_rows : P - 4) + t, t < P - 4 ? t : 0, t < P - 4};
 }
 
 // first orientation, mfma(A rows, W rows): fragment (i, j) holds rows m = mb + i*16 + fq*4 + r (r = 0..3) of column n = nb + j*16 + frow.

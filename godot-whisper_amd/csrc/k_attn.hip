@@ -19,6 +19,7 @@
 #include "kernels.h"
 #include "wave_ops.h"
 #include "xattn_tail.h"
+#include <cstdio>
 #include <cstdlib>
 #include <atomic>
 
@@ -46,7 +47,8 @@ __device__ __forceinline__ uint32_t lds_off(int row, int chunk) { return (uint32
 template <int NW, int KS>
 __global__ __launch_bounds__(NW * 64 * KS) void k_attn_enc(const __half * __restrict__ q, const __half * __restrict__ k,
                                                   const __half * __restrict__ vt, int T, int Tpad, int S, float scale,
-                                                  __half * __restrict__ out, float * __restrict__ out32, int qk_rows) {
+                                                  __half * __restrict__ out, float * __restrict__ out32, int qk_rows,
+                                                  int out_rows, const RowLens lens) {
     __shared__ __attribute__((aligned(16))) unsigned char sK_[KS][64 * 128];
     __shared__ __attribute__((aligned(16))) unsigned char sV_[KS][64 * 128];
     const int half = KS == 1 ? 0 : (int) (threadIdx.x / (NW * 64));       // key half of this wavefront group
@@ -54,11 +56,13 @@ __global__ __launch_bounds__(NW * 64 * KS) void k_attn_enc(const __half * __rest
     const int tid = threadIdx.x - half * (NW * 64), lane = tid & 63, wave = tid >> 6;
     const int fr = lane & 15, fq = lane >> 4;
     const int head = blockIdx.y;
+    // chunks with a length of their own (RowLens): chunk z is the one-chunk launch at its T; query blocks wholly behind it leave at once
+    if (lens.n) { T = lens.t[blockIdx.z]; if ((int) blockIdx.x * (NW * 16) >= T) return; }
     const int q0 = blockIdx.x * (NW * 16) + wave * 16;
-    {   // chunk (lane of a batched encode): activations are [B][T][S], V^T is [B][S][Tpad]
+    {   // chunk (lane of a batched encode): activations are [B][out_rows][S], V^T is [B][S][Tpad]
         const size_t zb = blockIdx.z;
         q += zb * (size_t) qk_rows * S; k += zb * (size_t) qk_rows * S; vt += zb * (size_t) S * Tpad;
-        if (out32) out32 += zb * (size_t) T * S; else out += zb * (size_t) T * S;
+        if (out32) out32 += zb * (size_t) out_rows * S; else out += zb * (size_t) out_rows * S;
     }
 
     half8 qf[2];
@@ -609,10 +613,25 @@ __global__ __launch_bounds__(256) void k_xattn_fused(const float * __restrict__ 
                                                      const __half * __restrict__ q16,
                                                      int S, const __half * __restrict__ kc, const __half * __restrict__ vc, int T, int ks, int ns,
                                                      float * __restrict__ pmax, float * __restrict__ part_o, float * __restrict__ part_l,
-                                                     int64_t kv_row_stride, int head_major, const Stamp sp) {
+                                                     int64_t kv_row_stride, int head_major, const Stamp sp, const RowLens lens) {
     __shared__ float qs[64];
     __shared__ float red[4], lred[4];
     __shared__ float ored[4][64];
+    if (lens.n) {
+        // lock-step rows with an encoder length of their own: row z attends its own T keys in the slices the one-row launch takes at that
+        // length (xattn_layout); `ns` stays the launch's (the layout of the partials).  A slice the row does not have leaves a neutral
+        // partial — weight 0 in every consumer's combine, so the row's f32 sums are those over its own slices, in the same order
+        const int z = blockIdx.z, hd = head_major ? blockIdx.x : blockIdx.y, sl = head_major ? blockIdx.y : blockIdx.x, Hn = head_major ? gridDim.x : gridDim.y;
+        T = lens.t[z];
+        int nsr = (T + 191) / 192; if (nsr < 1) nsr = 1; if (nsr > XS_MAX_SLICES) nsr = XS_MAX_SLICES;      // xattn_layout's plan at this length
+        if (sl >= nsr) {
+            const size_t at = ((size_t) z * Hn + hd) * ns + sl;
+            if (threadIdx.x < 64) part_o[at * 64 + threadIdx.x] = 0.0f;
+            if (threadIdx.x == 0) { part_l[at] = 0.0f; pmax[at] = -INFINITY; }
+            return;
+        }
+        ks = (T + nsr - 1) / nsr;
+    }
     const unsigned long long ts0 = stamp_t0(sp.base), tc0 = sp.base ? clock64() : 0ull;      // (+ shader-clock counter: the probe derives the effective clock)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     // head_major: grid (H, ns, n) — workgroup id % 8 = head % 8, so the 8 key slices of a head share one XCD's L2 and that L2
@@ -1097,7 +1116,7 @@ static XLayout xattn_layout(int n, int H, int T, float * scratch) {
     // WMI_XATTN_TWO_PASS: the literal two-launch form (global maximum before the f16 exponent), kept for A/B and as the S-agnostic fall-back
     static const bool two_pass = getenv("WMI_XATTN_TWO_PASS") != nullptr;
     XLayout L;
-    L.ns = (T + 191) / 192; if (L.ns < 1) L.ns = 1; if (L.ns > XS_MAX_SLICES) L.ns = XS_MAX_SLICES;
+    L.ns = (T + 191) / 192; if (L.ns < 1) L.ns = 1; if (L.ns > XS_MAX_SLICES) L.ns = XS_MAX_SLICES;      // (k_xattn_fused repeats this plan for rows with a length of their own)
     L.ks = (T + L.ns - 1) / L.ns;
     L.ld_sc = (T + 63) & ~63;
     L.sc = scratch;
@@ -1113,10 +1132,10 @@ static int g_xattn_probe_skip = 0;        // probe only: bit 0 skips the score k
 void set_xattn_probe_skip(int mask) { g_xattn_probe_skip = mask; }
 
 static void xattn_run(const XLayout & L, const __half * q, int n, int S, int H, const __half * kc, const __half * vc, int T,
-                      hipStream_t st, int64_t kv_row_stride) {
+                      hipStream_t st, int64_t kv_row_stride, const RowLens & lens = RowLens{}) {
     if (L.fused) {
         hipLaunchKernelGGL((k_xattn_fused<1, false>), xattn_grid(L.ns, H, n), dim3(256), 0, st, nullptr, nullptr, nullptr, 0.0f, nullptr, nullptr, 0.0f,
-                           q, S, kc, vc, T, L.ks, L.ns, L.pmax, L.part_o, L.part_l, kv_row_stride, xattn_head_major() ? 1 : 0, stamp_next());
+                           q, S, kc, vc, T, L.ks, L.ns, L.pmax, L.part_o, L.part_l, kv_row_stride, xattn_head_major() ? 1 : 0, stamp_next(), lens);
         return;
     }
     hipLaunchKernelGGL(k_xattn_scores, dim3(L.ns, H, n), dim3(256), 0, st, q, S, kc, T, L.ks, L.ns, L.sc, L.ld_sc, L.pmax, kv_row_stride);
@@ -1133,9 +1152,10 @@ void attn_cross_split(const __half * q, int n, int S, int H, const __half * kc, 
 
 void attn_cross_split_partials(const __half * q, int n, int S, int H, const __half * kc, const __half * vc, int T,
                                float * scratch, const float ** po, const float ** pl, const float ** pm, int * pns, hipStream_t st,
-                               int64_t kv_row_stride) {
+                               int64_t kv_row_stride, const RowLens * row_lens) {
     const XLayout L = xattn_layout(n, H, T, scratch);
-    xattn_run(L, q, n, S, H, kc, vc, T, st, kv_row_stride);
+    if (row_lens && row_lens->n && !L.fused) { fprintf(stderr, "attn_cross_split_partials: per-row lengths need the one-launch form - nothing launched\n"); *po = *pl = *pm = nullptr; *pns = 0; return; }
+    xattn_run(L, q, n, S, H, kc, vc, T, st, kv_row_stride, row_lens ? *row_lens : RowLens{});
     *po = L.part_o; *pl = L.part_l; *pm = L.fused ? L.pmax : nullptr; *pns = L.ns;
 }
 
@@ -1158,16 +1178,17 @@ void attn_cross_partials_layout(int n, int H, int T, float * scratch, const floa
 void attn_cross_qsplit_partials(const float * x32, const float * ln_g, const float * ln_b, float eps, const __half * wq,
                                 const float * bq, float qscale, int n, int S, int H, const __half * kc, const __half * vc, int T,
                                 float * scratch, const float ** po, const float ** pl, const float ** pm, int * pns, hipStream_t st,
-                                int64_t kv_row_stride) {
+                                int64_t kv_row_stride, const RowLens * row_lens) {
     const XLayout L = xattn_layout(n, H, T, scratch);
     *po = L.part_o; *pl = L.part_l; *pm = L.fused ? L.pmax : nullptr; *pns = L.ns;
     if (L.fused) {
         if (g_xattn_probe_skip & 1) return;
         auto kern = S <= 512 ? k_xattn_fused<1, true> : S <= 1024 ? k_xattn_fused<2, true> : k_xattn_fused<3, true>;      // S <= 1536
         hipLaunchKernelGGL(kern, xattn_grid(L.ns, H, n), dim3(256), 0, st, x32, ln_g, ln_b, eps, wq, bq, qscale, nullptr, S, kc, vc, T, L.ks, L.ns,
-                           L.pmax, L.part_o, L.part_l, kv_row_stride, xattn_head_major() ? 1 : 0, stamp_next());
+                           L.pmax, L.part_o, L.part_l, kv_row_stride, xattn_head_major() ? 1 : 0, stamp_next(), row_lens ? *row_lens : RowLens{});
         return;
     }
+    if (row_lens && row_lens->n) { fprintf(stderr, "attn_cross_qsplit_partials: per-row lengths need the one-launch form - nothing launched\n"); *po = *pl = *pm = nullptr; *pns = 0; return; }
     if (!(g_xattn_probe_skip & 1))
     {
         auto kern = S <= 512 ? k_xattn_qscores<1> : S <= 1024 ? k_xattn_qscores<2> : k_xattn_qscores<3>;      // S <= 1536
@@ -1178,6 +1199,8 @@ void attn_cross_qsplit_partials(const float * x32, const float * ln_g, const flo
     if (!(g_xattn_probe_skip & 2))
     hipLaunchKernelGGL(k_xattn_pv, dim3(L.ns, H, n), dim3(256), smem, st, vc, S, T, L.ks, L.ns, L.sc, L.ld_sc, L.pmax, L.part_o, L.part_l, kv_row_stride);
 }
+
+bool attn_cross_takes_row_lens(int H, int T) { return xattn_layout(1, H, T, nullptr).fused; }
 
 bool xback_usable(int S, int H, int T, int rows) {
     if (S > 512 || (S % 64) != 0 || H * 64 != S) return false;
@@ -1211,20 +1234,23 @@ static bool g_attn_one_group = false;
 void set_attn_one_group(bool on) { if (on != g_attn_one_group) bump_mode_epoch(); g_attn_one_group = on; }
 
 void attn_encoder(const __half * q, const __half * k, const __half * vt, int T, int Tpad, int S, int H, float scale,
-                  __half * out, hipStream_t st, int B, float * out32, int qk_chunk_rows) {
+                  __half * out, hipStream_t st, int B, float * out32, int qk_chunk_rows, const RowLens * row_lens, int out_chunk_rows) {
     const int qk_rows = qk_chunk_rows > 0 ? qk_chunk_rows : T;
+    const int out_rows = out_chunk_rows > 0 ? out_chunk_rows : T;
+    RowLens lens{};
+    if (row_lens && B > 1) lens = *row_lens;      // T = the largest of them: the grid and the split decisions below are taken once per launch
     // WMI_ATTN_FORM: 2 (default) = 32-row wavefronts, one sweep with a running maximum; 1 = the same kernel with the exact row
     // maximum found in a first sweep (the reference's soft-max argument); 0 = the round-1/2 kernel (16-row wavefronts, two sweeps)
     static const int form = getenv("WMI_ATTN_FORM") ? atoi(getenv("WMI_ATTN_FORM")) : 2;
     if (form >= 1 && scale == 0.125f && (Tpad % 64) == 0) {
         const bool split = ((T + 127) / 128) * H * B < 512 && T >= 512 && !g_attn_one_group;
-        attn_encoder2(q, k, vt, T, Tpad, S, H, out, st, B, out32, form == 2, split, qk_rows);
+        attn_encoder2(q, k, vt, T, Tpad, S, H, out, st, B, out32, form == 2, split, qk_rows, row_lens, out_rows);
         return;
     }
     const int nblk = ((T + 63) / 64) * H * B;
     const bool ks2 = nblk <= 512 && T >= 256 && !g_attn_one_group;
-    if (ks2) hipLaunchKernelGGL((k_attn_enc<4, 2>), dim3((T + 63) / 64, H, B), dim3(512), 0, st, q, k, vt, T, Tpad, S, scale, out, out32, qk_rows);
-    else     hipLaunchKernelGGL((k_attn_enc<4, 1>), dim3((T + 63) / 64, H, B), dim3(256), 0, st, q, k, vt, T, Tpad, S, scale, out, out32, qk_rows);
+    if (ks2) hipLaunchKernelGGL((k_attn_enc<4, 2>), dim3((T + 63) / 64, H, B), dim3(512), 0, st, q, k, vt, T, Tpad, S, scale, out, out32, qk_rows, out_rows, lens);
+    else     hipLaunchKernelGGL((k_attn_enc<4, 1>), dim3((T + 63) / 64, H, B), dim3(256), 0, st, q, k, vt, T, Tpad, S, scale, out, out32, qk_rows, out_rows, lens);
 }
 
 void attn_decoder(const __half * q, int n, int S, int H, const __half * kc, const __half * vc, int n_kv,

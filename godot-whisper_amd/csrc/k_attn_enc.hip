@@ -46,7 +46,8 @@ __device__ __forceinline__ float max3(float a, float b, float c) { float d; asm(
 template <int QW, int KS, bool ONE, int NST>
 __global__ __launch_bounds__(QW * KS * 64) void k_attn_enc2(const __half * __restrict__ q, const __half * __restrict__ k,
                                                             const __half * __restrict__ vt, int T, int Tpad, int S,
-                                                            __half * __restrict__ out, float * __restrict__ out32, int xcd_order, int qk_rows) {
+                                                            __half * __restrict__ out, float * __restrict__ out32, int xcd_order, int qk_rows,
+                                                            int out_rows, const RowLens lens) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     typedef float floatx16 __attribute__((ext_vector_type(16)));
     typedef float float2v __attribute__((ext_vector_type(2)));
@@ -74,11 +75,14 @@ __global__ __launch_bounds__(QW * KS * 64) void k_attn_enc2(const __half * __res
         wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx;
         bx = wg % gridDim.x; wg /= gridDim.x; head = wg % gridDim.y; bz = wg / gridDim.y;
     }
+    // chunks with a length of their own (RowLens): queries and keys of chunk bz stop at its T — from here on the kernel is the one-chunk
+    // launch at that length (same tiles, same tail handling); a workgroup whose query rows all lie behind it leaves before the first barrier
+    if (lens.n) { T = lens.t[bz]; if (bx * (QW * 32) >= T) return; }
     const int q0 = bx * (QW * 32) + qw * 32;
     {
         const size_t zb = bz;
         q += zb * (size_t) qk_rows * S; k += zb * (size_t) qk_rows * S; vt += zb * (size_t) S * Tpad;
-        if (out32) out32 += zb * (size_t) T * S; else out += zb * (size_t) T * S;
+        if (out32) out32 += zb * (size_t) out_rows * S; else out += zb * (size_t) out_rows * S;
     }
     unsigned char * const ring = smem + grp * (NST * STAGE);
     const uint32_t ring_lds = lds_addr(ring);
@@ -346,7 +350,7 @@ __global__ __launch_bounds__(QW * KS * 64) void k_attn_enc2(const __half * __res
 
 template <int QW, int KS, bool ONE, int NST>
 void launch_attn_enc2(const __half * q, const __half * k, const __half * vt, int T, int Tpad, int S, int H, __half * out,
-                      hipStream_t st, int B, float * out32, int qk_rows) {
+                      hipStream_t st, int B, float * out32, int qk_rows, int out_rows, const RowLens & lens) {
     static std::atomic<uint64_t> lds_ok{0};
     constexpr size_t ring = (size_t) KS * NST * 16384;
     constexpr size_t extra = (!ONE && KS > 1) ? (size_t) KS * QW * 32 * 4 : 0;
@@ -360,23 +364,26 @@ void launch_attn_enc2(const __half * q, const __half * k, const __half * vt, int
     static_assert(smem <= 160 * 1024, "LDS");
     if (smem > 48 * 1024) allow_full_lds((const void *) k_attn_enc2<QW, KS, ONE, NST>, lds_ok);
     hipLaunchKernelGGL((k_attn_enc2<QW, KS, ONE, NST>), dim3((T + QW * 32 - 1) / (QW * 32), H, B), dim3(QW * KS * 64), smem, st,
-                       q, k, vt, T, Tpad, S, out, out32, xcd_order, qk_rows);
+                       q, k, vt, T, Tpad, S, out, out32, xcd_order, qk_rows, out_rows, lens);
 }
 
 }  // namespace
 
 
 void attn_encoder2(const __half * q, const __half * k, const __half * vt, int T, int Tpad, int S, int H, __half * out, hipStream_t st,
-                   int B, float * out32, bool one_sweep, bool split, int qk_chunk_rows) {
+                   int B, float * out32, bool one_sweep, bool split, int qk_chunk_rows, const RowLens * row_lens, int out_chunk_rows) {
     const int qk_rows = qk_chunk_rows > 0 ? qk_chunk_rows : T;
+    const int out_rows = out_chunk_rows > 0 ? out_chunk_rows : T;
+    RowLens lens{};
+    if (row_lens && B > 1) lens = *row_lens;
     // one key group wherever the result must not depend on how many chunks share the launch (lock-step "exact" mode) and
     // wherever the grid fills the chip by itself; four key groups of two wavefronts for one or two chunks (the measured best)
     if (split) {
-        if (one_sweep) launch_attn_enc2<2, 4, true, 2>(q, k, vt, T, Tpad, S, H, out, st, B, out32, qk_rows);
-        else           launch_attn_enc2<2, 4, false, 2>(q, k, vt, T, Tpad, S, H, out, st, B, out32, qk_rows);
+        if (one_sweep) launch_attn_enc2<2, 4, true, 2>(q, k, vt, T, Tpad, S, H, out, st, B, out32, qk_rows, out_rows, lens);
+        else           launch_attn_enc2<2, 4, false, 2>(q, k, vt, T, Tpad, S, H, out, st, B, out32, qk_rows, out_rows, lens);
     } else {
-        if (one_sweep) launch_attn_enc2<4, 1, true, 2>(q, k, vt, T, Tpad, S, H, out, st, B, out32, qk_rows);
-        else           launch_attn_enc2<4, 1, false, 2>(q, k, vt, T, Tpad, S, H, out, st, B, out32, qk_rows);
+        if (one_sweep) launch_attn_enc2<4, 1, true, 2>(q, k, vt, T, Tpad, S, H, out, st, B, out32, qk_rows, out_rows, lens);
+        else           launch_attn_enc2<4, 1, false, 2>(q, k, vt, T, Tpad, S, H, out, st, B, out32, qk_rows, out_rows, lens);
     }
 }
 

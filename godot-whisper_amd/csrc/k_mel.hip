@@ -280,6 +280,7 @@ __global__ void k_mel_slice_batch(const MelSliceBatch mb, int n_mel, int n_frame
     __shared__ float tile[32][33];
     const int ch = blockIdx.z;
     const float * __restrict__ mel = mb.mel[ch]; const int n_len = mb.n_len[ch], offset = mb.offset[ch];
+    if (mb.n_frames[ch] > 0) n_frames = mb.n_frames[ch];        // a chunk with an encoder length of its own: the rows behind its frames are zero
     out += (size_t) ch * rows_total * ld;
     const int r0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
@@ -300,6 +301,12 @@ __global__ void k_mel_slice_batch(const MelSliceBatch mb, int n_mel, int n_frame
 __global__ void k_fill_zero_strided(uint32_t * p, size_t words, size_t stride_words, int count) {
     const size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
     if (i < words && (int) blockIdx.y < count) p[(size_t) blockIdx.y * stride_words + i] = 0u;
+}
+
+// run c: zeros in words [first.t[c] * row_words, end_words) behind p + c * stride_words
+__global__ void k_fill_zero_tails(uint32_t * p, const RowLens first, size_t row_words, size_t end_words, size_t stride_words) {
+    const size_t c = blockIdx.y, beg = (size_t) first.t[c] * row_words;
+    for (size_t i = beg + (size_t) blockIdx.x * blockDim.x + threadIdx.x; i < end_words; i += (size_t) gridDim.x * blockDim.x) p[c * stride_words + i] = 0u;
 }
 
 // mean |x| over a (2 hw + 1)-sample window, summed left to right with the reference's exact arithmetic
@@ -508,6 +515,10 @@ void mel_slice(const float * mel, int n_len, int n_mel, int offset, int n_frames
 void mel_slice_batch(const MelSliceBatch & mb, int nb, int n_mel, int n_frames, __half * out, int ld, int rows_total, hipStream_t st) {
     dim3 grid((rows_total + 31) / 32, (ld + 31) / 32, nb);
     hipLaunchKernelGGL(k_mel_slice_batch, grid, dim3(256), 0, st, mb, n_mel, n_frames, out, ld, rows_total);
+}
+void fill_zero_tails(void * p, const RowLens & first_row, size_t row_bytes, size_t end_bytes, size_t stride_bytes, int count, hipStream_t st) {
+    if (count <= 0 || count > 16) return;
+    hipLaunchKernelGGL(k_fill_zero_tails, dim3(64, count), dim3(256), 0, st, (uint32_t *) p, first_row, row_bytes / 4, end_bytes / 4, stride_bytes / 4);
 }
 void fill_zero_strided(void * p, size_t bytes, size_t stride_bytes, int count, hipStream_t st) {
     if (count <= 0 || bytes == 0) return;

@@ -102,9 +102,16 @@ void signal_energy_batch(const MelBatch & b, int nb, int hw, hipStream_t st);
 // token-major f16 slice for the conv front-end: out[r][c], r in [0, rows_total), row r holds frame
 // (offset + r - 1); rows outside [1, n_frames] and frames >= n_len are zero.
 // lock-step chunks: the slices of up to 16 chunks in one launch (chunk c -> rows c * rows_total ..), and the guard rows between stacked chunks
-struct MelSliceBatch { const float * mel[16]; int n_len[16]; int offset[16]; };
+struct MelSliceBatch { const float * mel[16]; int n_len[16]; int offset[16];
+                       int n_frames[16]; };                  // > 0: chunk c takes that many frames (an encoder length of its own), 0: the launch's n_frames
 void mel_slice_batch(const MelSliceBatch & mb, int nb, int n_mel, int n_frames, __half * out, int ld, int rows_total, hipStream_t st);
 void fill_zero_strided(void * p, size_t bytes, size_t stride_bytes, int count, hipStream_t st);
+// Lock-step chunks with an encoder length of their own (batch.cpp encode_rows): t[z] = encoder length of chunk row z.  n = 0: every
+// chunk has the launch's common length (the kernels then are what they were).  Passed by value: no allocation, nothing for a replay to miss.
+struct RowLens { int n; int t[16]; };
+// zeros with a start of its own per run: run c (< count <= 16) zeroes p + c * stride_bytes + [first_row.t[c] * row_bytes, end_bytes) — the conv1
+// rows behind each chunk's own 2 T + 1 rows, up to and including the next chunk's guard row
+void fill_zero_tails(void * p, const RowLens & first_row, size_t row_bytes, size_t end_bytes, size_t stride_bytes, int count, hipStream_t st);
 void mel_slice(const float * mel, int n_len, int n_mel, int offset, int n_frames, __half * out, int ld,
                int rows_total, hipStream_t st);
 
@@ -185,6 +192,7 @@ struct GemmArgs {
     int     S;                      // split width for the QKV / cross epilogues
     int64_t layer_stride;           // EPI_CROSS_KV: elements between layers in the cross cache
     int     rows_per_chunk;         // EPI_QKV_ENC, batched encode: M = chunks * rows_per_chunk (0: one chunk)
+    int     conv2_out_rows;         // EPI_CONV2 with rows_per_chunk: rows between the chunks of the output (0: rows_per_chunk - 4, back to back)
     int64_t chunk_stride_aux2;      //   elements between the chunks' V^T images
     int     no_glds;                // debug: keep 128x128 tiles on the register-staged loop
     unsigned long long * probe;     // probe (wmi_bench_kernel 7): per workgroup {entry, first tile landed, K loop done, epilogue done, SE/CU id}
@@ -213,10 +221,12 @@ void layernorm(const float * x, int rows, int S, const float * g, const float * 
 // f32 tensor directly, as the reference does); same for the decoder kernels below
 // second form (k_attn_enc.hip): 32-row wavefronts; one_sweep = running maximum, else exact maximum first; split = four key groups
 void attn_encoder2(const __half * q, const __half * k, const __half * vt, int T, int Tpad, int S, int H, __half * out, hipStream_t st,
-                   int B, float * out32, bool one_sweep, bool split, int qk_chunk_rows = 0);
+                   int B, float * out32, bool one_sweep, bool split, int qk_chunk_rows = 0, const RowLens * row_lens = nullptr, int out_chunk_rows = 0);
 void attn_encoder(const __half * q, const __half * k, const __half * vt, int T, int Tpad, int S, int H,
                   float scale, __half * out, hipStream_t st, int B = 1, float * out32 = nullptr,
-                  int qk_chunk_rows = 0);     // rows between the chunks of q and k (0 = T; lock-step chunks start on 16-row boundaries, batch.cpp)
+                  int qk_chunk_rows = 0,      // rows between the chunks of q and k (0 = T; lock-step chunks start on 16-row boundaries, batch.cpp)
+                  const RowLens * row_lens = nullptr,   // B > 1: chunk z attends row_lens->t[z] queries and keys (T = the largest: grid and key split are
+                  int out_chunk_rows = 0);              // decided once per launch by it); out_chunk_rows: rows between the chunks of out (0 = T)
 // decoder: one (token, head) per workgroup.  kc/vc: [n_kv][S] caches (this layer), mask: [n][ld_mask] or null
 void attn_decoder(const __half * q, int n, int S, int H, const __half * kc, const __half * vc, int n_kv,
                   const float * mask, int ld_mask, __half * out, hipStream_t st,
@@ -229,7 +239,10 @@ void attn_cross_split(const __half * q, int n, int S, int H, const __half * kc, 
 // same without the combine launch: the consumer GEMV combines the partials in its prologue (GemvArgs::comb_*)
 void attn_cross_split_partials(const __half * q, int n, int S, int H, const __half * kc, const __half * vc, int T,
                                float * scratch, const float ** part_o, const float ** part_l, const float ** part_m, int * ns, hipStream_t st,
-                               int64_t kv_row_stride = 0);   // row i reads kc/vc + i * kv_row_stride (lock-step chunks)
+                               int64_t kv_row_stride = 0,    // row i reads kc/vc + i * kv_row_stride (lock-step chunks)
+                               const RowLens * row_lens = nullptr);   // one-launch form only: row i attends row_lens->t[i] keys in the slices the one-row path
+                                                             // takes at that length; T = the largest (layout, grid); slices a row does not have write neutral
+                                                             // partials (m = -inf, l = 0, o = 0), which the consumers' combine passes over bit for bit
 // part_m: null when the partials are relative to the row's global maximum (two-launch form), else the slice maxima the
 // consumer rescales by (one-launch form, k_xattn_fused) — pass it on as GemvArgs::comb_m / to attn_cross_combine
 // the same with the query projection folded into the score kernel: q = (W_cq . LN(x32) + b_cq) * qscale is recomputed per
@@ -241,7 +254,8 @@ XattnPlan attn_cross_plan(int n, int H, int T, float * scratch);
 void attn_cross_qsplit_partials(const float * x32, const float * ln_g, const float * ln_b, float eps, const __half * wq,
                                 const float * bq, float qscale, int n, int S, int H, const __half * kc, const __half * vc, int T,
                                 float * scratch, const float ** part_o, const float ** part_l, const float ** part_m, int * ns, hipStream_t st,
-                                int64_t kv_row_stride = 0);
+                                int64_t kv_row_stride = 0, const RowLens * row_lens = nullptr);
+bool attn_cross_takes_row_lens(int H, int T);      // is the form the two functions above launch at T the one-launch form (the only one with row_lens)?
 size_t attn_cross_scratch_floats(int n, int H, int T);
 
 // ---------------------------------------------------------------- decoder small-batch (k_dec.hip)

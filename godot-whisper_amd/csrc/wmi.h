@@ -302,11 +302,12 @@ struct BatchWork {
     // granules of the one-launch front of a layer for lock-step rows (k::front, rows on grid.y): [B][2 S] granules, then 16 words
     // ([0], [1] the launches' tags, [4] the hand-offs' status); front_off: a hand-off failed once, the two launches from then on
     void   * front_hand = nullptr; bool front_off = false; int front_fallbacks = 0, front_backoff = 0;
-    int      enc_rows = 0, enc_T = 0;                         // chunk rows / encoder length of the last batched encode
+    int      enc_rows = 0, enc_T = 0;                         // chunk rows / rows between consecutive chunks (the row period) of the last batched encode
+    int      enc_Tmax = 0, enc_row_T[16] = {}; bool enc_ragged = false;   // its longest row, every row's own encoder length, and whether they differ
     int32_t  step_seq = 0;                                    // sequence number of the last lock-step decode step
     // the lock-step step as a captured graph, keyed by what its launches depend on (rows, encoder length, chunk rows of the cross
     // cache); eager until the same key has been decoded for a while (capture + instantiate cost more than a window's steps)
-    struct RowsGraph { hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; int nb = -1, T = -1, rows = -1, epoch = -1, seen = 0; bool failed = false; } rows_graph[4];   // [chained + 2 * fronted (the front of the layers as one launch, k::front)]
+    struct RowsGraph { hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; int nb = -1, T = -1, rows = -1, epoch = -1, seen = 0; bool failed = false; int row_T[16] = {}; bool ragged = false; } rows_graph[4];   // [chained + 2 * fronted (the front of the layers as one launch, k::front)]
     // chained steps: the pick kernel of a step leaves every row's next token, position and cache head in step_dev and the next
     // activation row in dx (as the one-row greedy step does, DeviceState::chain_*); a step whose host records say the same for
     // every row starts without the embedding launch (which reads the records over PCIe in front of everything else)
@@ -404,7 +405,7 @@ bool pcm_to_mel_batch(whisper_context & ctx, const std::vector<State *> & states
 bool set_mel(whisper_context & ctx, const float * data, int n_len, int n_mel);
 bool encode(whisper_context & ctx, int mel_offset, bool defer = false);
 // lock-step chunks (batch.cpp): rows[r] = lane whose mel feeds chunk row r, seek[r] = its mel frame offset
-bool encode_rows(whisper_context & ctx, const std::vector<int> & rows, const std::vector<int> & seek, int audio_ctx);
+bool encode_rows(whisper_context & ctx, const std::vector<int> & rows, const std::vector<int> & seek, int audio_ctx, const int * row_ctx = nullptr);
 // lang_logits (one token): the language head instead of the vocabulary projection — k::LANG_HEAD_N logits go to lang_logits, st.logits is left alone
 bool decode(whisper_context & ctx, const Batch & batch, float * lang_logits = nullptr);
 // block-quantised models (device_q.cpp): the layer loops of encode() / decode() with the quantised kernels
@@ -492,7 +493,11 @@ int  lang_detect_head(whisper_context & ctx, int offset_ms, float * lang_probs, 
 int  lang_probs_from_logits(const float * logits, float * lang_probs);       // k::LANG_HEAD_N logits -> id, probabilities (lang_probs may be null)
 int  full(whisper_context & ctx, whisper_full_params params, const float * samples, const float * d_samples, int n_samples);
 // several independent chunks in lock-step (batch.cpp); results per chunk in ctx.batch->results
-int  full_batch(whisper_context & ctx, whisper_full_params params, const float * const * pcm, const int * n_samples, int n_chunks, bool on_device);
+// the per-chunk encoder lengths of wmi_full_batch_ctx / wmi_capture_full_batch: 0, -1 for a negative entry, -5 (with whisper_full's message)
+// for one above the model's n_audio_ctx.  No device work.
+int  check_audio_ctxs(const whisper_context & ctx, const int * audio_ctx, int n, const char * who);
+int  full_batch(whisper_context & ctx, whisper_full_params params, const float * const * pcm, const int * n_samples, int n_chunks, bool on_device,
+                const int * audio_ctx = nullptr);       // audio_ctx: an encoder length per chunk (0 = the model's) instead of params.audio_ctx
 void free_batch(whisper_context & ctx);
 int  ensure_replicas(whisper_context & ctx, int n);     // create up to n replica contexts now; returns how many exist (<= n)
 void trim_replicas(whisper_context & ctx, int keep);         // release the replicas beyond `keep` (states, streams back to the pool)

@@ -114,12 +114,14 @@ class SpeechToText:
 
     # -- several independent buffers at once (product library only: include/wmi_device.h wmi_full_batch).  The
     #    reference host has no such call; the semantics are "transcribe() of each buffer, on a fresh context".
+    #    audio_ctxs: an encoder length per buffer (wmi_full_batch_ctx) instead of the common audio_ctx.
     def transcribe_batch(self, buffers: list, initial_prompt: str = "", audio_ctx: int = 0, params=None,
-                         device_ptrs: list | None = None) -> list:
+                         device_ptrs: list | None = None, audio_ctxs: list | None = None) -> list:
         if not self.ctx:
             return []
         p = params if params is not None else self.full_params(initial_prompt, audio_ctx)
         n = len(buffers)
+        assert audio_ctxs is None or len(audio_ctxs) == n, (n, audio_ctxs)
         if device_ptrs is None:
             bufs = [np.ascontiguousarray(b, dtype=np.float32) for b in buffers]
             ptrs = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
@@ -129,10 +131,17 @@ class SpeechToText:
             ptrs = (C.c_void_p * n)(*device_ptrs)
             lens = (C.c_int * n)(*[int(b) for b in buffers])          # sample counts
             on_dev = 1
-        ret = self.lib.wmi_full_batch(self.ctx, p, ptrs, lens, n, on_dev)
+        if audio_ctxs is None:
+            ret = self.lib.wmi_full_batch(self.ctx, p, ptrs, lens, n, on_dev)
+        else:
+            ret = self.lib.wmi_full_batch_ctx(self.ctx, p, ptrs, lens, (C.c_int * n)(*[int(a) for a in audio_ctxs]), n, on_dev)
         self.last_ret = ret
         if ret != 0:
             return []
+        return self.collect_batch(n)
+
+    def collect_batch(self, n: int) -> list:
+        """The n results of the last lock-step call (wmi_batch_select), and last_modes / last_langs."""
         out = []
         self.last_modes = []
         self.last_langs = []                                          # per chunk: the language id whisper_full would report (detected with "auto")
@@ -272,6 +281,16 @@ class CaptureSession:
         assert self.lib.wmi_capture_stats(self.cap, out) == 0
         return tuple(int(v) for v in out)
 
+    @staticmethod
+    def full_batch(sessions: list, params, audio_ctxs: list | None = None) -> int:
+        """wmi_capture_full_batch: the transcribe step of several sessions of one node in lock-step; results through
+        node.collect_batch(len(sessions))."""
+        n = len(sessions)
+        caps = (C.c_void_p * max(n, 1))(*[s.cap for s in sessions])
+        ctxs = (C.c_int * n)(*[int(a) for a in audio_ctxs]) if audio_ctxs is not None else None
+        lib = sessions[0].lib if n else None
+        return lib.wmi_capture_full_batch(caps, n, params, ctxs) if lib else -1
+
 
 class AudioStreamToText(SpeechToText):
     """addon/audio_stream_to_text.gd: one-shot "transcribe this WAV" node."""
@@ -351,14 +370,15 @@ class CaptureStreamToText(SpeechToText):
 
     def stream_capture(self, frames_xy: np.ndarray, mix_rate: int, interpolator_type: int = 2, max_calls: int | None = None,
                        use_session: bool = True, minimum_sentence_time: float = 3, maximum_sentence_time: float = 15,
-                       hallucinating_count: int = 1):
+                       hallucinating_count: int = 1, temperature_inc: float | None = None):
         """transcribe_thread (addon/capture_stream_to_text.gd:69-120) over pre-recorded stereo capture frames at `mix_rate`: every pass
         appends `interval` seconds of frames, resamples the whole accumulation, runs the VAD and transcribes with the node's
         parameters and audio_ctx = total_time * 1500 / 30 + 128.  Yields, per transcribe call,
         (finish_sentence, text, n_samples_used, audio_ctx, token dicts, no_activity); as in the node, a pass with no_activity neither
         ends the sentence nor updates the token count, and a finished sentence keeps the last 0.2 * mix_rate frames.
         use_session: the capture session (device-resident frames and PCM), else the same loop over resample() /
-        voice_activity_detection() / transcribe() on host arrays — the same tuples either way."""
+        voice_activity_detection() / transcribe() on host arrays — the same tuples either way.
+        temperature_inc (tests): replaces the node's default in the parameters of every call (0.0 = no temperature fallback)."""
         xy = np.ascontiguousarray(frames_xy, dtype=np.float32).reshape(-1, 2)
         sr = abi.WHISPER_SAMPLE_RATE
         step = max(int(round(self.interval * mix_rate)), 1)
@@ -384,11 +404,14 @@ class CaptureStreamToText(SpeechToText):
                     no_activity = self.voice_activity_detection(resampled)
                 total_time = size / sr
                 audio_ctx = min(int(total_time * 1500 / 30 + 128), 1500)            # :84
+                p = self.full_params("", audio_ctx)
+                if temperature_inc is not None:
+                    p.temperature_inc = float(temperature_inc)
                 if sess:
-                    self.last_ret = sess.full(self.full_params("", audio_ctx))
+                    self.last_ret = sess.full(p)
                     tokens = self.collect() if self.last_ret == 0 else []
                 else:
-                    tokens = self.transcribe(resampled, "", audio_ctx)
+                    tokens = self.transcribe(resampled, "", audio_ctx, params=p)
                 calls += 1
                 if not tokens:
                     return                                                          # push_warning("No tokens generated") (:88-90)
@@ -413,3 +436,74 @@ class CaptureStreamToText(SpeechToText):
         finally:
             if sess:
                 sess.close()
+
+    def stream_capture_many(self, streams: list, mix_rates: list, interpolator_type: int = 2, max_calls: int | None = None,
+                            minimum_sentence_time: float = 3, maximum_sentence_time: float = 15, hallucinating_count: int = 1,
+                            temperature_inc: float | None = None):
+        """stream_capture's loop for several pre-recorded speakers on ONE node, one capture session each: every pass pushes `interval`
+        seconds of each speaker's frames, resamples and runs the VAD per session, then transcribes the sessions that hold at least one
+        output sample with ONE wmi_capture_full_batch, each at the node's audio_ctx = total_time * 1500 / 30 + 128.  Yields
+        (speaker, finish_sentence, text, n_samples_used, audio_ctx, token dicts, no_activity) — per speaker the tuples stream_capture
+        yields for that speaker alone; keep_last and the token count are kept per speaker.  A speaker whose frames are used up (or who
+        produced no tokens, where stream_capture returns) drops out of later passes; max_calls counts passes with a transcription.
+        temperature_inc as in stream_capture.  self.pass_modes collects, per pass, wmi_batch_chunk_mode of its sessions (0 = lock-step row,
+        1 = the session asked for the temperature fallback and was run alone)."""
+        self.pass_modes = []
+        xys = [np.ascontiguousarray(f, dtype=np.float32).reshape(-1, 2) for f in streams]
+        n = len(xys)
+        assert len(mix_rates) == n
+        sr = abi.WHISPER_SAMPLE_RATE
+        steps = [max(int(round(self.interval * r)), 1) for r in mix_rates]
+        vad_thold = float(self.settings["audio/input/transcribe/vad_treshold"])
+        freq_thold = float(self.settings["audio/input/transcribe/freq_treshold"])
+        sessions = [CaptureSession(self, r, interpolator_type, frames_hint=int(maximum_sentence_time * r)) for r in mix_rates]
+        try:
+            pos, last_token_count, live = [0] * n, [0] * n, [True] * n
+            calls = 0
+            while any(live[i] and pos[i] < xys[i].shape[0] for i in range(n)):
+                ready = []                                                          # (speaker, size, no_activity, audio_ctx)
+                for i in range(n):
+                    if not live[i] or pos[i] >= xys[i].shape[0]:
+                        continue
+                    new = xys[i][pos[i]:pos[i] + steps[i]]
+                    pos[i] += new.shape[0]
+                    sessions[i].push(new)
+                    size, _ = sessions[i].resample()
+                    if size <= 0:
+                        continue
+                    no_activity = bool(sessions[i].vad(vad_thold, freq_thold))
+                    total_time = size / sr
+                    ready.append((i, size, no_activity, min(int(total_time * 1500 / 30 + 128), 1500)))
+                if not ready:
+                    continue
+                # (one parameter block for the pass: the speakers differ in audio_ctx only, which travels per session)
+                p = self.full_params("", 0)
+                if temperature_inc is not None:
+                    p.temperature_inc = float(temperature_inc)
+                self.last_ret = CaptureSession.full_batch([sessions[i] for i, _, _, _ in ready], p, [a for _, _, _, a in ready])
+                results = self.collect_batch(len(ready)) if self.last_ret == 0 else [[] for _ in ready]
+                if self.last_ret == 0:
+                    self.pass_modes.append(list(self.last_modes))
+                calls += 1
+                for (i, size, no_activity, audio_ctx), tokens in zip(ready, results):
+                    if not tokens:
+                        live[i] = False                                             # push_warning("No tokens generated") (:88-90)
+                        continue
+                    total_time = size / sr
+                    full_text = tokens.pop(0).decode("utf-8", errors="replace")
+                    finish = total_time > maximum_sentence_time
+                    text = remove_special_characters("".join(t["text"].decode("utf-8", errors="replace") for t in tokens))
+                    if any(ch in text for ch in self.punct) or no_activity:
+                        finish = True
+                    if total_time < minimum_sentence_time or abs(len(tokens) - last_token_count[i]) > hallucinating_count:
+                        finish = False
+                    yield i, finish, full_text, size, audio_ctx, list(tokens), no_activity
+                    if not no_activity:
+                        if finish:
+                            sessions[i].keep_last(int(0.2 * mix_rates[i]))
+                        last_token_count[i] = len(tokens)
+                if max_calls is not None and calls >= max_calls:
+                    return
+        finally:
+            for s in sessions:
+                s.close()

@@ -24,6 +24,9 @@ DEVICE_API = [
     ("wmi_pcm_to_mel_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     ("wmi_full_device_pcm", C.c_int, [C.c_void_p, abi.whisper_full_params, C.c_void_p, C.c_int, C.POINTER(C.c_float)]),
     ("wmi_full_batch", C.c_int, [C.c_void_p, abi.whisper_full_params, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_int, C.c_int]),
+    ("wmi_full_batch_ctx", C.c_int, [C.c_void_p, abi.whisper_full_params, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                     C.c_int, C.c_int]),
+    ("wmi_batch_enc_dims", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("wmi_set_lockstep_exact", None, [C.c_int]),
     ("wmi_batch_select", C.c_int, [C.c_void_p, C.c_int]),
     ("wmi_batch_chunk_mode", C.c_int, [C.c_void_p, C.c_int]),
@@ -79,6 +82,7 @@ DEVICE_API = [
     ("wmi_capture_read_pcm", C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     ("wmi_capture_vad", C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_void_p]),
     ("wmi_capture_full", C.c_int, [C.c_void_p, abi.whisper_full_params]),
+    ("wmi_capture_full_batch", C.c_int, [C.POINTER(C.c_void_p), C.c_int, abi.whisper_full_params, C.POINTER(C.c_int)]),
     ("wmi_capture_stats", C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     ("wmi_selftest_capture_plan", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong),
                                             C.POINTER(C.c_longlong)]),

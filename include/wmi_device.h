@@ -157,6 +157,12 @@ WHISPER_API int           wmi_capture_read_pcm(struct wmi_capture * cap, float *
 WHISPER_API int           wmi_capture_vad(struct wmi_capture * cap, float vad_thold, float freq_thold, float * energies);
 WHISPER_API int           wmi_capture_full(struct wmi_capture * cap, struct whisper_full_params params);
 WHISPER_API int           wmi_capture_stats(struct wmi_capture * cap, int64_t * out4);
+/* The transcribe step of several capture sessions of ONE context in lock-step: brings every session's PCM up to date, then
+ * wmi_full_batch_ctx over the sessions' device PCM.  Results per session index through wmi_batch_select & co.
+ * audio_ctx[i] (NULL: params.audio_ctx for all) is session i's encoder length, e.g. the node's total_time * 50 + 128.  The call takes the
+ * context's lock once and copies no PCM: it hands on the pointers wmi_capture_pcm returns.  -1 for n <= 0, a NULL session or sessions of
+ * different contexts; -3 when a session is empty (as wmi_full_batch for an empty chunk), before any device work; else wmi_full_batch_ctx's codes. */
+WHISPER_API int           wmi_capture_full_batch(struct wmi_capture * const * caps, int n, struct whisper_full_params params, const int * audio_ctx);
 /* Host half of the session's incremental resample (no device needed): for an accumulation that grew from n_old to n_new frames at
  * src_rate -> 16 kHz, the first output the session recomputes (outputs below it are the same bytes for both inputs; 0 = everything, e.g.
  * at rates without a closed form) and the frame counts of both plans.  Returns 0, -1 bad arguments, or the converter error of the new plan. */
@@ -190,6 +196,24 @@ WHISPER_API int wmi_selftest_vad(struct whisper_context * ctx, const float * pcm
  * pcm[c] are host pointers, or device pointers when pcm_on_device != 0.  Returns whisper_full's codes. */
 WHISPER_API int wmi_full_batch(struct whisper_context * ctx, struct whisper_full_params params, const float * const * pcm,
                                const int * n_samples, int n_chunks, int pcm_on_device);
+/* wmi_full_batch with an encoder length per chunk: chunk c is transcribed as whisper_full with params.audio_ctx = audio_ctx[c]
+ * on a fresh context (0 = the model's n_audio_ctx).  audio_ctx == NULL: params.audio_ctx for every chunk (= wmi_full_batch).
+ * The chunks still share every launch: the rows of a group are stacked with a common row period (the group's largest length rounded up
+ * to 16), and the kernels that must know a row's own length — mel slice, conv guard rows, encoder attention, decoder cross-attention —
+ * take the lengths by value; each row's cross-attention uses the key slices the one-chunk path takes at its length.  The call orders its
+ * lock-step chunks by length (longest first) before dealing them into groups of 16 and into wmi_set_lockstep_groups ranges, and reports
+ * results in the caller's order; in the exact mode (wmi_set_lockstep_exact) a chunk's result does not depend on that order, on the other
+ * chunks or on the grouping, and equals whisper_full's bit for bit.  With lengths given, a single chunk runs in lock-step form too.
+ * Block-quantised models (and the two-launch cross-attention, WMI_XATTN_TWO_PASS) carry ONE length per launch: there the ordered chunks
+ * are cut into sets of equal length and each set is a lock-step call of its own — same results, launches shared within a set only;
+ * wmi_get_batch_timings then reports the sums over the sets.
+ * Any entry above the model's n_audio_ctx: -5 (whisper_full's message); a negative entry: -1; both before any device work. */
+WHISPER_API int wmi_full_batch_ctx(struct whisper_context * ctx, struct whisper_full_params params, const float * const * pcm,
+                                   const int * n_samples, const int * audio_ctx, int n_chunks, int pcm_on_device);
+/* Layout of the last batched encoder pass, for the stage tests: rows, the row period of "batch_enc_x" / "batch_cross_k" / "batch_cross_v"
+ * (rows between consecutive chunks; = the common T for a uniform call), and each row's own encoder length into row_T[0 .. rows).
+ * Any pointer may be NULL.  -1 when there has been no such pass. */
+WHISPER_API int wmi_batch_enc_dims(struct whisper_context * ctx, int * rows, int * row_period, int * row_T);
 /* Lock-step projections run on the matrix cores by default (f32 sums in MFMA order), and a one-chunk encoder splits
  * the attention keys over two wavefront groups (partial sums added at the end).  on != 0 keeps the projections on the
  * weight-streaming VALU kernel and the attention on one group for every batch size: wmi_full_batch and whisper_full
