@@ -1032,6 +1032,78 @@ int wmi_selftest_quant(int device, int qtype, int mode, const void * w_blocks, c
     return ok ? 0 : -3;
 }
 
+int wmi_selftest_attn_encoder(int device, int B, int T, int Tpad, int S, int H, int qk_rows, int out_rows, const int32_t * row_T,
+                              int want_f32, int form, int groups, const uint16_t * q, const uint16_t * k, const uint16_t * v,
+                              uint32_t sentinel, void * out) {
+    // everything the product cannot launch is refused before the device is touched
+    if (B < 1 || B > 16 || T < 1 || H < 1 || S != 64 * H || Tpad < T || (Tpad % 64) != 0 || qk_rows < T || out_rows < T) return -1;
+    if (form < 0 || form > 2 || groups < -1 || groups > 1 || !q || !k || !v || !out) return -1;
+    if (row_T) for (int b = 0; b < B; ++b) if (row_T[b] < 1 || row_T[b] > T) return -1;
+    if (groups == 1 && T < (form == 0 ? 256 : 512)) return -1;
+    if (!HIP_OK(hipSetDevice(device))) return -2;
+    const size_t n_qk = (size_t) B * qk_rows * S, n_vt = (size_t) B * S * Tpad, n_out = (size_t) B * out_rows * S;
+    const size_t out_bytes = n_out * (want_f32 ? 4 : 2);
+    // V^T [B][S][Tpad] from the time-major v, with the one definition of the time order the q|k|v epilogue shares (kernels.h: vt_pos)
+    std::vector<uint16_t> vt(n_vt);
+    for (int b = 0; b < B; ++b)
+        for (int t = 0; t < Tpad; ++t)
+            for (int c = 0; c < S; ++c) vt[((size_t) b * S + c) * Tpad + k::vt_pos(t)] = v[((size_t) b * Tpad + t) * S + c];
+    std::vector<unsigned char> pre(out_bytes);
+    if (want_f32) for (size_t i = 0; i < n_out; ++i) memcpy(pre.data() + 4 * i, &sentinel, 4);
+    else { const uint16_t s16 = (uint16_t) sentinel; for (size_t i = 0; i < n_out; ++i) memcpy(pre.data() + 2 * i, &s16, 2); }
+    k::RowLens lens{};
+    if (row_T) { lens.n = B; for (int b = 0; b < B; ++b) lens.t[b] = row_T[b]; }
+    __half * d_q = nullptr, * d_k = nullptr, * d_vt = nullptr; unsigned char * d_o = nullptr;
+    hipStream_t st = nullptr;
+    bool ok = HIP_OK(hipMalloc((void **) &d_q, n_qk * 2)) && HIP_OK(hipMalloc((void **) &d_k, n_qk * 2)) &&
+              HIP_OK(hipMalloc((void **) &d_vt, n_vt * 2)) && HIP_OK(hipMalloc((void **) &d_o, out_bytes)) && HIP_OK(hipStreamCreate(&st));
+    ok = ok && HIP_OK(hipMemcpy(d_q, q, n_qk * 2, hipMemcpyHostToDevice)) && HIP_OK(hipMemcpy(d_k, k, n_qk * 2, hipMemcpyHostToDevice)) &&
+         HIP_OK(hipMemcpy(d_vt, vt.data(), n_vt * 2, hipMemcpyHostToDevice)) && HIP_OK(hipMemcpy(d_o, pre.data(), out_bytes, hipMemcpyHostToDevice));
+    if (ok) {
+        const bool split = groups < 0 ? k::attn_encoder_splits(form, T, Tpad, H, 0.125f, B) : groups == 1;
+        k::attn_encoder_form(d_q, d_k, d_vt, T, Tpad, S, H, 0.125f, want_f32 ? nullptr : (__half *) d_o, st, B, want_f32 ? (float *) d_o : nullptr,
+                             qk_rows, row_T ? &lens : nullptr, out_rows, form, split);
+        ok = HIP_OK(hipStreamSynchronize(st)) && HIP_OK(hipGetLastError());
+        ok = ok && HIP_OK(hipMemcpy(out, d_o, out_bytes, hipMemcpyDeviceToHost));
+    }
+    if (st) (void) hipStreamDestroy(st);
+    (void) hipFree(d_q); (void) hipFree(d_k); (void) hipFree(d_vt); (void) hipFree(d_o);
+    return ok ? 0 : -3;
+}
+
+int wmi_selftest_qkv_encoder(int device, int M, int S, int Tpad, int rows_per_chunk, const uint16_t * xn, const uint16_t * W, const float * bias,
+                             uint32_t sentinel, int out_rows, uint16_t * q, uint16_t * k, uint16_t * vt) {
+    if (M < 1 || S < 64 || (S % 64) != 0 || Tpad < 64 || (Tpad % 64) != 0 || rows_per_chunk < 0 || out_rows < M) return -1;
+    if (!xn || !W || !bias || !q || !k || !vt) return -1;
+    const int rpc = rows_per_chunk > 0 ? rows_per_chunk : M;
+    if (rpc > Tpad || (M % rpc) != 0 || M / rpc > 16) return -1;
+    if (!HIP_OK(hipSetDevice(device))) return -2;
+    const int chunks = M / rpc;
+    const size_t n_x = (size_t) M * S, n_w = (size_t) 3 * S * S, n_qk = (size_t) out_rows * S, n_vt = (size_t) chunks * S * Tpad;
+    const std::vector<uint16_t> pre(std::max(n_qk, n_vt), (uint16_t) sentinel);
+    __half * d_x = nullptr, * d_w = nullptr, * d_q = nullptr, * d_k = nullptr, * d_vt = nullptr; float * d_b = nullptr;
+    hipStream_t st = nullptr;
+    bool ok = HIP_OK(hipMalloc((void **) &d_x, n_x * 2)) && HIP_OK(hipMalloc((void **) &d_w, n_w * 2)) && HIP_OK(hipMalloc((void **) &d_b, (size_t) 3 * S * 4)) &&
+              HIP_OK(hipMalloc((void **) &d_q, n_qk * 2)) && HIP_OK(hipMalloc((void **) &d_k, n_qk * 2)) && HIP_OK(hipMalloc((void **) &d_vt, n_vt * 2)) &&
+              HIP_OK(hipStreamCreate(&st));
+    ok = ok && HIP_OK(hipMemcpy(d_x, xn, n_x * 2, hipMemcpyHostToDevice)) && HIP_OK(hipMemcpy(d_w, W, n_w * 2, hipMemcpyHostToDevice)) &&
+         HIP_OK(hipMemcpy(d_b, bias, (size_t) 3 * S * 4, hipMemcpyHostToDevice)) && HIP_OK(hipMemcpy(d_q, pre.data(), n_qk * 2, hipMemcpyHostToDevice)) &&
+         HIP_OK(hipMemcpy(d_k, pre.data(), n_qk * 2, hipMemcpyHostToDevice)) && HIP_OK(hipMemcpy(d_vt, pre.data(), n_vt * 2, hipMemcpyHostToDevice));
+    if (ok) {
+        k::GemmArgs a{};                                      // as encode_layers (device.cpp) and encode_rows (batch.cpp) fill it
+        a.A = d_x; a.lda = S; a.W = d_w; a.ldw = S; a.M = M; a.N = 3 * S; a.K = S; a.bias = d_b;
+        a.C = d_q; a.ldc = S; a.aux = d_k; a.ldaux = S; a.aux2 = d_vt; a.ldaux2 = Tpad; a.S = S;
+        if (rows_per_chunk > 0) { a.rows_per_chunk = rows_per_chunk; a.chunk_stride_aux2 = (int64_t) S * Tpad; }
+        k::gemm(k::EPI_QKV_ENC, a, st);
+        ok = HIP_OK(hipStreamSynchronize(st)) && HIP_OK(hipGetLastError());
+        ok = ok && HIP_OK(hipMemcpy(q, d_q, n_qk * 2, hipMemcpyDeviceToHost)) && HIP_OK(hipMemcpy(k, d_k, n_qk * 2, hipMemcpyDeviceToHost)) &&
+             HIP_OK(hipMemcpy(vt, d_vt, n_vt * 2, hipMemcpyDeviceToHost));
+    }
+    if (st) (void) hipStreamDestroy(st);
+    (void) hipFree(d_x); (void) hipFree(d_w); (void) hipFree(d_b); (void) hipFree(d_q); (void) hipFree(d_k); (void) hipFree(d_vt);
+    return ok ? 0 : -3;
+}
+
 int wmi_selftest_seqsum(const float * x, int n, float * out_blocked, float * out_plain) {
     if (!x || n < 0 || !out_blocked || !out_plain) return -1;
     volatile float acc = 0.0f;                              // the definition: one f32 addition after the other

@@ -1233,24 +1233,34 @@ size_t attn_cross_scratch_floats(int n, int H, int T) {
 static bool g_attn_one_group = false;
 void set_attn_one_group(bool on) { if (on != g_attn_one_group) bump_mode_epoch(); g_attn_one_group = on; }
 
-void attn_encoder(const __half * q, const __half * k, const __half * vt, int T, int Tpad, int S, int H, float scale,
-                  __half * out, hipStream_t st, int B, float * out32, int qk_chunk_rows, const RowLens * row_lens, int out_chunk_rows) {
+bool attn_encoder_splits(int form, int T, int Tpad, int H, float scale, int B) {
+    if (form >= 1 && scale == 0.125f && (Tpad % 64) == 0) return ((T + 127) / 128) * H * B < 512 && T >= 512 && !g_attn_one_group;
+    const int nblk = ((T + 63) / 64) * H * B;
+    return nblk <= 512 && T >= 256 && !g_attn_one_group;
+}
+
+void attn_encoder_form(const __half * q, const __half * k, const __half * vt, int T, int Tpad, int S, int H, float scale,
+                       __half * out, hipStream_t st, int B, float * out32, int qk_chunk_rows, const RowLens * row_lens, int out_chunk_rows,
+                       int form, bool split) {
     const int qk_rows = qk_chunk_rows > 0 ? qk_chunk_rows : T;
     const int out_rows = out_chunk_rows > 0 ? out_chunk_rows : T;
     RowLens lens{};
-    if (row_lens && B > 1) lens = *row_lens;      // T = the largest of them: the grid and the split decisions below are taken once per launch
-    // WMI_ATTN_FORM: 2 (default) = 32-row wavefronts, one sweep with a running maximum; 1 = the same kernel with the exact row
-    // maximum found in a first sweep (the reference's soft-max argument); 0 = the round-1/2 kernel (16-row wavefronts, two sweeps)
-    static const int form = getenv("WMI_ATTN_FORM") ? atoi(getenv("WMI_ATTN_FORM")) : 2;
+    if (row_lens && B > 1) lens = *row_lens;      // T = the largest of them: the grid and the split decisions are taken once per launch
     if (form >= 1 && scale == 0.125f && (Tpad % 64) == 0) {
-        const bool split = ((T + 127) / 128) * H * B < 512 && T >= 512 && !g_attn_one_group;
         attn_encoder2(q, k, vt, T, Tpad, S, H, out, st, B, out32, form == 2, split, qk_rows, row_lens, out_rows);
         return;
     }
-    const int nblk = ((T + 63) / 64) * H * B;
-    const bool ks2 = nblk <= 512 && T >= 256 && !g_attn_one_group;
-    if (ks2) hipLaunchKernelGGL((k_attn_enc<4, 2>), dim3((T + 63) / 64, H, B), dim3(512), 0, st, q, k, vt, T, Tpad, S, scale, out, out32, qk_rows, out_rows, lens);
-    else     hipLaunchKernelGGL((k_attn_enc<4, 1>), dim3((T + 63) / 64, H, B), dim3(256), 0, st, q, k, vt, T, Tpad, S, scale, out, out32, qk_rows, out_rows, lens);
+    if (split) hipLaunchKernelGGL((k_attn_enc<4, 2>), dim3((T + 63) / 64, H, B), dim3(512), 0, st, q, k, vt, T, Tpad, S, scale, out, out32, qk_rows, out_rows, lens);
+    else       hipLaunchKernelGGL((k_attn_enc<4, 1>), dim3((T + 63) / 64, H, B), dim3(256), 0, st, q, k, vt, T, Tpad, S, scale, out, out32, qk_rows, out_rows, lens);
+}
+
+void attn_encoder(const __half * q, const __half * k, const __half * vt, int T, int Tpad, int S, int H, float scale,
+                  __half * out, hipStream_t st, int B, float * out32, int qk_chunk_rows, const RowLens * row_lens, int out_chunk_rows) {
+    // WMI_ATTN_FORM: 2 (default) = 32-row wavefronts, one sweep with a running maximum; 1 = the same kernel with the exact row
+    // maximum found in a first sweep (the reference's soft-max argument); 0 = the round-1/2 kernel (16-row wavefronts, two sweeps)
+    static const int form = getenv("WMI_ATTN_FORM") ? atoi(getenv("WMI_ATTN_FORM")) : 2;
+    attn_encoder_form(q, k, vt, T, Tpad, S, H, scale, out, st, B, out32, qk_chunk_rows, row_lens, out_chunk_rows, form,
+                      attn_encoder_splits(form, T, Tpad, H, scale, B));
 }
 
 void attn_decoder(const __half * q, int n, int S, int H, const __half * kc, const __half * vc, int n_kv,

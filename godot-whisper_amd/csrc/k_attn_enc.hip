@@ -212,7 +212,12 @@ __global__ __launch_bounds__(QW * KS * 64) void k_attn_enc2(const __half * __res
         if constexpr (ONE) {
             const float mn = fmaxf(m, tile_max(s));
             // alpha = exp(m - mn) in f32; nothing seen yet (m = -inf) or nothing valid at all (mn = -inf): factor irrelevant / 1
-            const float alpha = mn == -INFINITY ? 1.0f : __builtin_amdgcn_exp2f((m - mn) * LOG2E);
+            // a maximum that rises by more than 17.5: every key seen so far has s - max < -17.5, a numerator below 2^-25, which is 0 in
+            // f16 — the reference and the two-sweep forms drop those keys, and so does this form: alpha = 0, not e^-17.5 or less.  (Kept,
+            // the remainder o * alpha, 1e-37 .. 1e-25, sat in the accumulator the P.V MFMA adds to: the matrix pipe counts a NEGATIVE
+            // addend far below the sum's last bit as minus one internal unit, and a sum that is exactly +2^k came out as the next f32
+            // below it — found by the selector cases of tests/test_gpu_attn_encoder.py)
+            const float alpha = mn == -INFINITY ? 1.0f : (m - mn < -17.5f ? 0.0f : __builtin_amdgcn_exp2f((m - mn) * LOG2E));
             m = mn;
             l *= alpha;
 #pragma unroll

@@ -227,6 +227,13 @@ void attn_encoder(const __half * q, const __half * k, const __half * vt, int T, 
                   int qk_chunk_rows = 0,      // rows between the chunks of q and k (0 = T; lock-step chunks start on 16-row boundaries, batch.cpp)
                   const RowLens * row_lens = nullptr,   // B > 1: chunk z attends row_lens->t[z] queries and keys (T = the largest: grid and key split are
                   int out_chunk_rows = 0);              // decided once per launch by it); out_chunk_rows: rows between the chunks of out (0 = T)
+// the same launch with the form (WMI_ATTN_FORM's values: 2, 1, 0) and the key-group choice given by the caller (split: four key groups
+// of the second form, two of the first) — attn_encoder() is this with the environment's form and attn_encoder_splits()' answer, its rule
+// for the launch (form, largest length, grid); the test hook wmi_selftest_attn_encoder names both itself
+bool attn_encoder_splits(int form, int T, int Tpad, int H, float scale, int B);
+void attn_encoder_form(const __half * q, const __half * k, const __half * vt, int T, int Tpad, int S, int H, float scale,
+                       __half * out, hipStream_t st, int B, float * out32, int qk_chunk_rows, const RowLens * row_lens, int out_chunk_rows,
+                       int form, bool split);
 // decoder: one (token, head) per workgroup.  kc/vc: [n_kv][S] caches (this layer), mask: [n][ld_mask] or null
 void attn_decoder(const __half * q, int n, int S, int H, const __half * kc, const __half * vc, int n_kv,
                   const float * mask, int ld_mask, __half * out, hipStream_t st,

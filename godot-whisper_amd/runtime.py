@@ -96,6 +96,10 @@ DEVICE_API = [
     ("wmi_weights_bytes", C.c_size_t, [C.c_void_p, C.c_int]),
     ("wmi_selftest_quant", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                      C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("wmi_selftest_attn_encoder", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                            C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    ("wmi_selftest_qkv_encoder", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int,
+                                           C.c_void_p, C.c_void_p, C.c_void_p]),
 ]
 
 _lib = None

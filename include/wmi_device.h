@@ -384,6 +384,26 @@ WHISPER_API int wmi_selftest_resample_plan(int n_frames, int src_rate, int dst_r
 WHISPER_API int wmi_selftest_quant(int device, int qtype, int mode, const void * w_blocks, const float * x, const int32_t * tokens,
                                    int M, int N, int K, float * out, int8_t * out_qs, float * out_ds);
 
+/* The encoder self-attention kernels on caller operands (parity tests, no context needed; tests/test_gpu_attn_encoder.py).  All host
+ * pointers; q, k [B][qk_rows][S] and v [B][Tpad][S] (time-major) are f16 bit patterns.  The hook lays v out as the V^T image
+ * [B][S][Tpad] the kernels read (time index with bits 2 and 3 swapped, the order the q|k|v epilogue writes), fills `out` — [B][out_rows][S],
+ * f16 or, with want_f32, f32 — with `sentinel` (its low 16 bits for f16), launches once and copies all of `out` back.
+ *   T        the launch's (largest) length; row_T (NULL, or B entries in [1, T]): a length per chunk, as lock-step chunks have (used from B = 2 on)
+ *   form     2 one sweep with a running maximum, 1 exact maximum first, 0 the first kernel (16-row wavefronts) — WMI_ATTN_FORM's values
+ *   groups   0 one key group, 1 the keys split over wave groups (four; form 0: two), -1 what the product decides for this launch
+ * Returns 0; -1 for what the product never launches (S != 64 H, Tpad % 64, Tpad / qk_rows / out_rows < T, B > 16, a row_T entry outside
+ * [1, T], groups = 1 below T = 512 (form 0: 256)) — decided before the device is touched; -2 / -3 on a device error. */
+WHISPER_API int wmi_selftest_attn_encoder(int device, int B, int T, int Tpad, int S, int H, int qk_rows, int out_rows, const int32_t * row_T,
+                                          int want_f32, int form, int groups, const uint16_t * q, const uint16_t * k, const uint16_t * v,
+                                          uint32_t sentinel, void * out);
+/* The encoder's q|k|v projection with its split epilogue on caller operands: xn [M][S] and W [3 S][S] as f16 bit patterns, bias [3 S] f32.
+ * rows_per_chunk = 0: one chunk of M rows; else M = chunks x rows_per_chunk (<= 16 chunks), each chunk with its own V^T image.  The
+ * arguments of the launch are the encoder's (ldaux2 = Tpad, chunk_stride_aux2 = S * Tpad).  q, k [out_rows][S] (out_rows >= M) and the raw
+ * V^T image vt [chunks][S][Tpad] are filled with `sentinel` first and come back whole.  Returns 0; -1 bad argument (before the device is
+ * touched: S % 64, Tpad % 64, rows_per_chunk > Tpad or not dividing M, out_rows < M); -2 / -3 on a device error. */
+WHISPER_API int wmi_selftest_qkv_encoder(int device, int M, int S, int Tpad, int rows_per_chunk, const uint16_t * xn, const uint16_t * W,
+                                         const float * bias, uint32_t sentinel, int out_rows, uint16_t * q, uint16_t * k, uint16_t * vt);
+
 /* Kernel micro-benchmarks on synthetic operands (used by bench.py for the roofline line):
  * runs `iters` launches on the context stream between two HIP events, returns average microseconds.
  *   which = 0  encoder MLP-0 GEMM  [T x 4S x S] f16 MFMA   (flops = 2*T*4S*S)
