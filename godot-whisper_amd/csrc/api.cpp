@@ -1104,6 +1104,58 @@ int wmi_selftest_qkv_encoder(int device, int M, int S, int Tpad, int rows_per_ch
     return ok ? 0 : -3;
 }
 
+int wmi_selftest_qkv_encoder_q(int device, int qtype, int M, int S, int Tpad, int rows_per_chunk, const float * x, const void * w_blocks,
+                               const float * bias, uint32_t sentinel, int out_rows, uint16_t * q, uint16_t * k, uint16_t * vt) {
+    const k::QGeom geo = k::q_geom(qtype);
+    if (!geo.qb || M < 1 || S < 128 || (S % 128) != 0 || Tpad < 64 || (Tpad % 64) != 0 || rows_per_chunk < 0 || out_rows < M) return -1;
+    if (!x || !w_blocks || !bias || !q || !k || !vt) return -1;
+    const int rpc = rows_per_chunk > 0 ? rows_per_chunk : M;
+    if (rpc > Tpad || (M % rpc) != 0 || M / rpc > 16) return -1;
+    if (!HIP_OK(hipSetDevice(device))) return -2;
+    const int chunks = M / rpc, N = 3 * S, nblk = S / 32;
+    const size_t n_qk = (size_t) out_rows * S, n_vt = (size_t) chunks * S * Tpad;
+    const std::vector<uint16_t> pre(std::max(n_qk, n_vt), (uint16_t) sentinel);
+    std::vector<uint8_t> tiles(k::q_matrix_bytes(qtype, N, S));
+    k::q_repack_host(qtype, (const uint8_t *) w_blocks, N, S, tiles.data());
+    uint8_t * d_t = nullptr; float * d_x = nullptr, * d_b = nullptr, * d_ds = nullptr; int8_t * d_qs = nullptr;
+    __half * d_q = nullptr, * d_k = nullptr, * d_vt = nullptr;
+    hipStream_t st = nullptr;
+    bool ok = HIP_OK(hipMalloc((void **) &d_t, tiles.size() + 4096)) && HIP_OK(hipMalloc((void **) &d_x, (size_t) M * S * 4)) &&
+              HIP_OK(hipMalloc((void **) &d_b, (size_t) N * 4)) && HIP_OK(hipMalloc((void **) &d_qs, (size_t) M * S)) &&
+              HIP_OK(hipMalloc((void **) &d_ds, (size_t) M * nblk * 8)) && HIP_OK(hipMalloc((void **) &d_q, n_qk * 2)) &&
+              HIP_OK(hipMalloc((void **) &d_k, n_qk * 2)) && HIP_OK(hipMalloc((void **) &d_vt, n_vt * 2)) && HIP_OK(hipStreamCreate(&st));
+    ok = ok && HIP_OK(hipMemcpy(d_t, tiles.data(), tiles.size(), hipMemcpyHostToDevice)) && HIP_OK(hipMemcpy(d_x, x, (size_t) M * S * 4, hipMemcpyHostToDevice)) &&
+         HIP_OK(hipMemcpy(d_b, bias, (size_t) N * 4, hipMemcpyHostToDevice)) && HIP_OK(hipMemcpy(d_q, pre.data(), n_qk * 2, hipMemcpyHostToDevice)) &&
+         HIP_OK(hipMemcpy(d_k, pre.data(), n_qk * 2, hipMemcpyHostToDevice)) && HIP_OK(hipMemcpy(d_vt, pre.data(), n_vt * 2, hipMemcpyHostToDevice));
+    if (ok) {
+        const k::QMat W{d_t, qtype};
+        k::Q8Rows A{d_qs, d_ds, d_ds + (size_t) nblk * M, M};          // (no f16 images: the block-dot kernel whatever M is)
+        A.form = k::QFORM_BLOCK_DOT;
+        k::quantize_rows(d_x, nullptr, M, S, nullptr, nullptr, 0.f, qtype, A, nullptr, nullptr, st);
+        k::GemmArgs a{};                                      // as encode_layers_q_on (device_q.cpp) fills it
+        a.M = M; a.N = N; a.K = S; a.bias = d_b;
+        a.C = d_q; a.ldc = S; a.aux = d_k; a.ldaux = S; a.aux2 = d_vt; a.ldaux2 = Tpad; a.S = S;
+        a.rows_per_chunk = rpc; a.chunk_stride_aux2 = (int64_t) S * Tpad;
+        k::qgemm(k::EPI_QKV_ENC, a, A, W, st);
+        ok = HIP_OK(hipStreamSynchronize(st)) && HIP_OK(hipGetLastError());
+        ok = ok && HIP_OK(hipMemcpy(q, d_q, n_qk * 2, hipMemcpyDeviceToHost)) && HIP_OK(hipMemcpy(k, d_k, n_qk * 2, hipMemcpyDeviceToHost)) &&
+             HIP_OK(hipMemcpy(vt, d_vt, n_vt * 2, hipMemcpyDeviceToHost));
+    }
+    if (st) (void) hipStreamDestroy(st);
+    (void) hipFree(d_t); (void) hipFree(d_x); (void) hipFree(d_b); (void) hipFree(d_qs); (void) hipFree(d_ds); (void) hipFree(d_q); (void) hipFree(d_k); (void) hipFree(d_vt);
+    return ok ? 0 : -3;
+}
+
+int wmi_selftest_lockstep_sets(const int * audio_ctx, int n, int n_audio_ctx, int quantised, int * order, int * set_of) {
+    if (!audio_ctx || n < 1 || n_audio_ctx < 1 || !order || !set_of) return -1;
+    for (int c = 0; c < n; ++c) if (audio_ctx[c] < 0 || audio_ctx[c] > n_audio_ctx) return -1;
+    try {
+        std::vector<int> eff(n);
+        for (int c = 0; c < n; ++c) eff[c] = audio_ctx[c] > 0 ? audio_ctx[c] : n_audio_ctx;
+        return lockstep_sets(eff.data(), n, quantised != 0, k::attn_cross_takes_row_lens(1, n_audio_ctx), order, set_of);
+    } catch (const std::exception &) { return -1; }
+}
+
 int wmi_selftest_seqsum(const float * x, int n, float * out_blocked, float * out_plain) {
     if (!x || n < 0 || !out_blocked || !out_plain) return -1;
     volatile float acc = 0.0f;                              // the definition: one f32 addition after the other

@@ -103,10 +103,11 @@ bool ensure_batch(whisper_context & ctx, int B) {
            && dalloc(w.dx, nb * S) && dalloc(w.dq, nb * S) && dalloc(w.datt, nb * S) && dalloc(w.dh, nb * 4 * S) && dalloc(w.logits, nb * hp.n_vocab)
            && dalloc(w.xattn, k::attn_cross_scratch_floats(B, (int) H, (int) T));
     if (ctx.model.quantised) {                               // q8 activation rows of all chunks + f32 attention outputs (device_q.cpp)
-        w.aq_rows = (int) (nb * T);
-        ok = ok && dalloc(w.aq, nb * T * 4 * S) && dalloc(w.ads, 2 * nb * T * (4 * S / 32)) && dalloc(w.att32, nb * T * S) && dalloc(w.datt32, nb * S);
+        // (TP rows per chunk, as every other image: chunks with lengths of their own are stacked with a period of up to TP rows)
+        w.aq_rows = (int) (nb * TP);
+        ok = ok && dalloc(w.aq, nb * TP * 4 * S) && dalloc(w.ads, 2 * nb * TP * (4 * S / 32)) && dalloc(w.att32, nb * TP * S) && dalloc(w.datt32, nb * S);
         w.wq16_elems = 8 * S * S;
-        ok = ok && dalloc(w.aq16, nb * T * 4 * S) && dalloc(w.wq16, w.wq16_elems);
+        ok = ok && dalloc(w.aq16, nb * TP * 4 * S) && dalloc(w.wq16, w.wq16_elems);
     }
     if (ok && !ctx.model.quantised && S <= 1024) {
         const size_t bytes = nb * 16 * S + 64 + nb * (size_t) k::XBACK_ROW_GRANULES * 8;      // + the rows' cross-attention back (k::xback)
@@ -125,6 +126,7 @@ bool ensure_batch(whisper_context & ctx, int B) {
     k::fill_zero(w.x, nb * TP * S * sizeof(float), s);              // (likewise where the chunks have lengths of their own: rows behind a chunk's
     k::fill_zero(w.att, nb * TP * S * sizeof(__half), s);           //  length are operands of the stacked GEMMs and are not written by every pass:
                                                                     //  the attention never writes att rows >= T_r, so w_o multiplies what earlier passes left — finite)
+    if (ctx.model.quantised) k::fill_zero(w.att32, nb * TP * S * sizeof(float), s);      // (att's f32 twin of the quantised pass: the same reason)
     k::fill_zero(w.conv1, (nb * (2 * T + 8) * S + 4 * S) * sizeof(__half), s);
     k::fill_zero(w.mel_t, (nb * w.mel_rows * hp.n_mels + 1024) * sizeof(__half), s);
     k::fill_zero(w.self_k, nb * Lt * n_ctx * S * sizeof(__half), s);
@@ -161,7 +163,17 @@ bool encode_rows(whisper_context & ctx, const std::vector<int> & rows, const std
         for (int r = 0; r < nb; ++r) ragged = ragged || lens.t[r] != T;
     } else if (row_ctx && nb == 1) T = row_ctx[0] > 0 ? row_ctx[0] : hp.n_audio_ctx;
     if (T > hp.n_audio_ctx || (row_ctx && nb > 16)) { WMI_ERR("%s: encoder length %d of %d rows is not served\n", __func__, T, nb); return false; }
-    if (ragged && ctx.model.quantised) { WMI_ERR("%s: rows of different lengths on a block-quantised model (full_batch partitions them)\n", __func__); return false; }
+    // block-quantised models: the projections of such a pass take the form each chunk's own pass takes (kernels.h QForm), so its chunks
+    // must lie on one side of that threshold (full_batch cuts its calls so: lockstep_sets)
+    int qform = k::QFORM_BY_M;
+    if (ragged && ctx.model.quantised) {
+        const bool f16 = k::qgemm_takes_f16_form(lens.t[0]);
+        for (int r = 1; r < nb; ++r) if (k::qgemm_takes_f16_form(lens.t[r]) != f16) {
+            WMI_ERR("%s: rows on both sides of the block-dot / f16 threshold of the quantised projections (%d and %d rows; full_batch partitions them)\n", __func__, lens.t[0], lens.t[r]);
+            return false;
+        }
+        qform = f16 ? k::QFORM_F16 : k::QFORM_BLOCK_DOT;
+    }
     // the rows step can give every row its own keys only in the one-launch cross-attention (full_batch cuts other calls into sets of one length)
     if (ragged && (hp.n_text_state > 1536 || !k::attn_cross_takes_row_lens(hp.n_text_head, T))) {
         WMI_ERR("%s: rows of different lengths need the one-launch cross-attention (not at S = %d, T = %d, WMI_XATTN_TWO_PASS)\n", __func__, hp.n_text_state, T);
@@ -178,6 +190,11 @@ bool encode_rows(whisper_context & ctx, const std::vector<int> & rows, const std
     //                  earlier passes (finite: zeroed at allocation, only ever written with finite values) in att; never read for a valid row
     //                  except as V^T columns of a chunk's last key tile, where their soft-max weight is exactly 0 — hence finite, not junk
     //   T <= t < TP    x zeroed below, the rest as above
+    // Block-quantised models (encode_layers_q_on): the same period in x, the q8 rows (aq / ads / aq16), q, k, att32, h, enc_out_h, cross K / V.
+    //   t < T_r        as above, with the projections in the form the one-chunk pass at T_r takes (qform)
+    //   T_r <= t < TP  x as above; the q8 rows, q, k, V^T, h, enc_out_h and cross K / V are written by this pass for every row of the stack
+    //                  (the quantiser and the GEMMs run over all nb * TP rows; a row of zeros quantises to d = 0, q = 0); att32 is att's
+    //                  twin: never written behind T_r, zeroed at allocation, only ever written with finite values
     // A pass whose rows all have one length keeps its period T (xn / q / k: T rounded up to 16), as before.
     const int P = ragged ? (T + 15) & ~15 : T;
     const int M = nb * P;
@@ -242,11 +259,14 @@ bool encode_rows(whisper_context & ctx, const std::vector<int> & rows, const std
         e.T = T; e.nb = nb; e.Tpad = b.Tpad; e.x = b.x; e.q = b.q; e.k = b.k; e.vt = b.vt; e.h = b.h; e.att32 = b.att32;
         e.enc_out = nullptr; e.enc_out_h = b.enc_out_h; e.kvc_k = b.kvc_k; e.kvc_v = b.kvc_v;
         e.A = q8_rows(b, S); e.A4 = q8_rows(b, 4 * S);
+        e.A.form = e.A4.form = qform;
+        if (ragged) { e.P = P; e.lens = lens; }
+        if (M > b.aq_rows) { WMI_ERR("%s: %d stacked rows exceed the work set (%d)\n", __func__, M, b.aq_rows); return false; }
         if (!encode_layers_q_on(ctx, e, s)) return false;
         HIP_TRY(hipStreamSynchronize(s));
         if (!HIP_OK(hipGetLastError())) return false;
-        b.enc_rows = nb; b.enc_T = T; b.enc_Tmax = T; b.enc_ragged = false;
-        for (int r = 0; r < 16; ++r) b.enc_row_T[r] = r < nb ? T : 0;
+        b.enc_rows = nb; b.enc_T = P; b.enc_Tmax = T; b.enc_ragged = ragged;
+        for (int r = 0; r < 16; ++r) b.enc_row_T[r] = r >= nb ? 0 : ragged ? lens.t[r] : T;
         b.t_encode_us += time_us() - t0;
         return true;
     }
@@ -672,6 +692,33 @@ int check_audio_ctxs(const whisper_context & ctx, const int * audio_ctx, int n, 
     return 0;
 }
 
+// The plan of a call with an encoder length per chunk (host only; wmi_selftest_lockstep_sets shows it to the tests): the order of the
+// chunks — longest first, stable; the caller's order when all lengths are equal — and the SETS the ordered chunks are cut into, each a
+// lock-step call of its own.  eff_T[c] > 0: chunk c's effective length.  order[i] = the chunk at position i, set_of[i] = its set (0, 1, ...
+// along the order).  Returns the number of sets.
+//   per_row (the rows can carry a length each: the one-launch cross-attention), f16 weights: one set.
+//   per_row, block-quantised weights: two chunks share a set when their lengths lie on the same side of the threshold between the block-dot
+//     and the f16 form of the projections (k::qgemm_takes_f16_form) — the stacked pass then runs every projection in the form each of its
+//     chunks' own passes takes (encode_rows) — at most two sets.
+//   else (the two-launch cross-attention): sets of equal length.
+int lockstep_sets(const int * eff_T, int n, bool quantised, bool per_row, int * order, int * set_of) {
+    bool uniform = true;
+    for (int c = 1; c < n; ++c) uniform = uniform && eff_T[c] == eff_T[0];
+    for (int c = 0; c < n; ++c) order[c] = c;
+    if (!uniform) std::stable_sort(order, order + n, [&](int a, int b2) { return eff_T[a] > eff_T[b2]; });
+    auto together = [&](int a, int b2) {
+        if (uniform || eff_T[a] == eff_T[b2]) return true;
+        if (!per_row) return false;
+        return !quantised || k::qgemm_takes_f16_form(eff_T[a]) == k::qgemm_takes_f16_form(eff_T[b2]);
+    };
+    int sets = 0;
+    for (int i = 0; i < n; ++i) {
+        if (i == 0 || !together(order[i - 1], order[i])) ++sets;
+        set_of[i] = sets - 1;
+    }
+    return sets;
+}
+
 // audio_ctx (wmi_full_batch_ctx): an encoder length per chunk.  The call orders the lock-step chunks by length (below), so the nested
 // calls it makes for that see `ordered` chunks
 static thread_local bool t_ordered = false;
@@ -779,15 +826,14 @@ int full_batch(whisper_context & ctx, whisper_full_params params, const float * 
     // ---- chunks with lengths of their own: longest first, so that the chunks that share a group of 16 rows (and a range of the groups below)
     // have neighbouring lengths and the rows behind a chunk's own length (encode_rows: TP) stay few.  Results go back in the caller's order.
     // A chunk's result does not depend on the order in exact mode (per-row arithmetic); in the default mode as it depends on the grouping.
-    // Where the rows cannot carry a length each — block-quantised models (encode_layers_q_on has one length), the two-launch form of the
-    // cross-attention — the ordered chunks are cut into sets of one length, each a lock-step call of its own with that length.
+    // The ordered chunks are cut into sets, each a lock-step call of its own (lockstep_sets has the rule): one set where the rows can carry a
+    // length each; two at most on a block-quantised model (the chunks below and from the projections' block-dot / f16 threshold on); sets of
+    // one length with the two-launch form of the cross-attention.  A set whose chunks all have one length is the uniform call of that length.
     if (audio_ctx && !t_ordered) {
-        bool uniform = true;
-        for (int c = 1; c < n_chunks; ++c) uniform = uniform && eff_T(c) == eff_T(0);
-        const bool per_row = !ctx.model.quantised && k::attn_cross_takes_row_lens(hp.n_text_head, hp.n_audio_ctx) && hp.n_text_state <= 1536;
-        std::vector<int> order(n_chunks);
-        for (int c = 0; c < n_chunks; ++c) order[c] = c;
-        if (!uniform) std::stable_sort(order.begin(), order.end(), [&](int a, int b2) { return eff_T(a) > eff_T(b2); });
+        const bool per_row = k::attn_cross_takes_row_lens(hp.n_text_head, hp.n_audio_ctx) && hp.n_text_state <= 1536;
+        std::vector<int> order(n_chunks), set_of(n_chunks), eff(n_chunks);
+        for (int c = 0; c < n_chunks; ++c) eff[c] = eff_T(c);
+        (void) lockstep_sets(eff.data(), n_chunks, ctx.model.quantised, per_row, order.data(), set_of.data());
         std::vector<const float *> o_pcm(n_chunks); std::vector<int> o_n(n_chunks), o_ctx(n_chunks);
         for (int i = 0; i < n_chunks; ++i) { o_pcm[i] = pcm[order[i]]; o_n[i] = n_samples[order[i]]; o_ctx[i] = audio_ctx[order[i]]; }
         BatchWork & bw = *ctx.batch;
@@ -797,11 +843,13 @@ int full_batch(whisper_context & ctx, whisper_full_params params, const float * 
         int64_t tm[4] = {0, 0, 0, 0}; int steps = 0, chained = 0, groups = 1;
         struct Flag { Flag() { t_ordered = true; } ~Flag() { t_ordered = false; } } flag;
         for (int i0 = 0; i0 < n_chunks; ) {
-            int i1 = n_chunks;
-            if (!per_row && !uniform) { i1 = i0 + 1; while (i1 < n_chunks && eff_T(order[i1]) == eff_T(order[i0])) ++i1; }
+            int i1 = i0 + 1;
+            while (i1 < n_chunks && set_of[i1] == set_of[i0]) ++i1;
+            bool one_length = true;
+            for (int i = i0 + 1; i < i1; ++i) one_length = one_length && eff[order[i]] == eff[order[i0]];
             whisper_full_params ps = params;
-            if (!per_row || uniform) ps.audio_ctx = o_ctx[i0];          // one length: the call wmi_full_batch makes
-            const int rc = full_batch(ctx, ps, o_pcm.data() + i0, o_n.data() + i0, i1 - i0, on_device, per_row && !uniform ? o_ctx.data() + i0 : nullptr);
+            if (one_length) ps.audio_ctx = o_ctx[i0];                   // one length: the call wmi_full_batch makes
+            const int rc = full_batch(ctx, ps, o_pcm.data() + i0, o_n.data() + i0, i1 - i0, on_device, one_length ? nullptr : o_ctx.data() + i0);
             if (rc != 0) return rc;
             for (int i = i0; i < i1; ++i) {
                 const int c = order[i];

@@ -70,7 +70,11 @@ bool encode_layers_q(whisper_context & ctx, int T) {
 bool encode_layers_q_on(whisper_context & ctx, const EncBufsQ & e, hipStream_t s) {
     const Weights & w = ctx.w; const HParams & hp = ctx.model.hp;
     const int S = hp.n_audio_state, H = hp.n_audio_head, La = hp.n_audio_layer, Lt = hp.n_text_layer;
-    const int T = e.T, M = e.nb * e.T;
+    // P: rows between consecutive chunks in every image (wmi.h EncBufsQ) — T, or the common period of chunks with lengths of their own.  The
+    // rows behind a chunk's own length are operands of the stacked quantiser and GEMMs like any other (row-wise kernels: they change no valid
+    // row) and are never read as queries or keys: the attention stops at the chunk's length (batch.cpp encode_rows has the table)
+    const int T = e.T, P = e.P > 0 ? e.P : e.T, M = e.nb * P;
+    const k::RowLens * lens = e.lens.n ? &e.lens : nullptr;
     k::Q8Rows A = e.A, A4 = e.A4;
     A.w_resident_ok = A4.w_resident_ok = true;              // the encoder's matrices: resident f16 images beside the blocks (k_quant.hip)
     const int qt = w.qtype;
@@ -84,10 +88,26 @@ bool encode_layers_q_on(whisper_context & ctx, const EncBufsQ & e, hipStream_t s
             k::GemmArgs a{};
             a.M = M; a.N = 3 * S; a.K = S; a.bias = l.b_qkv;
             a.C = e.q; a.ldc = S; a.aux = e.k; a.ldaux = S; a.aux2 = e.vt; a.ldaux2 = e.Tpad; a.S = S;
-            a.rows_per_chunk = T; a.chunk_stride_aux2 = (int64_t) S * e.Tpad;
+            a.rows_per_chunk = P; a.chunk_stride_aux2 = (int64_t) S * e.Tpad;
             k::qgemm(k::EPI_QKV_ENC, a, Aq, l.q_qkv, s);
         }
-        k::attn_encoder(e.q, e.k, e.vt, T, e.Tpad, S, H, kq_scale, nullptr, s, e.nb, e.att32);
+        if (!lens) k::attn_encoder(e.q, e.k, e.vt, T, e.Tpad, S, H, kq_scale, nullptr, s, e.nb, e.att32);
+        else {
+            // Chunks with lengths of their own: each attends with the key split its own one-chunk pass takes, as the projections take that
+            // pass's form — the split changes the f32 order of the soft-max sums, and the quantiser behind the attention turns that into whole
+            // q8 steps.  One launch per run of consecutive chunks with the same answer (the chunks arrive longest first: two runs at most)
+            for (int r0 = 0; r0 < e.nb; ) {
+                const bool split = k::attn_encoder_splits_alone(lens->t[r0], e.Tpad, H, kq_scale);
+                int r1 = r0 + 1;
+                while (r1 < e.nb && k::attn_encoder_splits_alone(lens->t[r1], e.Tpad, H, kq_scale) == split) ++r1;
+                k::RowLens run{}; run.n = r1 - r0;
+                int Trun = 0;
+                for (int r = r0; r < r1; ++r) { run.t[r - r0] = lens->t[r]; Trun = std::max(Trun, lens->t[r]); }
+                k::attn_encoder(e.q + (size_t) r0 * P * S, e.k + (size_t) r0 * P * S, e.vt + (size_t) r0 * S * e.Tpad, Trun, e.Tpad, S, H, kq_scale,
+                                nullptr, s, r1 - r0, e.att32 + (size_t) r0 * P * S, P, &run, P, split ? 1 : 0);
+                r0 = r1;
+            }
+        }
         Aq.wdeq_ready = k::quantize_rows(e.att32, nullptr, M, S, nullptr, nullptr, 0.f, qt, A, nullptr, nullptr, s, &l.q_o, S); Aq.wdeq_of = l.q_o.tiles;
         {
             k::GemmArgs a{};
@@ -299,13 +319,19 @@ void enqueue_rows_lang_step_q(whisper_context & ctx, int nb, float * out) { enqu
 static void enqueue_rows_step_q_(whisper_context & ctx, int nb, float * lang_out) {
     BatchWork & b = *ctx.batch; const Weights & w = ctx.w; const HParams & hp = ctx.model.hp;
     const int S = hp.n_text_state, H = hp.n_text_head, Lt = hp.n_text_layer, NV = hp.n_vocab, n_ctx = hp.n_text_ctx;
-    const int Tc = b.enc_T;
+    // Tc: the keys of the longest row (layout of the partials, grid); TPc: rows between the chunks' cross K / V.  Rows with lengths of their
+    // own: each attends its own keys in its own slices (k::RowLens by value: a captured step is keyed on them, batch.cpp decode_rows_step);
+    // the out projection's prologue combiner gives a slice a row does not have (maximum -inf) the weight 0
+    const int Tc = b.enc_Tmax, TPc = b.enc_T;
+    k::RowLens xlens{};
+    if (b.enc_ragged) { xlens.n = nb; for (int r = 0; r < nb; ++r) xlens.t[r] = b.enc_row_T[r]; }
+    const k::RowLens * xl = b.enc_ragged ? &xlens : nullptr;
     hipStream_t s = ctx.state->dev.stream;
     const k::DecStep * stp = (const k::DecStep *) b.step_dev;
     const float kq_scale = powf((float) S / H, -0.25f);
     const int step_stride = (int) (sizeof(k::DecStep) / sizeof(int32_t));
     const int64_t cache_stride = (int64_t) Lt * n_ctx * S;
-    const int64_t cross_layer = (int64_t) b.enc_rows * Tc * S;
+    const int64_t cross_layer = (int64_t) b.enc_rows * TPc * S;
     k::qdec_embed_step((const k::DecStep *) b.step_host, (k::DecStep *) b.step_dev, S, w.q_te, w.d_pe, b.dx, s, nb);
     const k::QMat * pfW = nullptr; int pfN = 0, pfK = 0;                       // the next weight-streaming launch's matrix (k_qrows prefetch)
     auto next = [&](const k::QMat & W, int N, int K) { pfW = &W; pfN = N; pfK = K; };
@@ -339,12 +365,12 @@ static void enqueue_rows_step_q_(whisper_context & ctx, int nb, float * lang_out
         next(l.q_co, S, S);
         const float * po = nullptr, * pl = nullptr, * pm = nullptr; int ns = 0;
         if (k::qattn_cross_qsplit_partials(b.dx, l.ln2_g, l.ln2_b, hp.eps, l.q_cq, l.b_cq, kq_scale, nb, S, H, b.kvc_k + (size_t) il * cross_layer,
-                                           b.kvc_v + (size_t) il * cross_layer, Tc, b.xattn, &po, &pl, &pm, &ns, s, (int64_t) Tc * S,
-                                           pfW ? *pfW : k::QMat{}, pfN, pfK)) pfW = nullptr;
+                                           b.kvc_v + (size_t) il * cross_layer, Tc, b.xattn, &po, &pl, &pm, &ns, s, (int64_t) TPc * S,
+                                           pfW ? *pfW : k::QMat{}, pfN, pfK, xl)) pfW = nullptr;
         else {
             k::qrows(rows(k::EPI_Q_SCALED, ln2, S, S, l.q_cq, l.b_cq, b.dq, S, nullptr, nullptr, nullptr, kq_scale, nullptr), nullptr, l.q_cq, s);
             k::attn_cross_split_partials(b.dq, nb, S, H, b.kvc_k + (size_t) il * cross_layer, b.kvc_v + (size_t) il * cross_layer, Tc,
-                                         b.xattn, &po, &pl, &pm, &ns, s, (int64_t) Tc * S);
+                                         b.xattn, &po, &pl, &pm, &ns, s, (int64_t) TPc * S, xl);
         }
         {
             next(l.q_fc1, 4 * S, S);

@@ -1254,13 +1254,17 @@ void attn_encoder_form(const __half * q, const __half * k, const __half * vt, in
     else       hipLaunchKernelGGL((k_attn_enc<4, 1>), dim3((T + 63) / 64, H, B), dim3(256), 0, st, q, k, vt, T, Tpad, S, scale, out, out32, qk_rows, out_rows, lens);
 }
 
+// WMI_ATTN_FORM: 2 (default) = 32-row wavefronts, one sweep with a running maximum; 1 = the same kernel with the exact row
+// maximum found in a first sweep (the reference's soft-max argument); 0 = the round-1/2 kernel (16-row wavefronts, two sweeps)
+static int attn_form_env() { static const int form = getenv("WMI_ATTN_FORM") ? atoi(getenv("WMI_ATTN_FORM")) : 2; return form; }
+
+bool attn_encoder_splits_alone(int T, int Tpad, int H, float scale) { return attn_encoder_splits(attn_form_env(), T, Tpad, H, scale, 1); }
+
 void attn_encoder(const __half * q, const __half * k, const __half * vt, int T, int Tpad, int S, int H, float scale,
-                  __half * out, hipStream_t st, int B, float * out32, int qk_chunk_rows, const RowLens * row_lens, int out_chunk_rows) {
-    // WMI_ATTN_FORM: 2 (default) = 32-row wavefronts, one sweep with a running maximum; 1 = the same kernel with the exact row
-    // maximum found in a first sweep (the reference's soft-max argument); 0 = the round-1/2 kernel (16-row wavefronts, two sweeps)
-    static const int form = getenv("WMI_ATTN_FORM") ? atoi(getenv("WMI_ATTN_FORM")) : 2;
+                  __half * out, hipStream_t st, int B, float * out32, int qk_chunk_rows, const RowLens * row_lens, int out_chunk_rows, int split) {
+    const int form = attn_form_env();
     attn_encoder_form(q, k, vt, T, Tpad, S, H, scale, out, st, B, out32, qk_chunk_rows, row_lens, out_chunk_rows, form,
-                      attn_encoder_splits(form, T, Tpad, H, scale, B));
+                      split < 0 ? attn_encoder_splits(form, T, Tpad, H, scale, B) : split != 0);
 }
 
 void attn_decoder(const __half * q, int n, int S, int H, const __half * kc, const __half * vc, int n_kv,

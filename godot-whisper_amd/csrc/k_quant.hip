@@ -1388,6 +1388,11 @@ static int qgemm_f16_rows() {
     static const int v = getenv("WMI_QGEMM_F16_ROWS") ? atoi(getenv("WMI_QGEMM_F16_ROWS")) : 256;
     return v;
 }
+bool qgemm_takes_f16_form(int rows) { return qgemm_f16_rows() > 0 && rows >= qgemm_f16_rows(); }
+// ... and with the caller's word (Q8Rows::form): a stacked pass of chunks with lengths of their own names the form of its chunks' own passes
+static bool rows_take_f16_form(const Q8Rows & A, int M) {
+    return A.form == QFORM_BY_M ? qgemm_takes_f16_form(M) : A.form == QFORM_F16 && qgemm_f16_rows() > 0;
+}
 
 template <int QT>
 static void q8_rows_wdeq_launch(const float * x32, const __half * x16, int M, int K, const float * ln_g, const float * ln_b, float eps,
@@ -1410,7 +1415,7 @@ bool quantize_rows(const float * x32, const __half * x16, int M, int K, const fl
     static const bool fuse = getenv("WMI_QGEMM_NO_FUSED_DEQ") == nullptr;    // A/B knob
     // (a projection whose matrix may be a resident f16 image gets it from qgemm — made on first use — not from this launch)
     static const bool resident_off = !(getenv("WMI_QENC_F16_CACHE") && atoi(getenv("WMI_QENC_F16_CACHE")) != 0);
-    if (fuse && W_next && (resident_off || !out.w_resident_ok) && W_next->tiles && W_next->qtype == qtype && out.deq && out.wdeq && qgemm_f16_rows() > 0 && M >= qgemm_f16_rows() &&
+    if (fuse && W_next && (resident_off || !out.w_resident_ok) && W_next->tiles && W_next->qtype == qtype && out.deq && out.wdeq && rows_take_f16_form(out, M) &&
         (K % 64) == 0 && (N_next % 32) == 0 && (size_t) N_next * K <= out.wdeq_elems) {
         // the projection that follows takes the f16 form: its weight image is written by this launch (qgemm is told through Q8Rows::wdeq_ready)
         switch (qtype) {
@@ -1448,8 +1453,8 @@ void qdequant(QMat W, int64_t row0, int64_t rows, int K, __half * out, hipStream
 }
 
 void qgemm(int epi, const GemmArgs & a, Q8Rows A, QMat W, hipStream_t st) {
-    const int f16_rows = qgemm_f16_rows();
-    if (f16_rows > 0 && a.M >= f16_rows && A.deq && A.wdeq && (a.K % 64) == 0 && (a.N % 32) == 0) {
+    // (the resident-image route and the fused weight image of quantize_rows are inside this branch: both follow the same choice)
+    if (rows_take_f16_form(A, a.M) && A.deq && A.wdeq && (a.K % 64) == 0 && (a.N % 32) == 0) {
         const int64_t cap = (int64_t) (A.wdeq_elems / (size_t) a.K) / 32 * 32;               // weight rows the image holds
         GemmArgs g = a; g.A = A.deq; g.lda = a.K; g.W = A.wdeq; g.ldw = a.K;
         if (!(A.wdeq_ready && A.wdeq_of == (const void *) W.tiles)) {
@@ -1507,7 +1512,10 @@ void qrows(const GemvArgs & a_in, const float * a32, QMat W, hipStream_t st) {
 bool qattn_cross_qsplit_partials(const float * x32, const float * ln_g, const float * ln_b, float eps, QMat Wcq, const float * bq, float qscale,
                                  int n, int S, int H, const __half * kc, const __half * vc, int T, float * scratch,
                                  const float ** po, const float ** pl, const float ** pm, int * pns, hipStream_t st, int64_t kv_row_stride,
-                                 QMat pfW, int pfN, int pfK) {
+                                 QMat pfW, int pfN, int pfK, const RowLens * row_lens) {
+    // rows with lengths of their own: k_xattn_fused_q runs one key range (T) for every row; the two launches (k_qrows + k_xattn_fused with
+    // the lengths) serve them.  Reached only under WMI_Q_XATTN_ROWS (n > 1 is declined below anyway)
+    if (row_lens && row_lens->n) return false;
     static const bool off = getenv("WMI_Q_XATTN_TWO_LAUNCHES") != nullptr;          // A/B knob: cross query as its own k_qrows launch
     // One row only (the greedy step): every (row, head, slice) workgroup unpacks the head's tiles for ITS row, where the k_qrows launch
     // unpacks a tile once for up to eight rows — large-v3 q5_1, beam 5: 44.3 -> 49.3 ms per chunk, 8 lock-step chunks 78.5 -> 87.4 ms per

@@ -226,7 +226,11 @@ void attn_encoder(const __half * q, const __half * k, const __half * vt, int T, 
                   float scale, __half * out, hipStream_t st, int B = 1, float * out32 = nullptr,
                   int qk_chunk_rows = 0,      // rows between the chunks of q and k (0 = T; lock-step chunks start on 16-row boundaries, batch.cpp)
                   const RowLens * row_lens = nullptr,   // B > 1: chunk z attends row_lens->t[z] queries and keys (T = the largest: grid and key split are
-                  int out_chunk_rows = 0);              // decided once per launch by it); out_chunk_rows: rows between the chunks of out (0 = T)
+                  int out_chunk_rows = 0,               // decided once per launch by it); out_chunk_rows: rows between the chunks of out (0 = T)
+                  int split = -1);                      // the key split: -1 by the launch (attn_encoder_splits), 0 / 1 named by the caller
+// would a one-chunk pass of T rows split its keys (attn_encoder at B = 1)?  The block-quantised stacked pass launches its chunks so
+// (device_q.cpp): the activation quantiser amplifies what the other summation order changes
+bool attn_encoder_splits_alone(int T, int Tpad, int H, float scale);
 // the same launch with the form (WMI_ATTN_FORM's values: 2, 1, 0) and the key-group choice given by the caller (split: four key groups
 // of the second form, two of the first) — attn_encoder() is this with the environment's form and attn_encoder_splits()' answer, its rule
 // for the launch (form, largest length, grid); the test hook wmi_selftest_attn_encoder names both itself
@@ -486,9 +490,17 @@ struct QMat { const uint8_t * tiles = nullptr; int qtype = QT_NONE; };
 // deq (optional): the same rows as f16(d * q) [M][K] — the A operand of the f16 form of qgemm; wdeq / wdeq_elems: scratch image for one
 // dequantised weight matrix (or a group of cross K | V layers) [rows][K] f16
 // wdeq_ready: the image already holds the matrix the next qgemm multiplies with (written by quantize_rows' fused launch)
+// The form of a projection over q8 rows: the block-dot kernel (integer dots per block, the reference's arithmetic) or the f16 MFMA form (both
+// operands expanded to f16, k_qdequant).  QFORM_BY_M: the f16 form from WMI_QGEMM_F16_ROWS rows of the LAUNCH on (qgemm_takes_f16_form(M)) —
+// every one-chunk and uniform pass.  The two forms do not give the same bits, so a pass that stacks chunks with lengths of their own names
+// the form each chunk's own one-chunk pass would take (batch.cpp: encode_rows) instead of letting the stacked M decide.
+enum QForm : int { QFORM_BY_M = 0, QFORM_BLOCK_DOT = 1, QFORM_F16 = 2 };
+// the side of the threshold: does a pass of `rows` activation rows take the f16 form when nothing else is said?  (host only)
+bool qgemm_takes_f16_form(int rows);
 struct Q8Rows { int8_t * qs; float * d; float * s; int ldm; __half * deq = nullptr; __half * wdeq = nullptr; size_t wdeq_elems = 0; bool wdeq_ready = false;
                 const void * wdeq_of = nullptr;        // wdeq_of: the matrix (QMat::tiles) whose f16 image wdeq holds when wdeq_ready — qgemm checks it
-                bool w_resident_ok = false; };         // the caller's matrices may be kept as resident f16 images (the encoder's: k_quant.hip qweights_f16_get)
+                bool w_resident_ok = false;            // the caller's matrices may be kept as resident f16 images (the encoder's: k_quant.hip qweights_f16_get)
+                int form = QFORM_BY_M; };              // which form the projection of these rows takes (QForm above): by the launch's M unless the caller names one
 // rows -> q8.  Exactly one source: x32 (+ optional LayerNorm gain/bias: y = LN(x) * g + b in f32, the reference quantises that
 // f32 tensor) or x16 (an f16 tensor, e.g. the GELU output, widened exactly).  out32 / out16: optional copy of the LN result.
 // W_next / N_next (optional): the [N_next][K] matrix of the projection these rows feed.  When that projection will take the f16 form
@@ -513,11 +525,12 @@ void qrows(const GemvArgs & a, const float * a32, QMat W, hipStream_t st);
 bool qrows_ksplit_ok(const GemvArgs & a, int parts);        // may this launch split K over `parts` workgroups per row group (GemvArgs::ksplit)?
 // the cross-attention of a row of a block-quantised model (more rows: WMI_Q_XATTN_ROWS, slower) with the query projection inside (LayerNorm(x32) . W_cq, scaled, f16) — one
 // launch instead of qrows(EPI_Q_SCALED) + attn_cross_split_partials, the same bits; partials as attn_cross_split_partials.  pfW / pfN / pfK:
-// the next weight-streaming launch's matrix (prefetched).  false: not available for this shape (nothing launched; take the two launches)
+// the next weight-streaming launch's matrix (prefetched).  false: not available for this shape (nothing launched; take the two launches) —
+// always so for rows with lengths of their own (row_lens->n > 0): this kernel has one key range for every row
 bool qattn_cross_qsplit_partials(const float * x32, const float * ln_g, const float * ln_b, float eps, QMat Wcq, const float * bq, float qscale,
                                  int n, int S, int H, const __half * kc, const __half * vc, int T, float * scratch,
                                  const float ** po, const float ** pl, const float ** pm, int * pns, hipStream_t st, int64_t kv_row_stride,
-                                 QMat pfW, int pfN, int pfK);
+                                 QMat pfW, int pfN, int pfK, const RowLens * row_lens = nullptr);
 
 // token embedding gather from a quantised matrix: x[i] = dequant(te[token[i]]) + pe[pos[i]]   (W/ggml.c get_rows, dequantize_row_*)
 void qdec_embed(const int32_t * tokens, const int32_t * pos, int n, int S, QMat te, const float * pe, float * x, hipStream_t st);

@@ -414,11 +414,16 @@ template <typename BUFS> inline k::Q8Rows q8_rows(const BUFS & d, int K) {
 }
 bool encode_layers_q(whisper_context & ctx, int T);
 // the same layer loop over caller-supplied buffers: nb chunks stacked along M (lock-step, batch.cpp) — activations [nb*T][S],
-// V^T [nb][S][Tpad], cross cache [L][nb*T][S]
+// V^T [nb][S][Tpad], cross cache [L][nb*T][S].
+// Chunks with lengths of their own (lens.n = nb): T is the largest of them, P the row period of EVERY image (x, the q8 rows, q, k, att32, h,
+// enc_out_h, cross K / V: chunk r starts at row r * P; V^T keeps its Tpad columns), lens the lengths; A.form / A4.form then name the form of
+// the projections (k::QForm: the one each chunk's own pass takes — the caller stacks only chunks on one side of the threshold).
+// P = 0: the period is T (one chunk, chunks of one length).
 struct EncBufsQ {
     int T, nb, Tpad;
     float * x; __half * q, * k, * vt, * h; float * att32; float * enc_out; __half * enc_out_h; __half * kvc_k, * kvc_v;
     k::Q8Rows A, A4;
+    int P; k::RowLens lens;
 };
 bool encode_layers_q_on(whisper_context & ctx, const EncBufsQ & e, hipStream_t s);
 void enqueue_rows_step_q(whisper_context & ctx, int nb);
@@ -496,6 +501,9 @@ int  full(whisper_context & ctx, whisper_full_params params, const float * sampl
 // the per-chunk encoder lengths of wmi_full_batch_ctx / wmi_capture_full_batch: 0, -1 for a negative entry, -5 (with whisper_full's message)
 // for one above the model's n_audio_ctx.  No device work.
 int  check_audio_ctxs(const whisper_context & ctx, const int * audio_ctx, int n, const char * who);
+// the plan of such a call (host only, batch.cpp): order[i] = the chunk at position i (longest first, stable), set_of[i] = the lock-step
+// call that position lands in; returns the number of calls.  eff_T: the chunks' effective lengths (> 0)
+int  lockstep_sets(const int * eff_T, int n, bool quantised, bool per_row, int * order, int * set_of);
 int  full_batch(whisper_context & ctx, whisper_full_params params, const float * const * pcm, const int * n_samples, int n_chunks, bool on_device,
                 const int * audio_ctx = nullptr);       // audio_ctx: an encoder length per chunk (0 = the model's) instead of params.audio_ctx
 void free_batch(whisper_context & ctx);

@@ -204,12 +204,26 @@ WHISPER_API int wmi_full_batch(struct whisper_context * ctx, struct whisper_full
  * lock-step chunks by length (longest first) before dealing them into groups of 16 and into wmi_set_lockstep_groups ranges, and reports
  * results in the caller's order; in the exact mode (wmi_set_lockstep_exact) a chunk's result does not depend on that order, on the other
  * chunks or on the grouping, and equals whisper_full's bit for bit.  With lengths given, a single chunk runs in lock-step form too.
- * Block-quantised models (and the two-launch cross-attention, WMI_XATTN_TWO_PASS) carry ONE length per launch: there the ordered chunks
- * are cut into sets of equal length and each set is a lock-step call of its own — same results, launches shared within a set only;
- * wmi_get_batch_timings then reports the sums over the sets.
+ * Block-quantised models stack their chunks the same way, with one rule more: the projections of a quantised encoder pass run in one of
+ * two forms — the block-dot kernel below WMI_QGEMM_F16_ROWS (256) activation rows, the f16 MFMA form from there on — and the two do not
+ * give the same bits.  In a pass whose rows have lengths of their own every projection takes the form the chunk's own one-chunk pass takes,
+ * not the form the stacked row count would select; so the ordered chunks are cut where their lengths cross that threshold and each side is
+ * a lock-step call of its own: at most two calls (one when all lengths lie on one side — the node's total_time * 50 + 128 reaches 256 from
+ * 2.56 s of audio on).  Each chunk's encoder attention likewise splits its keys as its own pass does (the activation quantiser behind it
+ * amplifies what another summation order changes), so the encoder values of a chunk are its one-chunk pass's in the default mode too.
+ * Calls whose chunks all have one length (audio_ctx == NULL, equal entries) choose by their stacked row count, as ever.
+ * With the two-launch cross-attention (WMI_XATTN_TWO_PASS) the rows carry ONE length per launch: there the ordered chunks are cut into
+ * sets of equal length, each a lock-step call of its own — same results, launches shared within a set only.
+ * wmi_get_batch_timings reports the sums over the calls made; wmi_batch_enc_dims describes the last of them.
  * Any entry above the model's n_audio_ctx: -5 (whisper_full's message); a negative entry: -1; both before any device work. */
 WHISPER_API int wmi_full_batch_ctx(struct whisper_context * ctx, struct whisper_full_params params, const float * const * pcm,
                                    const int * n_samples, const int * audio_ctx, int n_chunks, int pcm_on_device);
+/* The plan of wmi_full_batch_ctx for n chunks with the encoder lengths audio_ctx[0 .. n) (0 = n_audio_ctx) on a model with that n_audio_ctx,
+ * block-quantised or not (host only, no device, no context): order[i] = the chunk at position i of the order the call gives its chunks
+ * (longest first, stable; the caller's order when all lengths are equal), set_of[i] = the lock-step call (0, 1, ...) position i lands in.
+ * wmi_full_batch_ctx plans with the same function.  Returns the number of calls; -1 on a bad argument (NULL, n < 1, n_audio_ctx < 1, an
+ * entry below 0 or above n_audio_ctx). */
+WHISPER_API int wmi_selftest_lockstep_sets(const int * audio_ctx, int n, int n_audio_ctx, int quantised, int * order, int * set_of);
 /* Layout of the last batched encoder pass, for the stage tests: rows, the row period of "batch_enc_x" / "batch_cross_k" / "batch_cross_v"
  * (rows between consecutive chunks; = the common T for a uniform call), and each row's own encoder length into row_T[0 .. rows).
  * Any pointer may be NULL.  -1 when there has been no such pass. */
@@ -403,6 +417,14 @@ WHISPER_API int wmi_selftest_attn_encoder(int device, int B, int T, int Tpad, in
  * touched: S % 64, Tpad % 64, rows_per_chunk > Tpad or not dividing M, out_rows < M); -2 / -3 on a device error. */
 WHISPER_API int wmi_selftest_qkv_encoder(int device, int M, int S, int Tpad, int rows_per_chunk, const uint16_t * xn, const uint16_t * W,
                                          const float * bias, uint32_t sentinel, int out_rows, uint16_t * q, uint16_t * k, uint16_t * vt);
+/* Its block-quantised twin: the block-dot GEMM's q|k|v split epilogue (what a quantised encoder pass launches below the f16 threshold, and a
+ * stacked pass of short chunks at any row count).  x [M][S] f32 rows, quantised to q8 blocks as wmi_selftest_quant does; w_blocks = the ggml
+ * blocks of the [3 S][S] matrix of type `qtype` as a model file holds them; the rest as wmi_selftest_qkv_encoder.  No context.  Returns 0;
+ * -1 bad argument, before the device is touched (an unknown qtype, S % 128, Tpad % 64, rows_per_chunk > Tpad or not dividing M, more than 16
+ * chunks, out_rows < M, a NULL pointer); -2 / -3 on a device error. */
+WHISPER_API int wmi_selftest_qkv_encoder_q(int device, int qtype, int M, int S, int Tpad, int rows_per_chunk, const float * x,
+                                           const void * w_blocks, const float * bias, uint32_t sentinel, int out_rows, uint16_t * q,
+                                           uint16_t * k, uint16_t * vt);
 
 /* Kernel micro-benchmarks on synthetic operands (used by bench.py for the roofline line):
  * runs `iters` launches on the context stream between two HIP events, returns average microseconds.

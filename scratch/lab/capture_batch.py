@@ -10,7 +10,10 @@ no leg replays a captured step graph.  The first --warm steps are dropped; media
 leg the phase split of wmi_get_batch_timings of the last step.  A library without wmi_capture_full_batch (a parent build: --root <its
 tree>) runs the serial leg only.  Prints one JSON line per N.
 
-    python scratch/lab/capture_batch.py [--root DIR] [--shape small] [--steps 12] [--warm 3]
+--quant q5_1 (q4_0 / q4_1 / q5_0 / q8_0): the model block-quantised with synth.quantize_model (BASELINE configs[4] is large-v3 q5_1).  A parent
+build whose batch call cuts the sessions into sets of one length is measured the same way: --root <its tree>.
+
+    python scratch/lab/capture_batch.py [--root DIR] [--shape small] [--quant QTYPE] [--steps 12] [--warm 3]
 """
 import argparse
 import ctypes as C
@@ -28,6 +31,7 @@ ap.add_argument("--shape", default="small")
 ap.add_argument("--steps", type=int, default=12)
 ap.add_argument("--warm", type=int, default=3)
 ap.add_argument("--rate", type=int, default=44100)
+ap.add_argument("--quant", default=None, help="block-quantise the model: q4_0, q4_1, q5_0, q5_1 or q8_0")
 args = ap.parse_args()
 sys.path.insert(0, args.root)
 import __graft_entry__ as entry  # noqa: E402
@@ -39,7 +43,11 @@ lib = runtime.require_gpu()
 runtime.silence_logs(lib)
 node = host.CaptureStreamToText(lib)
 node.language = "en"
-node.set_language_model(synth.make_model(args.shape, seed=1234))
+model = synth.make_model(args.shape, seed=1234)
+if args.quant:
+    model = synth.quantize_model(model, args.quant)
+node.set_language_model(model)
+del model
 has_batch = hasattr(lib, "wmi_capture_full_batch")
 rate, sr = args.rate, 16000
 step = int(round(0.3 * rate))
@@ -101,7 +109,7 @@ for n in (2, 4, 8):
         lib.wmi_get_batch_timings(node.ctx, t4, C.byref(ns))
         phases = {"mel_us": t4[0], "encode_us": t4[1], "decode_us": t4[2], "emit_us": t4[3], "steps": ns.value, "lockstep_rows": node.last_modes.count(0)}
         ctx_last = ctxs
-    out = {"shape": args.shape, "speakers": n, "steps_timed": args.steps, "accumulated_s_at_end": [round(p / rate, 1) for p in pos],
+    out = {"shape": args.shape + (" " + args.quant if args.quant else ""), "speakers": n, "steps_timed": args.steps, "accumulated_s_at_end": [round(p / rate, 1) for p in pos],
            "audio_ctx_last_step": ctx_last, "serial": summary(t_serial)}
     if has_batch:
         out["batch"] = summary(t_batch)
