@@ -1104,6 +1104,113 @@ int wmi_selftest_qkv_encoder(int device, int M, int S, int Tpad, int rows_per_ch
     return ok ? 0 : -3;
 }
 
+static void gemm_plan_out(const k::GemmPlan & p, int * out) {
+    const int v[10] = {p.kernel, p.bm, p.bn, p.waves, p.ring, p.ring_w, p.dma, p.orient, p.ks, p.epi};
+    for (int i = 0; i < 10; ++i) out[i] = v[i];
+}
+
+int wmi_selftest_gemm_plan(int epi, int M, int N, int K, int S, int n_cu, int * out) {
+    if (!out || M < 1 || N < 1 || K < 32 || (K % 32) != 0 || S < 0 || n_cu < 0) return -1;
+    k::GemmArgs a{};
+    a.M = M; a.N = N; a.K = K; a.S = S;
+    const k::GemmPlan p = k::gemm_plan(epi, a, n_cu);
+    if (!p.kernel) return -1;
+    gemm_plan_out(p, out);
+    return 0;
+}
+
+int wmi_selftest_gemm(int device, int epi, int M, int N, int K, int lda, int S, float scale, int n_layers, int rows_per_chunk, int conv2_out_rows,
+                      int Tpad, int ld_pad, int in_place, int force8_bm, const uint16_t * A, const uint16_t * W, const float * bias,
+                      const float * resid, uint32_t sentinel, int out_rows, void * C, void * aux, void * aux2, int * plan_out) {
+    // everything a launch could read or write out of bounds with is refused before the device is touched
+    if (epi < k::EPI_F16_BIAS || epi > k::EPI_Q_SCALED || M < 1 || N < 4 || (N % 4) != 0 || K < 32 || (K % 32) != 0 || lda < 1) return -1;
+    if (ld_pad < 0 || (ld_pad % 8) != 0 || out_rows < M + 16 || rows_per_chunk < 0 || conv2_out_rows < 0 || !A || !W || !C || !plan_out) return -1;
+    if ((size_t) M * (size_t) lda + (size_t) K >= (1u << 30) || (size_t) N * (size_t) K >= (1u << 30) || out_rows > (1 << 20)) return -1;
+    const bool f32out = epi == k::EPI_F32_BIAS_RESID || epi == k::EPI_CONV2;
+    const bool split = epi == k::EPI_QKV_ENC || epi == k::EPI_QKV_DEC || epi == k::EPI_CROSS_KV;
+    const bool takes_resid = f32out;
+    if (takes_resid != (resid != nullptr) || (in_place && epi != k::EPI_F32_BIAS_RESID)) return -1;
+    if (split && (S < 64 || (S % 64) != 0)) return -1;
+    if (!split && (S != 0 || n_layers != 0)) return -1;
+    if ((epi == k::EPI_QKV_ENC || epi == k::EPI_QKV_DEC) && (N != 3 * S || n_layers != 0 || !aux || !aux2 || !bias)) return -1;
+    if (epi == k::EPI_CROSS_KV && (n_layers < 1 || N != n_layers * 2 * S || !aux || aux2 || !bias)) return -1;
+    if (epi != k::EPI_QKV_ENC && epi != k::EPI_QKV_DEC && aux2) return -1;
+    if (epi != k::EPI_CONV2 && !split && aux) return -1;
+    if (epi != k::EPI_CONV2 && conv2_out_rows != 0) return -1;
+    if (epi != k::EPI_CONV2 && epi != k::EPI_QKV_ENC && rows_per_chunk != 0) return -1;
+    if ((epi == k::EPI_QKV_ENC) != (Tpad != 0)) return -1;
+    int chunks = 1, pe_rows = M;
+    if (epi == k::EPI_QKV_ENC) {
+        const int rpc = rows_per_chunk > 0 ? rows_per_chunk : M;
+        if (Tpad < 64 || (Tpad % 64) != 0 || rpc > Tpad || (M % rpc) != 0 || M / rpc > 16) return -1;
+        chunks = M / rpc;
+    }
+    if (epi == k::EPI_CONV2 && rows_per_chunk > 0) {
+        const int P = rows_per_chunk, O = conv2_out_rows > 0 ? conv2_out_rows : P - 4;
+        if (P < 5 || O < P - 4) return -1;
+        chunks = (M + P - 1) / P; pe_rows = P - 4;
+        if ((size_t) chunks * O > (size_t) out_rows) return -1;      // the last chunk's rows c O + t, t < P - 4
+    }
+    const int ks8 = force8_bm == 288 ? 32 : 64;
+    k::GemmArgs a{};
+    a.M = M; a.N = N; a.K = K; a.S = S; a.lda = lda; a.ldw = K;
+    if (force8_bm != 0 && !k::gemm8_plan(epi, force8_bm, true, a, ks8).kernel) return -1;
+    if (!HIP_OK(hipSetDevice(device))) return -2;
+
+    const int ld = (split ? S : N) + ld_pad, layers = epi == k::EPI_CROSS_KV ? n_layers : 1;
+    const size_t esz = f32out ? 4 : 2;
+    const size_t n_a = (size_t) (M - 1) * lda + K, n_w = (size_t) N * K;
+    const size_t n_c = (size_t) layers * out_rows * ld;                                  // C, and aux / aux2 where they are row images
+    const size_t n_vt = epi == k::EPI_QKV_ENC ? (size_t) chunks * S * Tpad : 0;
+    const size_t n_resid = epi == k::EPI_CONV2 ? (size_t) pe_rows * N : (size_t) M * N;
+    std::vector<unsigned char> pre(std::max(n_c, n_vt) * esz);
+    if (f32out) for (size_t i = 0; i < pre.size() / 4; ++i) memcpy(pre.data() + 4 * i, &sentinel, 4);
+    else { const uint16_t s16 = (uint16_t) sentinel; for (size_t i = 0; i < pre.size() / 2; ++i) memcpy(pre.data() + 2 * i, &s16, 2); }
+    std::vector<unsigned char> pre_c;                        // in place: the residual sits in C's rows [0, M), columns [0, N)
+    if (in_place) {
+        pre_c.assign(pre.begin(), pre.begin() + n_c * 4);
+        for (int m = 0; m < M; ++m) memcpy(pre_c.data() + (size_t) m * ld * 4, resid + (size_t) m * N, (size_t) N * 4);
+    }
+    __half * d_a = nullptr, * d_w = nullptr; float * d_b = nullptr, * d_r = nullptr; unsigned char * d_c = nullptr, * d_x = nullptr, * d_x2 = nullptr;
+    hipStream_t st = nullptr;
+    const size_t x2_bytes = epi == k::EPI_QKV_ENC ? n_vt * 2 : n_c * 2;
+    bool ok = HIP_OK(hipMalloc((void **) &d_a, n_a * 2)) && HIP_OK(hipMalloc((void **) &d_w, n_w * 2)) && HIP_OK(hipMalloc((void **) &d_c, n_c * esz)) &&
+              HIP_OK(hipStreamCreate(&st));
+    if (bias) ok = ok && HIP_OK(hipMalloc((void **) &d_b, (size_t) N * 4)) && HIP_OK(hipMemcpy(d_b, bias, (size_t) N * 4, hipMemcpyHostToDevice));
+    if (resid && !in_place) ok = ok && HIP_OK(hipMalloc((void **) &d_r, n_resid * 4)) && HIP_OK(hipMemcpy(d_r, resid, n_resid * 4, hipMemcpyHostToDevice));
+    if (aux) ok = ok && HIP_OK(hipMalloc((void **) &d_x, n_c * esz)) && HIP_OK(hipMemcpy(d_x, pre.data(), n_c * esz, hipMemcpyHostToDevice));
+    if (aux2) ok = ok && HIP_OK(hipMalloc((void **) &d_x2, x2_bytes)) && HIP_OK(hipMemcpy(d_x2, pre.data(), x2_bytes, hipMemcpyHostToDevice));
+    ok = ok && HIP_OK(hipMemcpy(d_a, A, n_a * 2, hipMemcpyHostToDevice)) && HIP_OK(hipMemcpy(d_w, W, n_w * 2, hipMemcpyHostToDevice)) &&
+         HIP_OK(hipMemcpy(d_c, in_place ? pre_c.data() : pre.data(), n_c * esz, hipMemcpyHostToDevice));
+    if (ok) {
+        // as encode() (device.cpp), encode_rows() (batch.cpp) and the decoder's proj (device.cpp) fill it; the leading dimensions carry ld_pad
+        a.A = d_a; a.W = d_w; a.bias = d_b; a.C = d_c; a.ldc = ld; a.scale = scale;
+        if (epi == k::EPI_F32_BIAS_RESID) { a.resid = in_place ? (const float *) d_c : d_r; a.ldr = in_place ? ld : N; }
+        if (epi == k::EPI_CONV2) { a.resid = d_r; a.ldr = N; a.aux = d_x; a.ldaux = ld; a.rows_per_chunk = rows_per_chunk; a.conv2_out_rows = conv2_out_rows; }
+        if (epi == k::EPI_QKV_ENC) {
+            a.aux = d_x; a.ldaux = ld; a.aux2 = d_x2; a.ldaux2 = Tpad;
+            if (rows_per_chunk > 0) { a.rows_per_chunk = rows_per_chunk; a.chunk_stride_aux2 = (int64_t) S * Tpad; }
+        }
+        if (epi == k::EPI_QKV_DEC) { a.aux = d_x; a.ldaux = ld; a.aux2 = d_x2; a.ldaux2 = ld; }
+        if (epi == k::EPI_CROSS_KV) { a.aux = d_x; a.ldaux = ld; a.layer_stride = (int64_t) out_rows * ld; }
+        if (force8_bm != 0) {
+            gemm_plan_out(k::gemm8_plan(epi, force8_bm, true, a, ks8), plan_out);
+            ok = k::gemm8(epi, force8_bm, true, a, st, ks8);
+        } else {
+            gemm_plan_out(k::gemm_plan(epi, a, k::cu_count_x8()), plan_out);
+            k::gemm(epi, a, st);
+        }
+        plan_out[10] = k::cu_count_x8();
+        ok = ok && HIP_OK(hipStreamSynchronize(st)) && HIP_OK(hipGetLastError());
+        ok = ok && HIP_OK(hipMemcpy(C, d_c, n_c * esz, hipMemcpyDeviceToHost));
+        if (aux) ok = ok && HIP_OK(hipMemcpy(aux, d_x, n_c * esz, hipMemcpyDeviceToHost));
+        if (aux2) ok = ok && HIP_OK(hipMemcpy(aux2, d_x2, x2_bytes, hipMemcpyDeviceToHost));
+    }
+    if (st) (void) hipStreamDestroy(st);
+    (void) hipFree(d_a); (void) hipFree(d_w); (void) hipFree(d_b); (void) hipFree(d_r); (void) hipFree(d_c); (void) hipFree(d_x); (void) hipFree(d_x2);
+    return ok ? 0 : -3;
+}
+
 int wmi_selftest_qkv_encoder_q(int device, int qtype, int M, int S, int Tpad, int rows_per_chunk, const float * x, const void * w_blocks,
                                const float * bias, uint32_t sentinel, int out_rows, uint16_t * q, uint16_t * k, uint16_t * vt) {
     const k::QGeom geo = k::q_geom(qtype);

@@ -121,12 +121,12 @@ __global__ __launch_bounds__(NW * 64) void k_gemm(const GemmArgs a) {
     // conv 13.1 / 14.3) and at M = 12 000 for GELU (44.9 / 49.6) and cross K/V (142 / 150), but LOSES there for q|k|v (50.3 against
     // 43.7 us) and the residual epilogues (44.6 / 43.2 on 128 x 128 tiles, 23.9 / 21.6 on 64 x 64): those keep the first orientation
     // on the big grids.  Workgroup-uniform, both epilogues are compiled.
-    const bool big = a.M >= 4096;
     // (round 5, with the full-line stores of epilogue_cols_wide: the q and k thirds in the transposed form on the big grids measure the
     //  same as the first orientation — 41.3-41.8 against 40.9-41.2 us, profiles/r05b_gemm_lab_qkv.txt: the V^T third's scattered 8-byte
     //  stores are what the q|k|v epilogue costs over a plain one (34.5 us) — so the round-3 choice stays; a.no_glds bit 8 =
     //  WMI_GEMM_QKV_SWAP is the A/B knob)
-    const bool swap = SWAP && !(EPI == EPI_QKV_ENC && (n0 >= 2 * a.S || (big && !(a.no_glds & 8)))) && !(EPI == EPI_F32_BIAS_RESID && big && !(a.no_glds & 32));
+    const bool big = WMI_GEMM_BIG_GRID(a.M);
+    const bool swap = SWAP && WMI_GEMM_TILE_TRANSPOSED(EPI, big, a.no_glds, n0 >= 2 * a.S);     // (kernels.h: gemm_plan() reports the rule)
     auto compute = [&](int buf, auto sw_tag) {
         constexpr bool SWF = decltype(sw_tag)::value;
 #pragma unroll
@@ -154,7 +154,7 @@ __global__ __launch_bounds__(NW * 64) void k_gemm(const GemmArgs a) {
     auto k_loops = [&](auto sw_tag) {
     // 64x64 tiles take the same path while the grid is small (one chunk: latency-bound, -11..15 % per GEMM); with
     // thousands of small tiles the register-staged loop is the faster one (measured, scratch/lab/gemm_lab.hip)
-    if ((BM >= 96 || nwg <= 1024) && (a.K % BK) == 0 && !(a.no_glds & 1)) {
+    if (WMI_GEMM_TAKES_DMA_RING(BM, nwg, a.K, a.no_glds)) {            // (kernels.h: shared with gemm_plan())
         // Large tiles (batched encoder, cross K/V): operands go global -> LDS directly (global_load_lds, 16 B per lane,
         // 1 KiB per wave instruction, no staging VGPRs or ds_write pass).  LDS is written lane-linearly, so the XOR
         // swizzle is applied to each lane's GLOBAL address instead: position p = row*8 + (chunk ^ (row & 7)) of a
@@ -257,39 +257,42 @@ void launch_n(const GemmArgs & a, hipStream_t st) {
     allow_full_lds((const void *) k_gemm<BM, BN, EPI, NST, NW>, lds_ok);
     hipLaunchKernelGGL((k_gemm<BM, BN, EPI, NST, NW>), dim3(ntm * ntn), dim3(NW * 64), smem, st, a);
 }
-template <int BM, int BN, int EPI>
-void launch(const GemmArgs & a, hipStream_t st) {
-    const long nwg = (long) ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN);
+// ---- the dispatch rule: which tile, ring and loop serve (epilogue, M, N, K).  Pure arithmetic: gemm_plan() below.
+GemmPlan tile(int epi, const GemmArgs & a, int bm, int bn, int ring, int waves = 4) {
+    GemmPlan p;
+    p.epi = epi; p.kernel = 1; p.bm = bm; p.bn = bn; p.waves = waves; p.ring = p.ring_w = ring; p.ks = BK;
+    const int nwg = ((a.M + bm - 1) / bm) * ((a.N + bn - 1) / bn);
+    p.dma = WMI_GEMM_TAKES_DMA_RING(bm, nwg, a.K, a.no_glds) ? 1 : 0;
+    p.orient = gemm_orient_rule(epi, a.M, a.no_glds);
+    return p;
+}
+GemmPlan tile_by_grid(int epi, const GemmArgs & a, int bm, int bn) {
+    const long nwg = (long) ((a.M + bm - 1) / bm) * ((a.N + bn - 1) / bn);
     // (a 3-deep ring for the grids in between — q|k|v 576, mlp.0 768 tiles — measured the same as 2)
-    if (BM < 128 && nwg <= 400) launch_n<BM, BN, EPI, 4>(a, st);
-    else                        launch_n<BM, BN, EPI, 2>(a, st);
+    return tile(epi, a, bm, bn, bm < 128 && nwg <= 400 ? 4 : 2);
 }
 
-template <int EPI>
-void dispatch(const GemmArgs & a, hipStream_t st) {
+GemmPlan plan_tiles(int epi, const GemmArgs & a) {
     // 256 CUs: prefer the 128x128 tile only when it still yields >= ~1.5 waves of workgroups
     const long t128 = (long) ((a.M + 127) / 128) * ((a.N + 127) / 128);
     const long t64 = (long) ((a.M + 63) / 64) * ((a.N + 63) / 64);
-    // WMI_GEMM_WIDE=1 (A/B knob, off): 128 x 256 tiles on eight wavefronts with a three-deep ring for the big grids (lock-step encoder,
+    // WMI_GEMM_WIDE=1 (A/B knob, off; a.no_glds bit 64): 128 x 256 tiles on eight wavefronts with a three-deep ring for the big grids (lock-step encoder,
     // M = chunks x T).  Measured (profiles/r03b_gemm_wide_tile_and_gelu.txt): mlp.0 x 8 45.8 us against 43.5 us for two co-resident
     // 128 x 128 workgroups per CU — its K loop takes 7.9 us per 128 x 256 tile against 7.3 us per PAIR of 128 x 128 tiles, so the loop is
     // not waiting for operands to arrive (twice the bytes in flight changed nothing); it is bound by LDS traffic per MFMA (16 fragment
     // reads per 32 MFMAs of a wavefront + the DMA writes: ~900 LDS cycles per 1024 MFMA cycles of a SIMD).
-    static const int wide = getenv("WMI_GEMM_WIDE") ? atoi(getenv("WMI_GEMM_WIDE")) : 0;
     const long t256 = (long) ((a.M + 127) / 128) * (a.N / 256);
-    if constexpr (EPI == EPI_F16_BIAS_GELU || EPI == EPI_QKV_ENC || EPI == EPI_CROSS_KV || EPI == EPI_F16_BIAS) {
-        if (wide && (a.N % 256) == 0 && t256 >= 384 && (a.K % BK) == 0 && !(a.no_glds & 1)) { launch_n<128, 256, EPI, 3, 8>(a, st); return; }
+    if (epi == EPI_F16_BIAS_GELU || epi == EPI_QKV_ENC || epi == EPI_CROSS_KV || epi == EPI_F16_BIAS) {
+        if ((a.no_glds & 64) && (a.N % 256) == 0 && t256 >= 384 && (a.K % BK) == 0 && !(a.no_glds & 1)) return tile(epi, a, 128, 256, 3, 8);
     }
     // Round 6: the N = S projections of the big grids (out, mlp.2 at M = chunks x 1500) on 192 x 128 tiles, ONE workgroup of eight wavefronts per CU
     // on a three-deep ring: 252 tiles at 8 chunks = one round, 76.8 flop per operand byte against 54.9 for two co-resident 96 x 128 workgroups.
     // Measured at 8 chunks (profiles/r06e_*): mlp.2 40.3 -> 34.2 us, out 15.5 -> 13.8; 16 chunks mlp.2 75.6 -> 72.2; 4 chunks mlp.2 34.3 -> 28.2 but
     // out 9.2 -> 10.6 (128 tiles: half the chip) — so the short-K projection takes it only with >= 200 tiles.  Ring depth: two 40.0, three 35.8, four
     // (all 160 KB of LDS) 33.4 - 34.8 us for mlp.2; four wavefronts 42.1; the conv front-end on this tile 33.3 - 33.9 against 33.4 - 34.7 us (stays).
-    if constexpr (EPI == EPI_F32_BIAS_RESID) {
+    if (epi == EPI_F32_BIAS_RESID) {
         const long t192 = (long) ((a.M + 191) / 192) * (a.N / 128);
-        if (a.M >= 4096 && a.N <= 1024 && (a.N % 128) == 0 && (a.K % BK) == 0 && !(a.no_glds & 1) && (a.K >= 1024 || t192 >= 200)) {
-            launch_n<192, 128, EPI, 4, 8>(a, st); return;
-        }
+        if (a.M >= 4096 && a.N <= 1024 && (a.N % 128) == 0 && (a.K % BK) == 0 && !(a.no_glds & 1) && (a.K >= 1024 || t192 >= 200)) return tile(epi, a, 192, 128, 4, 8);
     }
     // 376 tiles (out projection at M = 12 000): 18.6 us against 23.0 us as 1 504 tiles of 64 x 64
     if (t128 >= 320 || (t128 >= 256 && a.K >= 1024)) {
@@ -298,23 +301,35 @@ void dispatch(const GemmArgs & a, hipStream_t st) {
         // 500: whole rounds.  Taken when they fill the rounds better by more than their ~5 % lower operand reuse costs.
         // (round 6: the conv front-end's big grids on 96-row tiles too — conv2 x8 is 376 tiles of 128 rows = 0.73 of the 512 resident slots, 504 of 96
         //  rows fill them: 38.5 -> 33.4 us, conv1 18.6 -> 17.6)
-        if constexpr (EPI == EPI_QKV_ENC || EPI == EPI_F32_BIAS_RESID || EPI == EPI_CONV2 || EPI == EPI_F16_BIAS_GELU) {
+        if (epi == EPI_QKV_ENC || epi == EPI_F32_BIAS_RESID || epi == EPI_CONV2 || epi == EPI_F16_BIAS_GELU) {
             const long t96 = (long) ((a.M + 95) / 96) * ((a.N + 127) / 128);
             auto fill = [](long t) { return (double) t / (double) (((t + 511) / 512) * 512); };
-            if (a.M >= 4096 && (a.K % BK) == 0 && fill(t96) > fill(t128) + 0.08) { launch_n<96, 128, EPI, 2>(a, st); return; }
+            if (a.M >= 4096 && (a.K % BK) == 0 && fill(t96) > fill(t128) + 0.08) return tile(epi, a, 96, 128, 2);
         }
-        launch<128, 128, EPI>(a, st);
+        return tile_by_grid(epi, a, 128, 128);
     }
-    else if constexpr (EPI == EPI_F32_BIAS_RESID) {
+    if (epi == EPI_F32_BIAS_RESID) {
         // The N = S projections of the widest models at one chunk (large-v3: 1500 x 1280, K = 1280 / 5120): 240 tiles of 64 x 128 on a four-deep ring
         // instead of 480 of 64 x 64 — a quarter fewer LDS fragment reads per flop.  Measured on the large-v3 q5_1 encoder (64 of these GEMMs):
         // 6.85 -> 6.70 ms; 128 x 64 tiles 6.83, 64 x 128 on a two-deep ring 6.99 (profiles/r03c_gemm_ns_tile.txt).
-        if (a.K >= 1024 && (a.N % 128) == 0 && (a.K % BK) == 0 && t64 >= 400 && !(a.no_glds & 1)) { launch_n<64, 128, EPI, 4>(a, st); return; }
+        if (a.K >= 1024 && (a.N % 128) == 0 && (a.K % BK) == 0 && t64 >= 400 && !(a.no_glds & 1)) return tile(epi, a, 64, 128, 4);
         // one chunk, N = S: 64x64 tiles give fewer workgroups than CUs (192 for base.en) and each walks K alone with nothing to
         // overlap its loads; 64x32 tiles double the workgroups
-        if (t64 < 256) launch<64, 32, EPI>(a, st); else launch<64, 64, EPI>(a, st);
+        return t64 < 256 ? tile_by_grid(epi, a, 64, 32) : tile_by_grid(epi, a, 64, 64);
     }
-    else             launch<64, 64, EPI>(a, st);
+    return tile_by_grid(epi, a, 64, 64);
+}
+
+// ---- the launch of a k_gemm plan: the instantiations the rule above can name, per epilogue
+template <int EPI>
+bool launch_tiles(const GemmPlan & p, const GemmArgs & a, hipStream_t st) {
+#define WMI_TILE(BM, BN, NST, NW) if (p.bm == BM && p.bn == BN && p.ring == NST && p.waves == NW) { launch_n<BM, BN, EPI, NST, NW>(a, st); return true; }
+    WMI_TILE(64, 64, 4, 4) WMI_TILE(64, 64, 2, 4) WMI_TILE(128, 128, 2, 4)
+    if constexpr (EPI == EPI_F16_BIAS_GELU || EPI == EPI_QKV_ENC || EPI == EPI_CROSS_KV || EPI == EPI_F16_BIAS) { WMI_TILE(128, 256, 3, 8) }
+    if constexpr (EPI == EPI_QKV_ENC || EPI == EPI_F32_BIAS_RESID || EPI == EPI_CONV2 || EPI == EPI_F16_BIAS_GELU) { WMI_TILE(96, 128, 2, 4) }
+    if constexpr (EPI == EPI_F32_BIAS_RESID) { WMI_TILE(192, 128, 4, 8) WMI_TILE(64, 128, 4, 4) WMI_TILE(64, 32, 4, 4) WMI_TILE(64, 32, 2, 4) }
+#undef WMI_TILE
+    return false;
 }
 
 } // namespace
@@ -322,22 +337,9 @@ void dispatch(const GemmArgs & a, hipStream_t st) {
 static thread_local GemmLog * tl_gemm_log = nullptr;
 void gemm_log_install(GemmLog * log) { tl_gemm_log = log; }
 
-void gemm(int epi, const GemmArgs & a_in, hipStream_t st) {
-    static const bool no_glds = getenv("WMI_GEMM_NO_GLDS") != nullptr;       // debug / A-B: register-staged loop for every tile size
-    static const bool guard_all = getenv("WMI_GEMM_GUARD_ALL") != nullptr;   // debug / A-B: bounds-checked epilogue for every tile
-    static const bool narrow = getenv("WMI_GEMM_NARROW_STORES") != nullptr;  // debug / A-B: 8-byte epilogue stores
-    static const bool qkv_swap = getenv("WMI_GEMM_QKV_SWAP") != nullptr;    // debug / A-B: q and k thirds of the big q|k|v grids in the transposed orientation
-    static const bool resid_swap = getenv("WMI_GEMM_RESID_SWAP") != nullptr;   // debug / A-B: the residual epilogues of the big grids in the transposed orientation (16-byte f32 stores)
-    static const bool vt_narrow = getenv("WMI_GEMM_VT_NARROW") != nullptr;  // debug / A-B: the V^T third of the encoder's q|k|v as 8-byte stores
-    GemmArgs a = a_in; a.no_glds = (no_glds ? 1 : 0) | (guard_all ? 2 : 0) | (narrow ? 4 : 0) | (qkv_swap ? 8 : 0) | (vt_narrow ? 16 : 0) | (resid_swap ? 32 : 0);
-    if (GemmLog * lg = tl_gemm_log) {
-        const size_t wgs = (size_t) ((a.M + 63) / 64) * (size_t) ((a.N + 31) / 32);     // the smallest tile any dispatch below uses is 64 x 32
-        if (!a.probe && lg->used + wgs * 5 <= lg->cap_words) {
-            a.probe = lg->buf + lg->used;
-            lg->entries.push_back(GemmLogEntry{epi, a.M, a.N, a.K, lg->used, (int) wgs});
-            lg->used += wgs * 5;
-        }
-    }
+GemmPlan gemm_plan(int epi, const GemmArgs & a, int n_cu) {
+    if (epi < EPI_F16_BIAS || epi > EPI_Q_SCALED || a.M < 1 || a.N < 1 || a.K < 1) return GemmPlan{};
+    const bool no_glds = (a.no_glds & 1) != 0;
     // The big grids (lock-step encoder: M = chunks x 1500) whose output is wide enough for several 192 x 256 tiles per CU go to the
     // persistent ping-pong kernel (k_gemm8.hip): mlp.0 (N = 4 S) and the cross K / V of all decoder layers (N = 2 L S).  Measured at
     // M = 12 000 (profiles/r04a_gemm8_lab_*): mlp.0 41 -> 35.7 us, cross K/V 132 -> 105 us, every output element identical.  The N = S
@@ -346,28 +348,61 @@ void gemm(int epi, const GemmArgs & a_in, hipStream_t st) {
         (epi != EPI_CROSS_KV || (a.S % 64) == 0)) {
         const long t192 = (long) ((a.M + 191) / 192) * (a.N / 256);
         // (round 6: 288-row tiles for these two measured slower — cross K/V 90.4 against 85.0 us, mlp.0 43.5 against 32.7: profiles/r06c_*)
-        if (t192 >= 384) { GemmArgs b = a; b.no_glds = a.no_glds & 16; if (gemm8(epi, 192, true, b, st)) return; }
+        if (t192 >= 384) { const GemmPlan p = gemm8_plan(epi, 192, true, a, 64); if (p.kernel) return p; }
     }
     // (q|k|v stays below: on 288-row tiles — 42 x 6 = 252, ONE round at M = 12 000 — the persistent kernel measures 41.1 us against 41.0 us
     //  here, in situ 37.5 against 37.4: the V^T third's epilogue decides, not the tiling)
     // (round 6: with the V^T third leaving in whole lines — gemm_epi.h: epilogue_vt_wide, chunks on 16-row boundaries — the tiling decides again:
     //  288-row tiles in whole rounds of the persistent kernel)
-    if (!no_glds && epi == EPI_QKV_ENC && a.M >= 4096 && (a.N % 256) == 0 && (a.K % 64) == 0 && a.S > 0 && (a.S % 128) == 0 && a.N == 3 * a.S) {
+    if (!no_glds && epi == EPI_QKV_ENC && a.M >= 4096 && (a.N % 256) == 0 && (a.K % 64) == 0 && a.S > 0 && (a.S % 128) == 0 && a.N == 3 * a.S && n_cu > 0) {
         const long t288 = (long) ((a.M + 287) / 288) * (a.N / 256);
-        const long n_cu = cu_count_x8(), rounds = (t288 + n_cu - 1) / n_cu;
-        if (t288 * 5 >= rounds * n_cu * 4) { GemmArgs b = a; b.no_glds = a.no_glds & 16; if (gemm8(epi, 288, true, b, st, 32)) return; }
+        const long rounds = (t288 + n_cu - 1) / n_cu;
+        if (t288 * 5 >= rounds * n_cu * 4) { const GemmPlan p = gemm8_plan(epi, 288, true, a, 32); if (p.kernel) return p; }
     }
-    switch (epi) {
-        case EPI_F16_BIAS:       dispatch<EPI_F16_BIAS>(a, st); break;
-        case EPI_F16_BIAS_GELU:  dispatch<EPI_F16_BIAS_GELU>(a, st); break;
-        case EPI_F32_BIAS_RESID: dispatch<EPI_F32_BIAS_RESID>(a, st); break;
-        case EPI_CONV2:          dispatch<EPI_CONV2>(a, st); break;
-        case EPI_QKV_ENC:        dispatch<EPI_QKV_ENC>(a, st); break;
-        case EPI_QKV_DEC:        dispatch<EPI_QKV_DEC>(a, st); break;
-        case EPI_CROSS_KV:       dispatch<EPI_CROSS_KV>(a, st); break;
-        case EPI_Q_SCALED:       dispatch<EPI_Q_SCALED>(a, st); break;
+    return plan_tiles(epi, a);
+}
+
+// gemm() without its knobs and its probe log: the launch of a plan
+static void gemm_launch(const GemmPlan & p, const GemmArgs & a, hipStream_t st) {
+    if (p.kernel == 8) {
+        GemmArgs b = a; b.no_glds = a.no_glds & 16;
+        if (gemm8(p.epi, p.bm, true, b, st, p.ks)) return;
+        gemm_launch(plan_tiles(p.epi, a), a, st);          // (not reached: gemm8_plan() named a kernel gemm8() has)
+        return;
+    }
+    if (p.kernel != 1) return;
+    switch (p.epi) {
+        case EPI_F16_BIAS:       launch_tiles<EPI_F16_BIAS>(p, a, st); break;
+        case EPI_F16_BIAS_GELU:  launch_tiles<EPI_F16_BIAS_GELU>(p, a, st); break;
+        case EPI_F32_BIAS_RESID: launch_tiles<EPI_F32_BIAS_RESID>(p, a, st); break;
+        case EPI_CONV2:          launch_tiles<EPI_CONV2>(p, a, st); break;
+        case EPI_QKV_ENC:        launch_tiles<EPI_QKV_ENC>(p, a, st); break;
+        case EPI_QKV_DEC:        launch_tiles<EPI_QKV_DEC>(p, a, st); break;
+        case EPI_CROSS_KV:       launch_tiles<EPI_CROSS_KV>(p, a, st); break;
+        case EPI_Q_SCALED:       launch_tiles<EPI_Q_SCALED>(p, a, st); break;
         default: break;
     }
+}
+
+void gemm(int epi, const GemmArgs & a_in, hipStream_t st) {
+    static const bool no_glds = getenv("WMI_GEMM_NO_GLDS") != nullptr;       // debug / A-B: register-staged loop for every tile size
+    static const bool guard_all = getenv("WMI_GEMM_GUARD_ALL") != nullptr;   // debug / A-B: bounds-checked epilogue for every tile
+    static const bool narrow = getenv("WMI_GEMM_NARROW_STORES") != nullptr;  // debug / A-B: 8-byte epilogue stores
+    static const bool qkv_swap = getenv("WMI_GEMM_QKV_SWAP") != nullptr;    // debug / A-B: q and k thirds of the big q|k|v grids in the transposed orientation
+    static const bool resid_swap = getenv("WMI_GEMM_RESID_SWAP") != nullptr;   // debug / A-B: the residual epilogues of the big grids in the transposed orientation (16-byte f32 stores)
+    static const bool vt_narrow = getenv("WMI_GEMM_VT_NARROW") != nullptr;  // debug / A-B: the V^T third of the encoder's q|k|v as 8-byte stores
+    static const bool wide = getenv("WMI_GEMM_WIDE") && atoi(getenv("WMI_GEMM_WIDE")) != 0;      // debug / A-B: 128 x 256 tiles for the big grids (plan_tiles)
+    GemmArgs a = a_in; a.no_glds = (no_glds ? 1 : 0) | (guard_all ? 2 : 0) | (narrow ? 4 : 0) | (qkv_swap ? 8 : 0) | (vt_narrow ? 16 : 0) | (resid_swap ? 32 : 0) | (wide ? 64 : 0);
+    if (GemmLog * lg = tl_gemm_log) {
+        const size_t wgs = (size_t) ((a.M + 63) / 64) * (size_t) ((a.N + 31) / 32);     // the smallest tile any dispatch below uses is 64 x 32
+        if (!a.probe && lg->used + wgs * 5 <= lg->cap_words) {
+            a.probe = lg->buf + lg->used;
+            lg->entries.push_back(GemmLogEntry{epi, a.M, a.N, a.K, lg->used, (int) wgs});
+            lg->used += wgs * 5;
+        }
+    }
+    // (the CU count decides for the big q|k|v grids alone)
+    gemm_launch(gemm_plan(epi, a, epi == EPI_QKV_ENC && a.M >= 4096 ? cu_count_x8() : 0), a, st);
 }
 
 }} // namespace wmi::k

@@ -332,6 +332,19 @@ void launch8(const GemmArgs & a, hipStream_t st) {
 // bm: rows per tile; ks: k extent of a slot (32 or 64).  false = this epilogue / shape / tile is not served here (the caller keeps gemm()).
 // The library instantiates what its dispatch uses (k_gemm.hip: gemm()): the transposed orientation on 192-row tiles (128 as the fallback
 // for narrower outputs) for the GELU and cross K/V epilogues; the lab (scratch/lab/gemm8_lab.hip) builds the whole grid of variants.
+// what the library's gemm8() launches (the table below, without the launch): kernel = 0 where it is not served
+GemmPlan gemm8_plan(int epi, int bm, bool swapped, const GemmArgs & a, int ks) {
+    GemmPlan p;
+    if ((a.N % 256) != 0 || (a.K % 64) != 0 || a.M < 1 || !swapped) return p;
+    const bool qkv288 = epi == EPI_QKV_ENC && bm == 288 && ks == 32;
+    const bool wide192 = (epi == EPI_F16_BIAS_GELU || epi == EPI_CROSS_KV) && (bm == 192 || bm == 128) && ks == 64;
+    if (!qkv288 && !wide192) return p;
+    p.epi = epi; p.kernel = 8; p.bm = bm; p.bn = 256; p.waves = 8; p.dma = 1; p.ks = ks;
+    p.ring = bm == 128 ? 3 : 2; p.ring_w = bm == 288 ? 2 : 3;
+    p.orient = epi == EPI_QKV_ENC ? GEMM_ORIENT_PER_TILE : GEMM_ORIENT_COLS;      // (k_gemm8: SWAPPED, the V^T third per tile; `big` plays no part here)
+    return p;
+}
+
 bool gemm8(int epi, int bm, bool swapped, const GemmArgs & a, hipStream_t st, int ks) {
     if ((a.N % 256) != 0 || (a.K % 64) != 0 || a.M < 1) return false;
 #ifdef WMI_G8_LAB
@@ -360,7 +373,7 @@ bool gemm8(int epi, int bm, bool swapped, const GemmArgs & a, hipStream_t st, in
 #undef WMI_G8
 #undef WMI_G8B
 #else
-    if (!swapped) return false;
+    if (!gemm8_plan(epi, bm, swapped, a, ks).kernel) return false;
     // q|k|v of the lock-step encoder: 288-row tiles on 32-deep slots (42 x 6 = 252 tiles at M = 12 000: one round), orientation per column tile
     if (epi == EPI_QKV_ENC && bm == 288 && ks == 32) { launch8<288, EPI_QKV_ENC, 2, 2, true, 32>(a, st); return true; }
     if (ks != 64) return false;

@@ -209,6 +209,47 @@ void gemm_log_install(GemmLog * log);       // null = off
 // false = not served (N % 256, K % 64, epilogue): the caller keeps gemm().
 bool gemm8(int epi, int bm, bool swapped, const GemmArgs & a, hipStream_t st, int ks = 64);
 
+// gemm()'s decision, apart from its launch: gemm() is launch(gemm_plan(...)).  Pure host arithmetic over (epilogue, M, N, K, S, the lab bits
+// in GemmArgs::no_glds, the CU count): no device, no launch — wmi_selftest_gemm_plan hands it to the CPU tests, wmi_selftest_gemm reports the
+// plan that served a call, and tests/gemm_f64.py holds the table of plans the product reaches.
+enum GemmOrient : int {
+    GEMM_ORIENT_ROWS = 0,       // first orientation, mfma(A rows, W rows): epilogue_rows
+    GEMM_ORIENT_COLS = 1,       // transposed, mfma(W rows, A rows): epilogue_cols / epilogue_cols_wide
+    GEMM_ORIENT_PER_TILE = 2,   // EPI_QKV_ENC: q and k column tiles transposed, the V^T third (n0 >= 2 S) in the first orientation
+};
+struct GemmPlan {
+    int epi = 0;
+    int kernel = 0;             // 0 = not served, 1 = k_gemm, 8 = k_gemm8
+    int bm = 0, bn = 0;         // tile
+    int waves = 0;              // wavefronts per workgroup
+    int ring = 0, ring_w = 0;   // LDS ring depth (k_gemm8: of the A image and of the W image)
+    int dma = 0;                // 1 = DMA ring (global_load_lds), 0 = register-staged loop
+    int orient = 0;             // GemmOrient: the rule the kernel applies
+    int ks = 0;                 // k extent of a slot (k_gemm8: 32 or 64; k_gemm: one 64-wide LDS tile)
+};
+GemmPlan gemm_plan(int epi, const GemmArgs & a, int n_cu);        // n_cu: cu_count_x8() of the device that will run it
+GemmPlan gemm8_plan(int epi, int bm, bool swapped, const GemmArgs & a, int ks);     // what gemm8() launches for these arguments (kernel = 0: not served)
+// The two run-time choices a k_gemm workgroup makes itself, written once for the kernel and for gemm_plan().  Macros, not functions: the
+// kernel's code stays what it was instruction for instruction (an inlined function evaluates its arguments — loads of kernel arguments —
+// ahead of the short-circuits, and hipcc then schedules the prologue differently).
+//   the K loop: 64-row tiles take the DMA ring while the grid is small, the register-staged loop with thousands of tiles or a half K tile
+#define WMI_GEMM_TAKES_DMA_RING(bm, nwg, K, no_glds) (((bm) >= 96 || (nwg) <= 1024) && ((K) % 64) == 0 && !((no_glds) & 1))
+//   the orientation of the accumulator fragments of a tile (vt_third: its first column is >= 2 S, the V^T third of the encoder's q|k|v), for
+//   the epilogues that have a transposed form at all (all but EPI_QKV_DEC); measurements: k_gemm.hip
+#define WMI_GEMM_BIG_GRID(M) ((M) >= 4096)
+#define WMI_GEMM_TILE_TRANSPOSED(epi, big, no_glds, vt_third) \
+    (!((epi) == EPI_QKV_ENC && ((vt_third) || ((big) && !((no_glds) & 8)))) && !((epi) == EPI_F32_BIAS_RESID && (big) && !((no_glds) & 32)))
+inline int gemm_orient_rule(int epi, int M, int no_glds) {
+#ifdef WMI_GEMM_NO_SWAP
+    return GEMM_ORIENT_ROWS;
+#else
+    if (epi == EPI_QKV_DEC) return GEMM_ORIENT_ROWS;
+    const bool big = WMI_GEMM_BIG_GRID(M);
+    const bool qk = WMI_GEMM_TILE_TRANSPOSED(epi, big, no_glds, false), v = WMI_GEMM_TILE_TRANSPOSED(epi, big, no_glds, epi == EPI_QKV_ENC);
+    return qk && v ? GEMM_ORIENT_COLS : qk ? GEMM_ORIENT_PER_TILE : GEMM_ORIENT_ROWS;
+#endif
+}
+
 // ---------------------------------------------------------------- LayerNorm (k_norm.hip)
 // y = (x - mean) / sqrt(var + eps) * g + b ; one wave per row. out16 and/or out32 may be null.
 void layernorm(const float * x, int rows, int S, const float * g, const float * b, float eps,

@@ -417,6 +417,27 @@ WHISPER_API int wmi_selftest_attn_encoder(int device, int B, int T, int Tpad, in
  * touched: S % 64, Tpad % 64, rows_per_chunk > Tpad or not dividing M, out_rows < M); -2 / -3 on a device error. */
 WHISPER_API int wmi_selftest_qkv_encoder(int device, int M, int S, int Tpad, int rows_per_chunk, const uint16_t * xn, const uint16_t * W,
                                          const float * bias, uint32_t sentinel, int out_rows, uint16_t * q, uint16_t * k, uint16_t * vt);
+/* gemm()'s decision without a launch (host only, no device): the plan for epilogue `epi` (kernels.h Epi: 0 F16_BIAS, 1 F16_BIAS_GELU,
+ * 2 F32_BIAS_RESID, 3 CONV2, 4 QKV_ENC, 5 QKV_DEC, 6 CROSS_KV, 7 Q_SCALED) at (M, N, K), split width S, on a device of n_cu compute units,
+ * with none of the WMI_GEMM_* lab switches.  out[10] = {kernel (1 k_gemm, 8 k_gemm8), BM, BN, wavefronts, ring depth (k_gemm8: of the A
+ * image), ring depth of the W image, 1 DMA ring / 0 register-staged loop, orientation rule (0 first, 1 transposed, 2 per tile: q and k
+ * transposed, V^T first), k extent of a slot, epi}.  Returns 0; -1 bad argument. */
+WHISPER_API int wmi_selftest_gemm_plan(int epi, int M, int N, int K, int S, int n_cu, int * out);
+/* One f16 GEMM with its epilogue on caller operands, through gemm() — or, with force8_bm in {128, 192, 288}, through gemm8() directly.  No
+ * context, no model.  A: f16 bit patterns, exactly (M - 1) lda + K elements (lda < K: the convolutions' implicit GEMM); W [N][K]; bias [N]
+ * f32 (NULL: none, for the epilogues that allow it); resid f32: [M][N] for F32_BIAS_RESID (in_place = 1: placed in C and passed as
+ * resid == C, as the product does), the positional rows [rows_per_chunk - 4 or M][N] for CONV2.  The arguments are filled as encode(),
+ * encode_rows() and the decoder's projections fill them, with leading dimensions ld = (S for the split epilogues, else N) + ld_pad:
+ *   C     [out_rows][ld] f16 or f32 (CROSS_KV: [n_layers][out_rows][ld], layer stride out_rows x ld)
+ *   aux   CONV2 [out_rows][ld] f32 (NULL: not written) | QKV_ENC, QKV_DEC k [out_rows][ld] | CROSS_KV v [n_layers][out_rows][ld]
+ *   aux2  QKV_ENC the raw V^T image [chunks][S][Tpad] | QKV_DEC v [out_rows][ld]
+ * every one filled with `sentinel` (its low 16 bits for f16) first and copied back whole; out_rows >= M + 16.  plan_out[11]: the plan that
+ * served the call, as wmi_selftest_gemm_plan reports it, and in [10] the device's CU count the dispatch used.  Returns 0; -1 for a bad argument or a shape whose launch could leave its
+ * buffers — decided before the device is touched; -2 / -3 on a device error. */
+WHISPER_API int wmi_selftest_gemm(int device, int epi, int M, int N, int K, int lda, int S, float scale, int n_layers, int rows_per_chunk,
+                                  int conv2_out_rows, int Tpad, int ld_pad, int in_place, int force8_bm, const uint16_t * A,
+                                  const uint16_t * W, const float * bias, const float * resid, uint32_t sentinel, int out_rows, void * C,
+                                  void * aux, void * aux2, int * plan_out);
 /* Its block-quantised twin: the block-dot GEMM's q|k|v split epilogue (what a quantised encoder pass launches below the f16 threshold, and a
  * stacked pass of short chunks at any row count).  x [M][S] f32 rows, quantised to q8 blocks as wmi_selftest_quant does; w_blocks = the ggml
  * blocks of the [3 S][S] matrix of type `qtype` as a model file holds them; the rest as wmi_selftest_qkv_encoder.  No context.  Returns 0;
