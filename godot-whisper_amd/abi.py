@@ -186,6 +186,15 @@ WHISPER_API = [
 ]
 
 
+class wmi_window(C.Structure):  # include/wmi_device.h: a 30 s window of a call made with a no-speech mode (wmi_set_no_speech)
+    _fields_ = [("seek", C.c_int32), ("no_speech_prob", C.c_float), ("outcome", C.c_int32), ("i_segment", C.c_int32),
+                ("n_segments", C.c_int32)]
+
+
+NO_SPEECH_OFF, NO_SPEECH_REPORT, NO_SPEECH_DROP, NO_SPEECH_GATE = range(4)       # wmi_set_no_speech modes
+WINDOW_EMITTED, WINDOW_DROPPED, WINDOW_GATED = range(3)                          # wmi_window.outcome
+
+
 class whisper_model_loader(C.Structure):  # W/whisper.h:108-114
     _fields_ = [("context", C.c_void_p),
                 ("read", C.CFUNCTYPE(C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t)),

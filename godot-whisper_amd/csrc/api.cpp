@@ -789,6 +789,7 @@ int wmi_batch_select(struct whisper_context * ctx, int chunk) {
     CtxScope lk(ctx);
     if (!ctx->state || !ctx->batch || chunk < 0 || chunk >= (int) ctx->batch->results.size()) return -1;
     ctx->state->result_all = ctx->batch->results[chunk];
+    if (chunk < (int) ctx->batch->windows.size()) ctx->state->windows = ctx->batch->windows[chunk]; else ctx->state->windows.clear();
     if (chunk < (int) ctx->batch->lang_id.size() && ctx->batch->lang_id[chunk] >= 0) ctx->state->lang_id = ctx->batch->lang_id[chunk];
     return (int) ctx->state->result_all.size();
 }
@@ -1030,6 +1031,53 @@ int wmi_selftest_quant(int device, int qtype, int mode, const void * w_blocks, c
     (void) hipFree(d_t); (void) hipFree(d_x); (void) hipFree(d_o); (void) hipFree(d_z); (void) hipFree(d_qs); (void) hipFree(d_ds); (void) hipFree(d_tok);
     (void) hipFree(d_a16); (void) hipFree(d_w16);
     return ok ? 0 : -3;
+}
+
+int wmi_selftest_no_speech(int device, int form, int rows, int n_vocab, int nosp, const float * logits, const uint16_t * W, const float * x,
+                           int K, float * logits_out, float * p_out) {
+    if ((form != 0 && form != 1) || rows < 1 || rows > k::NSP_MAX_ROWS || n_vocab < 1 || n_vocab > k::NSP_MAX_VOCAB || nosp < 0 || nosp >= n_vocab || !p_out) return -1;
+    if (form == 1 && !logits) return -1;
+    if (form == 0 && (!W || !x || !k::lang_head_usable(K))) return -1;
+    if (!HIP_OK(hipSetDevice(device))) return -2;
+    struct Bufs {
+        std::vector<void *> dev; void * host = nullptr; hipStream_t st = nullptr;
+        ~Bufs() { if (st) (void) hipStreamDestroy(st); for (void * q : dev) (void) hipFree(q); if (host) (void) hipHostFree(host); }
+        void * get(size_t bytes) { void * q = nullptr; if (!HIP_OK(hipMalloc(&q, bytes))) return nullptr; dev.push_back(q); return q; }
+    } b;
+    void * scratch = b.get(k::no_speech_scratch_bytes(n_vocab));
+    if (!scratch || !HIP_OK(hipHostMalloc(&b.host, k::NSP_MAX_ROWS * sizeof(k::NoSpeechOut), hipHostMallocDefault)) || !HIP_OK(hipStreamCreate(&b.st))) return -3;
+    memset(b.host, 0, k::NSP_MAX_ROWS * sizeof(k::NoSpeechOut));
+    k::NoSpeechOut * out = (k::NoSpeechOut *) b.host;
+    const int32_t tag = 0x5eed;
+    bool ok = true;
+    if (form == 1) {
+        float * d_l = (float *) b.get((size_t) rows * n_vocab * 4);
+        if (!d_l || !HIP_OK(hipMemcpyAsync(d_l, logits, (size_t) rows * n_vocab * 4, hipMemcpyHostToDevice, b.st))) return -3;
+        k::NoSpeechRows nr{}; nr.n = rows; for (int r = 0; r < rows; ++r) nr.row[r] = r;
+        ok = k::no_speech_logits(d_l, n_vocab, nr, n_vocab, nosp, scratch, out, tag, b.st);
+    } else {
+        __half * d_W = (__half *) b.get((size_t) n_vocab * K * 2);
+        float * d_x = (float *) b.get((size_t) rows * K * 4), * d_g = (float *) b.get((size_t) K * 4), * d_b = (float *) b.get((size_t) K * 4);
+        float * d_l = logits_out ? (float *) b.get((size_t) rows * n_vocab * 4) : nullptr;
+        if (!d_W || !d_x || !d_g || !d_b || (logits_out && !d_l)) return -3;
+        const std::vector<float> ones((size_t) K, 1.0f);
+        if (!HIP_OK(hipMemcpyAsync(d_W, W, (size_t) n_vocab * K * 2, hipMemcpyHostToDevice, b.st)) ||
+            !HIP_OK(hipMemcpyAsync(d_x, x, (size_t) rows * K * 4, hipMemcpyHostToDevice, b.st)) ||
+            !HIP_OK(hipMemcpyAsync(d_g, ones.data(), (size_t) K * 4, hipMemcpyHostToDevice, b.st)) ||
+            !HIP_OK(hipMemsetAsync(d_b, 0, (size_t) K * 4, b.st)) || !HIP_OK(hipStreamSynchronize(b.st))) return -3;
+        ok = k::no_speech_head(d_x, rows, K, d_g, d_b, 1e-5f, d_W, n_vocab, nosp, scratch, out, tag, b.st);
+        for (int r = 0; ok && d_l && r < rows; ++r) {             // the product's one-row vocabulary projection, a row at a time
+            k::GemvArgs g{};
+            g.x32 = d_x + (size_t) r * K; g.ln_g = d_g; g.ln_b = d_b; g.eps = 1e-5f; g.n = 1; g.K = K; g.N = n_vocab; g.W = d_W;
+            g.epi = k::EPI_LOGITS; g.C = d_l + (size_t) r * n_vocab; g.ldc = n_vocab; g.ldr = K; g.ldaux = K; g.ldaux2 = K; g.S = K;
+            k::gemv(g, b.st);
+        }
+        if (ok && d_l && !HIP_OK(hipMemcpyAsync(logits_out, d_l, (size_t) rows * n_vocab * 4, hipMemcpyDeviceToHost, b.st))) return -3;
+    }
+    if (!ok) return -3;
+    if (!HIP_OK(hipStreamSynchronize(b.st)) || !HIP_OK(hipGetLastError())) return -3;
+    for (int r = 0; r < rows; ++r) { if (out[r].tag != tag) return -3; p_out[r] = out[r].p; }
+    return 0;
 }
 
 int wmi_selftest_attn_encoder(int device, int B, int T, int Tpad, int S, int H, int qk_rows, int out_rows, const int32_t * row_T,

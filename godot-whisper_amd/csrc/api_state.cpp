@@ -210,6 +210,12 @@ int whisper_full_parallel(struct whisper_context * ctx, struct whisper_full_para
     State & main = *ctx->state;
     for (int i = 0; i < n_processors - 1; ++i) {
         State & si = *S(states[i]);
+        // (no-speech modes: the piece's windows follow the main state's, seek and first segment shifted to the whole signal)
+        for (WindowRec wr : si.windows) {
+            wr.seek += (int32_t) (100 * (int64_t) ((i + 1) * per) / WHISPER_SAMPLE_RATE + offset_t);
+            wr.seg0 += (int32_t) main.result_all.size();
+            main.windows.push_back(wr);
+        }
         for (auto & seg : si.result_all) {
             const int64_t shift = 100 * (int64_t) ((i + 1) * per) / WHISPER_SAMPLE_RATE + offset_t;
             seg.t0 += shift; seg.t1 += shift;
@@ -254,6 +260,37 @@ const char * whisper_full_get_token_text_from_state(struct whisper_context * ctx
 whisper_token whisper_full_get_token_id_from_state(struct whisper_state * state, int i, int j) { return S(state)->result_all[i].tokens[j].id; }
 whisper_token_data whisper_full_get_token_data_from_state(struct whisper_state * state, int i, int j) { return S(state)->result_all[i].tokens[j]; }
 float whisper_full_get_token_p_from_state(struct whisper_state * state, int i, int j) { return S(state)->result_all[i].tokens[j].p; }
+
+// the windows of a call made with a no-speech mode (wmi_device.h)
+int wmi_full_n_windows_from_state(struct whisper_state * state) { return state ? (int) S(state)->windows.size() : 0; }
+int wmi_full_get_window_from_state(struct whisper_state * state, int i, struct wmi_window * out) {
+    if (!state || !out || i < 0 || i >= (int) S(state)->windows.size()) return -1;
+    const WindowRec & w = S(state)->windows[i];
+    out->seek = w.seek; out->no_speech_prob = w.p; out->outcome = w.outcome; out->i_segment = w.seg0; out->n_segments = w.n_seg;
+    return 0;
+}
+float wmi_full_get_segment_no_speech_prob_from_state(struct whisper_state * state, int i_segment) {
+    if (!state || i_segment < 0) return -1.0f;
+    for (const WindowRec & w : S(state)->windows) if (i_segment >= w.seg0 && i_segment < w.seg0 + w.n_seg) return w.p;
+    return -1.0f;
+}
+int wmi_full_n_windows(struct whisper_context * ctx) { return ctx && ctx->state ? wmi_full_n_windows_from_state(reinterpret_cast<struct whisper_state *>(ctx->state.get())) : 0; }
+int wmi_full_get_window(struct whisper_context * ctx, int i, struct wmi_window * out) {
+    return ctx && ctx->state ? wmi_full_get_window_from_state(reinterpret_cast<struct whisper_state *>(ctx->state.get()), i, out) : -1;
+}
+float wmi_full_get_segment_no_speech_prob(struct whisper_context * ctx, int i_segment) {
+    return ctx && ctx->state ? wmi_full_get_segment_no_speech_prob_from_state(reinterpret_cast<struct whisper_state *>(ctx->state.get()), i_segment) : -1.0f;
+}
+int wmi_set_no_speech(struct whisper_context * ctx, int mode) {
+    if (!ctx) return -2;
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    const int prev = ctx->no_speech_mode;
+    ctx->no_speech_mode = mode < 0 ? 0 : (mode > 3 ? 3 : mode);
+    return prev;
+}
+int wmi_selftest_no_speech_rule(int mode, float p, float thold, int failed, double avg_logprob, float logprob_thold) {
+    return no_speech_rule(mode, p, thold, failed != 0, avg_logprob, logprob_thold);
+}
 
 const char * whisper_lang_str_full(int id) { return lang_str_full(id); }
 

@@ -578,7 +578,30 @@ struct Row {
     int n_fed = 0;                           // prompt tokens already through the decoder
     int i = 0;                               // sampled tokens accepted in this window
     bool done = false;                       // window finished (completed, failed or length limit)
+    float p = -1.0f; bool gated = false;     // no-speech modes: the window's probability from its <sot> step, and whether that step ended it
 };
+
+// The no-speech head behind a lock-step step (form 1: the step has written every row's raw logits to b.logits): one launch over the `n`
+// rows `which` that have just fed <sot>, one wait; p[i] = row which[i]'s probability.
+bool rows_no_speech(whisper_context & ctx, const int * which, int n, float * p) {
+    BatchWork & b = *ctx.batch; const Vocab & v = ctx.model.vocab;
+    hipStream_t s = ctx.state->dev.stream;
+    if (n < 1 || n > k::NSP_MAX_ROWS || v.n_vocab > k::NSP_MAX_VOCAB) return false;
+    if (!b.nsp_scratch) HIP_TRY(hipMalloc(&b.nsp_scratch, k::no_speech_scratch_bytes(v.n_vocab)));
+    if (!b.nsp_host) {
+        HIP_TRY(hipHostMalloc(&b.nsp_host, k::NSP_MAX_ROWS * sizeof(k::NoSpeechOut), hipHostMallocDefault));
+        memset(b.nsp_host, 0, k::NSP_MAX_ROWS * sizeof(k::NoSpeechOut));
+    }
+    k::NoSpeechRows rows{}; rows.n = n;
+    for (int i = 0; i < n; ++i) rows.row[i] = which[i];
+    b.nsp_seq = b.nsp_seq >= 0x7fffffff ? 1 : b.nsp_seq + 1;
+    const k::NoSpeechOut * out = (const k::NoSpeechOut *) b.nsp_host;
+    if (!k::no_speech_logits(b.logits, v.n_vocab, rows, v.n_vocab, v.nosp, b.nsp_scratch, (k::NoSpeechOut *) b.nsp_host, b.nsp_seq, s)) return false;
+    HIP_TRY(hipStreamSynchronize(s));
+    if (!HIP_OK(hipGetLastError())) return false;
+    for (int i = 0; i < n; ++i) { if (out[i].tag != b.nsp_seq) return false; p[i] = out[i].p; }
+    return true;
+}
 
 } // namespace
 
@@ -677,6 +700,8 @@ void free_batch(whisper_context & ctx) {
     if (w.step_host) (void) hipHostFree(w.step_host);
     if (w.sample_host) (void) hipHostFree(w.sample_host);
     if (w.lang_host) (void) hipHostFree(w.lang_host);
+    if (w.nsp_scratch) (void) hipFree(w.nsp_scratch);
+    if (w.nsp_host) (void) hipHostFree(w.nsp_host);
     for (size_t i = 1; i < w.lanes.size(); ++i) free_lane_state(w.lanes[i]);
     for (whisper_context * r : w.replicas) free_replica(r);
     delete ctx.batch;
@@ -738,6 +763,9 @@ int full_batch(whisper_context & ctx, whisper_full_params params, const float * 
     auto eff_T = [&](int c) { return actx(c) > 0 ? actx(c) : hp.n_audio_ctx; };
     ctx.batch->results.assign(n_chunks, {});
     ctx.batch->redo.assign(n_chunks, 0);
+    // the no-speech mode of this call (wmi_set_no_speech), handed on to whatever context transcribes a chunk of it; windows per chunk
+    const int nsm = ctx.no_speech_mode;
+    ctx.batch->windows.assign(n_chunks, {});
     ctx.batch->lang_id.assign(n_chunks, -1); ctx.batch->lang_detected.assign(n_chunks, 0); ctx.batch->lang_probs.assign((size_t) n_chunks * k::LANG_HEAD_N, 0.0f);
     // what whisper_full_lang_id reports after whisper_full on a chunk, and the probabilities if that call detected the language
     auto keep_lang = [&](int c, const State & st) {
@@ -753,8 +781,8 @@ int full_batch(whisper_context & ctx, whisper_full_params params, const float * 
         // depend on which chunks were transcribed before it
         for (auto & dec : primary->decoders) dec.rng = std::mt19937(0);
         const int rc = full(ctx, params_of(c), on_device ? nullptr : pcm[c], on_device ? pcm[c] : nullptr, n_samples[c]);
-        if (rc == 0) { ctx.batch->results[c] = std::move(primary->result_all); keep_lang(c, *primary); }
-        primary->result_all.clear();
+        if (rc == 0) { ctx.batch->results[c] = std::move(primary->result_all); ctx.batch->windows[c] = std::move(primary->windows); keep_lang(c, *primary); }
+        primary->result_all.clear(); primary->windows.clear();
         return rc;
     };
 
@@ -797,9 +825,10 @@ int full_batch(whisper_context & ctx, whisper_full_params params, const float * 
                     if (w == 0) rc = run_alone(c);
                     else {
                         for (auto & dec : wc.state->decoders) dec.rng = std::mt19937(0);
+                        wc.no_speech_mode = nsm;
                         rc = full(wc, params_of(c), on_device ? nullptr : pcm[c], on_device ? pcm[c] : nullptr, n_samples[c]);
-                        if (rc == 0) { ctx.batch->results[c] = std::move(wc.state->result_all); keep_lang(c, *wc.state); }
-                        wc.state->result_all.clear();
+                        if (rc == 0) { ctx.batch->results[c] = std::move(wc.state->result_all); ctx.batch->windows[c] = std::move(wc.state->windows); keep_lang(c, *wc.state); }
+                        wc.state->result_all.clear(); wc.state->windows.clear();
                     }
                     if (rc != 0) { rets[w] = rc; return; }
                     ctx.batch->redo[c] = 1;
@@ -837,7 +866,7 @@ int full_batch(whisper_context & ctx, whisper_full_params params, const float * 
         std::vector<const float *> o_pcm(n_chunks); std::vector<int> o_n(n_chunks), o_ctx(n_chunks);
         for (int i = 0; i < n_chunks; ++i) { o_pcm[i] = pcm[order[i]]; o_n[i] = n_samples[order[i]]; o_ctx[i] = audio_ctx[order[i]]; }
         BatchWork & bw = *ctx.batch;
-        std::vector<std::vector<Segment>> all(n_chunks);
+        std::vector<std::vector<Segment>> all(n_chunks); std::vector<std::vector<WindowRec>> all_win(n_chunks);
         std::vector<int> all_redo(n_chunks, 0), all_lang(n_chunks, -1); std::vector<char> all_det(n_chunks, 0);
         std::vector<float> all_probs((size_t) n_chunks * k::LANG_HEAD_N, 0.0f);
         int64_t tm[4] = {0, 0, 0, 0}; int steps = 0, chained = 0, groups = 1;
@@ -853,7 +882,7 @@ int full_batch(whisper_context & ctx, whisper_full_params params, const float * 
             if (rc != 0) return rc;
             for (int i = i0; i < i1; ++i) {
                 const int c = order[i];
-                all[c] = std::move(bw.results[i - i0]); all_redo[c] = bw.redo[i - i0];
+                all[c] = std::move(bw.results[i - i0]); all_win[c] = std::move(bw.windows[i - i0]); all_redo[c] = bw.redo[i - i0];
                 all_lang[c] = bw.lang_id[i - i0]; all_det[c] = bw.lang_detected[i - i0];
                 std::copy_n(bw.lang_probs.begin() + (size_t) (i - i0) * k::LANG_HEAD_N, k::LANG_HEAD_N, all_probs.begin() + (size_t) c * k::LANG_HEAD_N);
             }
@@ -861,7 +890,7 @@ int full_batch(whisper_context & ctx, whisper_full_params params, const float * 
             groups = std::max(groups, bw.groups_last);
             i0 = i1;
         }
-        bw.results = std::move(all); bw.redo = std::move(all_redo);
+        bw.results = std::move(all); bw.windows = std::move(all_win); bw.redo = std::move(all_redo);
         bw.lang_id = std::move(all_lang); bw.lang_detected = std::move(all_det); bw.lang_probs = std::move(all_probs);
         bw.t_mel_us = tm[0]; bw.t_encode_us = tm[1]; bw.t_decode_us = tm[2]; bw.t_emit_us = tm[3]; bw.n_steps = steps; bw.n_chained = chained;
         bw.groups_last = groups;
@@ -883,7 +912,7 @@ int full_batch(whisper_context & ctx, whisper_full_params params, const float * 
         G = std::max(1, std::min(G, n_chunks / 2));
         if (G > 1) G = ensure_replicas(ctx, G - 1) + 1;                    // (out of memory: fewer groups)
         if (G > 1) {
-            std::vector<std::vector<Segment>> all(n_chunks);
+            std::vector<std::vector<Segment>> all(n_chunks); std::vector<std::vector<WindowRec>> all_win(n_chunks);
             std::vector<int> all_redo(n_chunks, 0), rets(G, 0), c0(G + 1, 0), all_lang(n_chunks, -1);
             std::vector<char> all_det(n_chunks, 0); std::vector<float> all_probs((size_t) n_chunks * k::LANG_HEAD_N, 0.0f);
             for (int g = 0; g < G; ++g) c0[g + 1] = c0[g] + n_chunks / G + (g < n_chunks % G ? 1 : 0);
@@ -894,6 +923,7 @@ int full_batch(whisper_context & ctx, whisper_full_params params, const float * 
                     whisper_context & wc = g == 0 ? ctx : *ctx.batch->replicas[g - 1];
                     (void) hipSetDevice(ctx.device);
                     if (g > 0 && wc.batch) wc.batch->groups_wanted = 1;
+                    wc.no_speech_mode = nsm;
                     t_in_group = true;
                     struct Off { ~Off() { t_in_group = false; } } off;
                     const int cnt = c0[g + 1] - c0[g];
@@ -903,7 +933,7 @@ int full_batch(whisper_context & ctx, whisper_full_params params, const float * 
                     if (rc != 0 || !wc.batch) return;
                     std::lock_guard<std::mutex> lk(merge_mu);
                     for (int i = 0; i < cnt; ++i) {
-                        all[c0[g] + i] = std::move(wc.batch->results[i]); all_redo[c0[g] + i] = wc.batch->redo[i];
+                        all[c0[g] + i] = std::move(wc.batch->results[i]); all_win[c0[g] + i] = std::move(wc.batch->windows[i]); all_redo[c0[g] + i] = wc.batch->redo[i];
                         all_lang[c0[g] + i] = wc.batch->lang_id[i]; all_det[c0[g] + i] = wc.batch->lang_detected[i];
                         std::copy_n(wc.batch->lang_probs.begin() + (size_t) i * k::LANG_HEAD_N, k::LANG_HEAD_N, all_probs.begin() + (size_t) (c0[g] + i) * k::LANG_HEAD_N);
                     }
@@ -923,7 +953,7 @@ int full_batch(whisper_context & ctx, whisper_full_params params, const float * 
             }
             for (int g = 0; g < G; ++g) if (rets[g] != 0) return rets[g];
             BatchWork & bw = *ctx.batch;
-            bw.results = std::move(all); bw.redo = std::move(all_redo);
+            bw.results = std::move(all); bw.windows = std::move(all_win); bw.redo = std::move(all_redo);
             bw.lang_id = std::move(all_lang); bw.lang_detected = std::move(all_det); bw.lang_probs = std::move(all_probs);
             bw.t_mel_us = tm[0]; bw.t_encode_us = tm[1]; bw.t_decode_us = tm[2]; bw.t_emit_us = tm[3]; bw.n_steps = steps; bw.n_chained = chained;
             bw.groups_last = G;
@@ -994,6 +1024,7 @@ int full_batch(whisper_context & ctx, whisper_full_params params, const float * 
             State & ls = *b.lanes[r];
             StateSwap sw(ctx, &ls);
             ls.result_all.clear();
+            ls.windows.clear();
             ls.ts_failed = false;
             ls.prompt_past = prompt_user;                     // every chunk is an independent transcription (no_context semantics)
             ls.exp_n_audio_ctx = actx(row.chunk);
@@ -1115,6 +1146,7 @@ int full_batch(whisper_context & ctx, whisper_full_params params, const float * 
                 }
                 row.prompt.insert(row.prompt.end(), row.prompt_init.begin(), row.prompt_init.end());
                 row.n_fed = 0; row.i = 0; row.done = false;
+                row.p = -1.0f; row.gated = false;
             }
 
             // ---- decode steps: every row feeds one token (prompt tokens first, one per step, then its own samples)
@@ -1149,6 +1181,21 @@ int full_batch(whisper_context & ctx, whisper_full_params params, const float * 
                 if (!any) break;
                 ++b.step_seq;
                 if (!decode_rows_step(ctx, nb)) { WMI_ERR("%s: failed to decode\n", __func__); return -8; }
+                if (nsm != 0) {
+                    // the rows that have just fed <sot>: their raw logits are in b.logits, the head runs behind the step.  Gate: such a row is
+                    // done at this step — its pick is not taken — while the other rows go on
+                    int which[k::NSP_MAX_ROWS], n_which = 0; float pw[k::NSP_MAX_ROWS];
+                    for (int r = 0; r < nb; ++r) {
+                        const Row & row = rows[act[r]];
+                        if (!row.done && row.n_fed == (int) (row.prompt.size() - row.prompt_init.size())) which[n_which++] = r;
+                    }
+                    if (n_which > 0 && !rows_no_speech(ctx, which, n_which, pw)) { WMI_ERR("%s: failed to decode\n", __func__); return -8; }
+                    for (int i = 0; i < n_which; ++i) {
+                        Row & row = rows[act[which[i]]];
+                        row.p = pw[i];
+                        if (no_speech_rule(nsm, row.p, params.no_speech_thold, false, 0.0, params.logprob_thold) == NSP_GATE) { row.gated = true; row.done = true; }
+                    }
+                }
                 const k::SampleOut * so = (const k::SampleOut *) b.sample_host;
                 for (int r = 0; r < nb; ++r) {
                     Row & row = rows[act[r]];
@@ -1191,19 +1238,33 @@ int full_batch(whisper_context & ctx, whisper_full_params params, const float * 
             for (int r = 0; r < nb; ++r) {
                 Row & row = rows[act[r]]; State & ls = *b.lanes[row.lane];
                 Decoder & d = ls.decoders[0];
+                if (row.gated) {                               // no segments, the whole window's advance, prompt_past as it was
+                    ls.windows.push_back(WindowRec{ row.seek, row.p, WINDOW_GATED, (int32_t) ls.result_all.size(), 0 });
+                    row.seek += 100 * WHISPER_CHUNK_SIZE;
+                    continue;
+                }
                 if (!d.failed) {
                     d.sequence.tokens.resize(d.sequence.result_len);
                     sequence_score(params, d.sequence);
                     if (d.sequence.result_len > 32 && d.sequence.entropy < params.entropy_thold) { d.failed = true; primary->n_fail_h++; }
                 }
-                if (has_fallback && (d.failed || d.sequence.avg_logprobs < params.logprob_thold)) { row.redo = true; primary->n_fail_p++; continue; }
+                // (mode 0: the rule says "fall back" exactly where the reference does)
+                const int rule = no_speech_rule(nsm, row.p, params.no_speech_thold, d.failed, d.sequence.avg_logprobs, params.logprob_thold);
+                if (rule == NSP_DROP) {
+                    ls.windows.push_back(WindowRec{ row.seek, row.p, WINDOW_DROPPED, (int32_t) ls.result_all.size(), 0 });
+                    row.seek += 100 * WHISPER_CHUNK_SIZE;
+                    continue;
+                }
+                if (has_fallback && rule == NSP_FALLBACK) { row.redo = true; primary->n_fail_p++; continue; }
                 emit.push_back(act[r]);
             }
             {
                 const int64_t te0 = time_us();
                 auto emit_row = [&](int ri) {
                     Row & row = rows[ri]; State & ls = *b.lanes[row.lane];
+                    const int32_t seg0 = (int32_t) ls.result_all.size();
                     emit_window(ctx, ls, params, row.seek, row.prompt, row.prompt_init.size(), ls.decoders[0]);
+                    if (nsm != 0) ls.windows.push_back(WindowRec{ row.seek, row.p, WINDOW_EMITTED, seg0, (int32_t) ls.result_all.size() - seg0 });
                     row.seek += ls.decoders[0].seek_delta;
                 };
                 // token times refined on the device (envelopes in HBM): the chunks' pending segments go in ONE launch behind the per-chunk work
@@ -1231,7 +1292,8 @@ int full_batch(whisper_context & ctx, whisper_full_params params, const float * 
                 if (rc != 0) return rc;
             } else {
                 b.results[row.chunk] = std::move(b.lanes[row.lane]->result_all);
-                b.lanes[row.lane]->result_all.clear();
+                b.windows[row.chunk] = std::move(b.lanes[row.lane]->windows);
+                b.lanes[row.lane]->result_all.clear(); b.lanes[row.lane]->windows.clear();
             }
         }
     }

@@ -217,6 +217,9 @@ void destroy_state(State * st) {
     if (d.draw_host) (void) hipHostFree(d.draw_host);
     if (d.step_host) (void) hipHostFree(d.step_host);
     if (d.sample_host) (void) hipHostFree(d.sample_host);
+    if (d.nsp_scratch) (void) hipFree(d.nsp_scratch);
+    dfree(d.nsp_logits);
+    if (d.nsp_host) (void) hipHostFree(d.nsp_host);
     if (d.pinned) (void) hipHostFree(d.pinned);
     if (d.stream && d.stream_own_queue) own_queue_stream_put(st->device, d.stream);
     else if (d.stream) (void) hipStreamDestroy(d.stream);
@@ -554,6 +557,17 @@ bool decode(whisper_context & ctx, const Batch & batch, float * lang_logits) {
     std::vector<int> rows;
     for (int i = 0; i < n; ++i) { p_tok[i] = batch.token[i]; p_pos[i] = batch.pos[i]; if (batch.logits[i]) rows.push_back(i); }
     for (size_t i = 0; i < rows.size(); ++i) p_rows[i] = rows[i];
+    // the no-speech head on batch row nsp_row (full(): the prompt's <sot> row), a request for this call only.  The row's raw logits are in
+    // d.logits when it is among the rows that asked for them (nsp_slot); otherwise its index rides behind theirs in the staging block
+    const int nsp_row = d.nsp_row < n ? d.nsp_row : -1;
+    d.nsp_row = -1;
+    int nsp_slot = -1;
+    if (nsp_row >= 0) {
+        if (lang_logits || !no_speech_ensure(ctx, d)) return false;
+        if (rows.size() <= 8) for (size_t i = 0; i < rows.size(); ++i) if (rows[i] == nsp_row) nsp_slot = (int) i;
+        if (nsp_slot < 0 && (int) rows.size() >= n) return false;      // (every row asked for logits, more than 8 of them: no caller does)
+        if (nsp_slot < 0) p_rows[rows.size()] = nsp_row;
+    }
     for (int j = 0; j < n; ++j) {
         const int32_t pos = batch.pos[j], seq = batch.seq_id[j];
         for (int i = 0; i < n_kv; ++i)
@@ -568,7 +582,9 @@ bool decode(whisper_context & ctx, const Batch & batch, float * lang_logits) {
     static_assert(LANG_PINNED_TAIL >= k::LANG_HEAD_N * sizeof(float), "the language head's logits fit the tail");
     float * const lang_pinned = lang_logits ? (float *) ((char *) d.pinned + d.pinned_bytes - LANG_PINNED_TAIL) : nullptr;
     if (ctx.model.quantised) {
-        if (!decode_layers_q(ctx, n, n_kv, kv_head, Tc, rows, lang_pinned)) return false;
+        const bool nsp_own = nsp_row >= 0 && nsp_slot < 0;
+        if (!decode_layers_q(ctx, n, n_kv, kv_head, Tc, rows, lang_pinned, nsp_own ? d.d_rows + rows.size() : nullptr, nsp_own ? d.nsp_logits : nullptr)) return false;
+        if (nsp_row >= 0 && !(nsp_own ? no_speech_from_logits(ctx, d.nsp_logits, 0) : no_speech_from_logits(ctx, d.logits, nsp_slot))) return false;
         HIP_TRY(hipStreamSynchronize(s));
         if (!HIP_OK(hipGetLastError())) return false;
         if (lang_logits) memcpy(lang_logits, lang_pinned, k::LANG_HEAD_N * sizeof(float));
@@ -636,6 +652,8 @@ bool decode(whisper_context & ctx, const Batch & batch, float * lang_logits) {
         for (int r = 0; r < nr; ++r)
             memcpy(st.logits.data() + (size_t) rows[r0 + r] * NV, (const float *) d.pinned + (size_t) r * NV, (size_t) NV * 4);
     }
+    // the no-speech head: from the row's logits where the projection above wrote them, else from its final residual in d.dx (form 0)
+    if (nsp_row >= 0 && !(nsp_slot >= 0 ? no_speech_from_logits(ctx, d.logits, nsp_slot) : no_speech_from_row(ctx, d.dx + (size_t) nsp_row * S))) return false;
     HIP_TRY(hipStreamSynchronize(s));
     if (!HIP_OK(hipGetLastError())) return false;
     if (lang_logits) memcpy(lang_logits, lang_pinned, k::LANG_HEAD_N * sizeof(float));
@@ -645,6 +663,60 @@ bool decode(whisper_context & ctx, const Batch & batch, float * lang_logits) {
     if (n == 1)      { st.t_decode_us += dt; st.n_decode++; }
     else if (n < 16) { st.t_batchd_us += dt; st.n_batchd += n; }
     else             { st.t_prompt_us += dt; st.n_prompt += n; }
+    return true;
+}
+
+// ------------------------------------------------------------------------------------------------ no-speech head
+bool no_speech_ensure(whisper_context & ctx, DeviceState & d) {
+    if (d.nsp_host) return true;
+    const int NV = ctx.model.hp.n_vocab;
+    if (NV > k::NSP_MAX_VOCAB) { WMI_ERR("%s: a vocabulary of %d entries is not covered (max %d)\n", __func__, NV, k::NSP_MAX_VOCAB); return false; }
+    if (!d.nsp_scratch) HIP_TRY(hipMalloc(&d.nsp_scratch, k::no_speech_scratch_bytes(NV)));
+    if (ctx.model.quantised && !d.nsp_logits && !dalloc(d.nsp_logits, (size_t) NV)) return false;
+    void * h = nullptr;
+    HIP_TRY(hipHostMalloc(&h, k::NSP_MAX_ROWS * sizeof(k::NoSpeechOut), hipHostMallocDefault));
+    memset(h, 0, k::NSP_MAX_ROWS * sizeof(k::NoSpeechOut));
+    d.nsp_host = h;
+    return true;
+}
+
+static int32_t no_speech_next_tag(int32_t & seq) { seq = seq >= 0x7fffffff ? 1 : seq + 1; return seq; }      // (never 0: the records start zeroed)
+
+bool no_speech_from_logits(whisper_context & ctx, const float * logits, int row) {
+    DeviceState & d = ctx.state->dev; const Vocab & v = ctx.model.vocab;
+    if (!no_speech_ensure(ctx, d)) return false;
+    k::NoSpeechRows rows{}; rows.n = 1; rows.row[0] = row;
+    if (!k::no_speech_logits(logits, v.n_vocab, rows, v.n_vocab, v.nosp, d.nsp_scratch, (k::NoSpeechOut *) d.nsp_host, no_speech_next_tag(d.nsp_seq), d.stream)) {
+        WMI_ERR("%s: the no-speech head does not cover this vocabulary (n_vocab = %d, nosp = %d)\n", __func__, v.n_vocab, v.nosp);
+        return false;
+    }
+    return true;
+}
+
+bool no_speech_from_row(whisper_context & ctx, const float * x) {
+    DeviceState & d = ctx.state->dev; const Vocab & v = ctx.model.vocab; const HParams & hp = ctx.model.hp; const Weights & w = ctx.w;
+    if (ctx.model.quantised || !w.d_te || !no_speech_ensure(ctx, d)) return false;
+    if (!k::no_speech_head(x, 1, hp.n_text_state, w.d_ln_g, w.d_ln_b, hp.eps, w.d_te, v.n_vocab, v.nosp, d.nsp_scratch, (k::NoSpeechOut *) d.nsp_host,
+                           no_speech_next_tag(d.nsp_seq), d.stream)) {
+        WMI_ERR("%s: the no-speech head does not cover this model (n_text_state = %d, n_vocab = %d)\n", __func__, hp.n_text_state, v.n_vocab);
+        return false;
+    }
+    return true;
+}
+
+bool no_speech_read(State & st, float * p) {
+    DeviceState & d = st.dev;
+    if (!d.nsp_host || d.nsp_seq == 0) return false;
+    const volatile k::NoSpeechOut * r = (const volatile k::NoSpeechOut *) d.nsp_host;
+    // (the record is one 8-byte store: read it as one)
+    auto rec = [&]() { const uint64_t b = *(const volatile uint64_t *) r; k::NoSpeechOut o; memcpy(&o, &b, sizeof(o)); return o; };
+    k::NoSpeechOut o = rec();
+    if (o.tag != d.nsp_seq) {
+        if (!HIP_OK(hipStreamSynchronize(d.stream))) return false;
+        o = rec();
+        if (o.tag != d.nsp_seq) { WMI_ERR("%s: the no-speech head's record did not arrive\n", __func__); return false; }
+    }
+    *p = o.p;
     return true;
 }
 

@@ -140,7 +140,8 @@ bool encode_layers_q_on(whisper_context & ctx, const EncBufsQ & e, hipStream_t s
     return true;
 }
 
-bool decode_layers_q(whisper_context & ctx, int n, int n_kv, int kv_head, int Tc, const std::vector<int> & rows, float * lang_out) {
+bool decode_layers_q(whisper_context & ctx, int n, int n_kv, int kv_head, int Tc, const std::vector<int> & rows, float * lang_out,
+                     const int32_t * nsp_row_dev, float * nsp_logits) {
     State & st = *ctx.state; DeviceState & d = st.dev; const Weights & w = ctx.w; const HParams & hp = ctx.model.hp;
     KVCache & kv = st.kv_self;
     const int S = hp.n_text_state, H = hp.n_text_head, Lt = hp.n_text_layer, NV = hp.n_vocab, n_ctx = (int) kv.size;
@@ -242,6 +243,12 @@ bool decode_layers_q(whisper_context & ctx, int n, int n_kv, int kv_head, int Tc
         HIP_TRY(hipStreamSynchronize(s));
         for (int r = 0; r < nr; ++r)
             memcpy(st.logits.data() + (size_t) rows[r0 + r] * NV, (const float *) d.pinned + (size_t) r * NV, (size_t) NV * 4);
+    }
+    if (nsp_row_dev) {                                      // the no-speech head's row (an interior prompt row: nobody else wants its logits)
+        k::GemvArgs g{};
+        g.x32 = d.dx; g.ln_g = w.d_ln_g; g.ln_b = w.d_ln_b; g.eps = hp.eps; g.n = 1; g.K = S; g.N = NV;
+        g.epi = k::EPI_LOGITS; g.C = nsp_logits; g.ldc = NV; g.rows = nsp_row_dev; g.pend = pend;
+        k::qrows(g, nullptr, w.q_te, s);
     }
     return true;
 }

@@ -64,6 +64,9 @@ int full(whisper_context & ctx, whisper_full_params params, const float * sample
     st.result_all.clear();
     st.ts_failed = false;
     st.lang_probs.clear();
+    // the no-speech mode of this call (wmi_set_no_speech; 0: nothing below launches or stores anything)
+    const int nsm = ctx.no_speech_mode;
+    st.windows.clear();
     // the envelope kernel reads the caller's samples on a side stream: never return while it is in flight
     struct EnvelopeGuard { State & st; ~EnvelopeGuard() { (void) signal_energy_wait(st); } } envelope_guard{st};
     static const bool defer_phases = getenv("WMI_PHASE_SYNC") == nullptr;
@@ -183,6 +186,10 @@ int full(whisper_context & ctx, whisper_full_params params, const float * sample
         if (seek > seek_start && seek + 500 >= seek_end) prompt_past.clear();
 
         int best_decoder_id = 0;
+        // the window's no-speech probability: taken once, at the first temperature's <sot> row (p_asked: the head is on the stream, its
+        // record is read where the rule first needs it)
+        float p_win = -1.0f; bool p_asked = false, p_known = false, gated = false, dropped = false;
+        auto p_read = [&]() { if (p_asked && !p_known) p_known = no_speech_read(st, &p_win); return !p_asked || p_known; };
         for (int it = 0; it < (int) temperatures.size(); ++it) {
             const float t_cur = temperatures[it];
             int n_cur = 1;
@@ -227,24 +234,49 @@ int full(whisper_context & ctx, whisper_full_params params, const float * sample
             struct KeepOff { bool & f; ~KeepOff() { f = false; } } keep_off{st.dev.keep_logits_on_device};
             whisper_token_data fast_next{};      // token picked on the device for the upcoming sampling step
             auto step_filter = [&](const Decoder & d) { return make_step_filter(v, hp, params, d); };
+            // the prompt row that carries <sot>, and whether this attempt takes the window's no-speech probability there: an interior row
+            // goes with the decode() of the rows in front of the last one (device.cpp), the last row's raw logits are in d.logits behind its step
+            const int sot_idx = (int) (prompt.size() - prompt_init.size());
+            const bool want_p = nsm != 0 && !p_asked && ctx.model.n_loaded > 0;
+            // gate: a window whose <sot> row says "no speech" ends where its probability is known, before its first sampling step
+            auto gate_here = [&]() {
+                return nsm == 3 && it == 0 && p_known &&
+                       no_speech_rule(nsm, p_win, params.no_speech_thold, false, 0.0, params.logprob_thold) == NSP_GATE;
+            };
             if (fast) {
                 bool ok = true;
                 if (prompt.size() > 1) {            // all but the last prompt token: plain batch decode, no logits wanted
                     st.batch.prep_legacy(prompt.data(), (int) prompt.size() - 1, 0, 0);
                     st.batch.logits[prompt.size() - 2] = 0;
+                    if (want_p && sot_idx < (int) prompt.size() - 1) { st.dev.nsp_row = sot_idx; p_asked = true; }
                     ok = decode(ctx, st.batch);
+                    st.dev.nsp_row = -1;
+                    if (ok && nsm == 3 && it == 0 && p_asked) {      // an interior <sot>: the window may end before its last prompt row's step
+                        ok = p_read();
+                        if (ok && gate_here()) { gated = true; break; }
+                    }
                 }
                 ok = ok && decode_greedy_step(ctx, prompt.back(), (int) prompt.size() - 1, step_filter(st.decoders[0]), fast_next);
+                if (ok && want_p && !p_asked) { ok = no_speech_from_logits(ctx, st.dev.logits, 0); p_asked = true; }
                 if (!ok || (params.abort_callback && params.abort_callback(params.abort_callback_user_data))) {
                     WMI_ERR("%s: failed to decode\n", __func__);
                     return -7;
                 }
             } else {
             st.batch.prep_legacy(prompt.data(), (int) prompt.size(), 0, 0);
-            if (!decode(ctx, st.batch) || (params.abort_callback && params.abort_callback(params.abort_callback_user_data))) {
+            if (want_p) { st.dev.nsp_row = sot_idx; p_asked = true; }
+            const bool ok_prompt = decode(ctx, st.batch);
+            st.dev.nsp_row = -1;
+            if (!ok_prompt || (params.abort_callback && params.abort_callback(params.abort_callback_user_data))) {
                 WMI_ERR("%s: failed to decode\n", __func__);
                 return -7;
             }
+            }
+            if (nsm == 3 && it == 0) {              // (<sot> as the last prompt row, and the general path: behind the prompt)
+                if (!p_read()) { WMI_ERR("%s: failed to decode\n", __func__); return -7; }
+                if (gate_here()) { gated = true; break; }
+            }
+            if (!fast) {                            // the general path again, behind the gate: the prompt's last row feeds every decoder
             {
                 const int64_t ts = time_us();
                 st.decoders[0].i_batch = (int) prompt.size() - 1;
@@ -428,18 +460,29 @@ int full(whisper_context & ctx, whisper_full_params params, const float * sample
                 }
             }
             bool success = true;
-            if (it != (int) temperatures.size() - 1) {
+            {
+                // (mode 0: no_speech_rule says "fall back" exactly where the reference does, W/whisper.cpp:5661-5668)
                 const Decoder & d = st.decoders[best_decoder_id];
-                if (d.failed || d.sequence.avg_logprobs < params.logprob_thold) { success = false; st.n_fail_p++; }
+                if (!p_read()) { WMI_ERR("%s: failed to decode\n", __func__); return -7; }
+                const int rule = no_speech_rule(p_known ? nsm : 0, p_win, params.no_speech_thold, d.failed, d.sequence.avg_logprobs, params.logprob_thold);
+                if (rule == NSP_DROP) { dropped = true; break; }
+                if (it != (int) temperatures.size() - 1 && rule == NSP_FALLBACK) { success = false; st.n_fail_p++; }
             }
             if (success) break;
         }
 
         // results of this window
+        if (gated || dropped) {                    // no segments, the whole window's advance, prompt_past as it was
+            st.windows.push_back(WindowRec{ seek, p_win, gated ? WINDOW_GATED : WINDOW_DROPPED, (int32_t) st.result_all.size(), 0 });
+            seek += 100 * WHISPER_CHUNK_SIZE;
+            continue;
+        }
         {
             const Decoder & best = st.decoders[best_decoder_id];
+            const int32_t seg0 = (int32_t) st.result_all.size();
             emit_window(ctx, st, params, seek, prompt, prompt_init.size(), best);
             if (st.ts_failed) { WMI_ERR("%s: failed to refine the token timestamps on the device\n", __func__); return -9; }
+            if (nsm != 0) st.windows.push_back(WindowRec{ seek, p_win, WINDOW_EMITTED, seg0, (int32_t) st.result_all.size() - seg0 });
             seek += best.seek_delta;
         }
     }

@@ -311,6 +311,15 @@ void sequence_score(const whisper_full_params & params, Sequence & seq) {       
     seq.entropy = entropy;
 }
 
+// ------------------------------------------------------------------ no-speech rule (OpenAI's transcribe.py)
+int no_speech_rule(int mode, float p, float thold, bool failed, double avg_logprob, float logprob_thold) {
+    const bool poor = failed || avg_logprob < logprob_thold;           // what sends a window to the next temperature (W/whisper.cpp:5661-5668)
+    const bool silent = mode >= 2 && mode <= 3 && p > thold;
+    if (silent && mode == 3) return NSP_GATE;
+    if (silent) return poor ? NSP_DROP : NSP_EMIT;                     // no fallback for a window that says "no speech"
+    return poor ? NSP_FALLBACK : NSP_EMIT;
+}
+
 // ------------------------------------------------------------------ language detection (W/whisper.cpp:3569-3650)
 int lang_auto_detect(whisper_context & ctx, int offset_ms, float * lang_probs) {
     State & st = *ctx.state;

@@ -393,6 +393,24 @@ void lang_head(const float * x, int rows, int S, const float * ln_g, const float
 // per-row results do not depend on the rows that share a launch): out[r][i] = src[r * ld + off + i], i < LANG_HEAD_N
 void lang_gather(const float * src, int ld, int off, int rows, float * out, hipStream_t st);
 
+// The no-speech head (k_nospeech.hip): p = soft-max(l)[nosp] of a decoder row's RAW logits l, OpenAI's no_speech_prob.  The arithmetic is
+// fixed: the vocabulary is cut into blocks of NSP_BLOCK entries; a block keeps m_b = max l and s_b = sum exp(double(l - m_b))
+// — the difference in f32, exp and the sums in double, lane L of one wavefront adding entries L and L + 64 and the 64 lanes in the xor
+// order 32 .. 1; an entry of -inf adds 0.  A second launch combines the blocks in ascending order: M = max m_b,
+// S = sum_b s_b exp(double(m_b - M)), p = float(exp(double(l[nosp] - M)) / S) — one rounding to f32 — and stores {p, tag} as ONE 8-byte
+// store, usually into pinned host memory.  Workgroups are independent: no atomics, no hand-off inside a launch; a row's result does not
+// depend on the rows that share the launch, and both forms give the same bits on the same logits.
+//   form 1 (no_speech_logits): logits already in HBM, row r of the launch reads logits + rows.row[r] * ld
+//   form 0 (no_speech_head):   the logits are k_lang_head's — gemv's one-row EPI_LOGITS bits — for ALL rows of the token embedding, from
+//                              the f32 residual row x + r * S; they live in LDS only.  S as lang_head_usable says.
+constexpr int NSP_BLOCK = 128, NSP_MAX_ROWS = 16, NSP_MAX_VOCAB = 65536;
+struct NoSpeechOut { float p; int32_t tag; };
+struct NoSpeechRows { int n; int row[NSP_MAX_ROWS]; };          // logits row of launch row r (form 1)
+size_t no_speech_scratch_bytes(int n_vocab);                    // the block partials of NSP_MAX_ROWS rows
+bool no_speech_logits(const float * logits, int ld, const NoSpeechRows & rows, int n_vocab, int nosp, void * scratch, NoSpeechOut * out, int32_t tag, hipStream_t st);
+bool no_speech_head(const float * x, int rows, int S, const float * ln_g, const float * ln_b, float eps, const __half * te, int n_vocab, int nosp,
+                    void * scratch, NoSpeechOut * out, int32_t tag, hipStream_t st);
+
 // One decoder MLP of the one-row step as ONE launch: x += W2 . gelu(W1 . LN(x) + b1) + b2 (k_mlp_pair, k_dec.hip).  The hidden row goes
 // from the workgroups that produce it to every workgroup of the same launch through data-tagged 8-byte granules ({two f16, tag}, written
 // and read past the caches): no launch boundary between the two projections.  `hand` holds 2 S granules (16 S bytes, zeroed once),

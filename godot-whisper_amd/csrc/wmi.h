@@ -178,6 +178,9 @@ struct Decoder {
 struct Segment { int64_t t0, t1; std::string text; std::vector<whisper_token_data> tokens; bool speaker_turn_next; };
 
 struct Mel { int n_len = 0, n_len_org = 0, n_mel = 0; };
+// one 30 s window of a transcription call made with a no-speech mode (wmi_set_no_speech): what wmi_full_get_window reports
+enum { WINDOW_EMITTED = 0, WINDOW_DROPPED = 1, WINDOW_GATED = 2 };
+struct WindowRec { int32_t seek = 0; float p = -1.0f; int32_t outcome = WINDOW_EMITTED, seg0 = 0, n_seg = 0; };
 
 // device scratch for one in-flight chunk; sized at init for the model's maxima
 struct DeviceState {
@@ -250,6 +253,9 @@ struct DeviceState {
     void  * draw_host = nullptr;                                   // DecStep[8] | u[8][8] | SampleOut[8][8] (pinned)
     void  * draw_scratch = nullptr;
     bool    step_capture_failed = false;                               // a failed capture is not retried
+    // the no-speech head (device.cpp: no_speech_*): block partials, the <sot> row's logits of a quantised prompt batch, the pinned {p, tag}
+    // records of up to k::NSP_MAX_ROWS rows, the tag of the last launch; nsp_row >= 0 asks the next decode() for the head on that batch row
+    void  * nsp_scratch = nullptr; float * nsp_logits = nullptr; void * nsp_host = nullptr; int32_t nsp_seq = 0; int nsp_row = -1;
     int     step_seen_T = -1;                                          // encoder length of recent steps (StepGraph::seen counts them)
 };
 
@@ -267,6 +273,7 @@ struct State {
     Decoder decoders[8];
     std::vector<float> logits;                    // [n_tokens][n_vocab] host copy (flagged rows only)
     std::vector<Segment> result_all;
+    std::vector<WindowRec> windows;               // its windows (empty in mode 0)
     std::vector<int32_t> prompt_past;
     int     lang_id = 0;
     std::vector<float> lang_probs;                // the language probabilities of the last full() that detected its language (empty: it did not)
@@ -314,6 +321,8 @@ struct BatchWork {
     bool chain_valid = false; int chain_nb = 0; int32_t chain_token[16] = {}, chain_pos[16] = {}; bool chain_row_ok[16] = {};
     std::vector<State *> lanes;                               // lanes[0] is the context's own state (not owned)
     std::vector<std::vector<Segment>> results;                // per chunk of the last wmi_full_batch call
+    std::vector<std::vector<WindowRec>> windows;          // per chunk: its windows (no-speech modes 1 - 3)
+    void * nsp_scratch = nullptr, * nsp_host = nullptr; int32_t nsp_seq = 0;   // the no-speech head of the lock-step rows (as DeviceState's)
     std::vector<int> redo;                                    // per chunk: 1 if it was re-run alone (temperature fallback)
     // per chunk: the language id whisper_full would report, whether it was detected, and the detection's probabilities [chunk][LANG_HEAD_N]
     std::vector<int> lang_id; std::vector<char> lang_detected; std::vector<float> lang_probs;
@@ -364,6 +373,7 @@ struct whisper_context {
     // have not arrived yet — every compute call fails until wmi_arena_commit() says the broadcast / peer copy has landed
     bool           weights_pending = false;
     wmi::BatchWork * batch = nullptr;   // lazily created by wmi_full_batch
+    int            no_speech_mode = 0;  // wmi_set_no_speech: 0 off, 1 report, 2 drop, 3 gate; read at the start of every transcription call
     // streams with a hardware queue of their own, made together with the context's first stream and handed to replica contexts later
     // (init_state: it is the ORDER in which the queues are created that decides whether the replicas run beside each other)
     std::vector<hipStream_t> spare_streams;
@@ -428,7 +438,9 @@ struct EncBufsQ {
 bool encode_layers_q_on(whisper_context & ctx, const EncBufsQ & e, hipStream_t s);
 void enqueue_rows_step_q(whisper_context & ctx, int nb);
 void enqueue_rows_lang_step_q(whisper_context & ctx, int nb, float * out);      // the same step ending in the language head (batch.cpp: detection)
-bool decode_layers_q(whisper_context & ctx, int n, int n_kv, int kv_head, int Tc, const std::vector<int> & rows, float * lang_out = nullptr);
+// nsp_row_dev (device, one batch row index): that row's raw logits also go to nsp_logits (the no-speech head reads them there)
+bool decode_layers_q(whisper_context & ctx, int n, int n_kv, int kv_head, int Tc, const std::vector<int> & rows, float * lang_out = nullptr,
+                     const int32_t * nsp_row_dev = nullptr, float * nsp_logits = nullptr);
 void enqueue_greedy_step_q(whisper_context & ctx, int Tc);
 // greedy fast path: decode ONE token of sequence 0 at position `pos` and pick the next token on the device
 struct StepFilter { bool ban_blank, last_ts, penult_ts; int ts_floor_end, ts_initial_start; };
@@ -454,6 +466,18 @@ enum : unsigned { STEP_FORM_LONG_KV = 1, STEP_FORM_CHAINED = 2, STEP_FORM_GRAPH 
                   STEP_FORM_BACKED = 32, STEP_FORM_RERUN = 64, STEP_FORM_SLOW = 128, STEP_FORM_QUANTISED = 256 };
 bool decode_greedy_step(whisper_context & ctx, int32_t token, int32_t pos, const StepFilter & f, whisper_token_data & out, unsigned * forms = nullptr);
 bool upload_static_ban(whisper_context & ctx, const whisper_full_params & params);
+// The no-speech probability of a window (kernels.h: no_speech_*).  A launch is tagged; no_speech_read waits for the record
+// with that tag (it is there already behind a wait the caller has made; otherwise one stream synchronisation) and hands p back.
+bool no_speech_ensure(whisper_context & ctx, DeviceState & d);
+// form 1 on `rows` of `logits` ([..][n_vocab], device) / form 0 on the residual row x (f16 models): the launches only
+bool no_speech_from_logits(whisper_context & ctx, const float * logits, int row);
+bool no_speech_from_row(whisper_context & ctx, const float * x);
+bool no_speech_read(State & st, float * p);
+// The driver's rule, shared by full() and the lock-step loop (pure): what becomes of a window whose <sot> row said p.  Before the
+// window's sampling steps only the answer "gate" matters (failed = false, avg_logprob = 0); behind them `failed` / `avg_logprob` are the
+// best decoder's.  0 emit, 1 fall back to the next temperature (where there is one), 2 drop, 3 gate.
+enum { NSP_EMIT = 0, NSP_FALLBACK = 1, NSP_DROP = 2, NSP_GATE = 3 };
+int  no_speech_rule(int mode, float p, float thold, bool failed, double avg_logprob, float logprob_thold);
 // k draws per row from the filtered distribution of logits row `rows[r]` of the last decode() (keep_logits_on_device), r < n_rows <= 8;
 // u [n_rows][k] uniform numbers in [0, 1) from the decoders' generators.  out [n_rows][k].
 bool sample_rows_device(whisper_context & ctx, const StepFilter * f, const int * rows, int n_rows, float temperature, int k,

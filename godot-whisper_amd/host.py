@@ -37,9 +37,13 @@ def _fptr(a: np.ndarray):
 class SpeechToText:
     """One `whisper_context` per node (src/speech_to_text.h:135); not re-entrant."""
 
-    def __init__(self, lib: C.CDLL, settings: dict | None = None):
+    def __init__(self, lib: C.CDLL, settings: dict | None = None, no_speech: int = 0):
+        """no_speech (product library only, include/wmi_device.h wmi_set_no_speech): 0 off — the reference's behaviour —, 1 report the
+        windows' no-speech probability, 2 drop (OpenAI's rule), 3 gate.  The windows of a call are in last_windows after collect()."""
         self.lib = lib
         self.ctx = None
+        self.no_speech = int(no_speech)
+        self.last_windows = []
         self.language = "en"  # Language enum -> code, src/speech_to_text.cpp:117-324
         self.settings = dict(SETTINGS)
         if settings:
@@ -56,6 +60,14 @@ class SpeechToText:
         cp = abi.whisper_context_params(bool(self.settings["audio/input/transcribe/use_gpu"]))
         self.ctx = self.lib.whisper_init_from_buffer_with_params(C.cast(buf, C.c_void_p), len(model_bytes), cp)
         del buf  # the loader only borrows the buffer during the call (W/whisper.cpp:3231-3240)
+        self.set_no_speech(self.no_speech)
+
+    def set_no_speech(self, mode: int) -> int:
+        """The context's no-speech mode from the next transcription call on; returns the previous one (0 without a context)."""
+        self.no_speech = int(mode)
+        if not self.ctx or not (self.no_speech or hasattr(self.lib, "wmi_set_no_speech")):
+            return 0
+        return self.lib.wmi_set_no_speech(self.ctx, self.no_speech)      # (a library without the call cannot serve a mode: AttributeError)
 
     def close(self):
         self.lib.whisper_free(self.ctx)
@@ -110,6 +122,21 @@ class SpeechToText:
                     "pt": t.pt, "ptsum": t.ptsum, "t0": t.t0, "t1": t.t1, "tid": t.tid, "vlen": t.vlen,
                 })
         out.insert(0, full_text)
+        self.last_windows = self.windows()
+        return out
+
+    def windows(self) -> list:
+        """The windows of the last call (or of the chunk selected last): seek in 10 ms frames, no_speech_prob, outcome (abi.WINDOW_*),
+        first segment, segment count.  Empty in mode 0 and for a library without the interface."""
+        lib, ctx = self.lib, self.ctx
+        if not ctx or not hasattr(lib, "wmi_full_n_windows"):
+            return []
+        out = []
+        for i in range(lib.wmi_full_n_windows(ctx)):
+            w = abi.wmi_window()
+            assert lib.wmi_full_get_window(ctx, i, C.byref(w)) == 0
+            out.append({"seek": w.seek, "no_speech_prob": w.no_speech_prob, "outcome": w.outcome, "i_segment": w.i_segment,
+                        "n_segments": w.n_segments})
         return out
 
     # -- several independent buffers at once (product library only: include/wmi_device.h wmi_full_batch).  The
@@ -141,8 +168,9 @@ class SpeechToText:
         return self.collect_batch(n)
 
     def collect_batch(self, n: int) -> list:
-        """The n results of the last lock-step call (wmi_batch_select), and last_modes / last_langs."""
+        """The n results of the last lock-step call (wmi_batch_select), and last_modes / last_langs / last_batch_windows."""
         out = []
+        self.last_batch_windows = []
         self.last_modes = []
         self.last_langs = []                                          # per chunk: the language id whisper_full would report (detected with "auto")
         for c in range(n):
@@ -150,6 +178,7 @@ class SpeechToText:
             self.last_modes.append(self.lib.wmi_batch_chunk_mode(self.ctx, c))
             self.last_langs.append(self.lib.wmi_batch_lang_id(self.ctx, c))
             out.append(self.collect())
+            self.last_batch_windows.append(self.last_windows)
         return out
 
     # -- resample (src/speech_to_text.cpp:353-376): stereo capture frames at the mix rate -> mono 16 kHz.  The reference goes through
@@ -324,12 +353,19 @@ class CaptureStreamToText(SpeechToText):
     16 kHz PCM stay on the device) or, for comparison, over resample() / voice_activity_detection() / transcribe() on host arrays."""
 
     def __init__(self, lib, settings=None, transcribe_interval: float = 0.3, minimum_sentence_ms: int = 3000,
-                 maximum_sentence_ms: int = 15000, punctuation_characters: str = ".!?;。；？！"):
-        super().__init__(lib, settings)
+                 maximum_sentence_ms: int = 15000, punctuation_characters: str = ".!?;。；？！", no_speech_gate: bool = False):
+        """no_speech_gate: transcribe in the no-speech mode "gate" (wmi_set_no_speech 3).  A step whose window was gated is treated like
+        "no activity": nothing is emitted for it and the loop goes on."""
+        super().__init__(lib, settings, no_speech=abi.NO_SPEECH_GATE if no_speech_gate else 0)
+        self.no_speech_gate = bool(no_speech_gate)
         self.interval = transcribe_interval
         self.min_ms = minimum_sentence_ms
         self.max_ms = maximum_sentence_ms
         self.punct = punctuation_characters
+
+    def _gated(self, tokens: list) -> bool:
+        """The call just collected produced no tokens because its window was gated (no_speech_gate)."""
+        return self.no_speech_gate and len(tokens) <= 1 and any(w["outcome"] == abi.WINDOW_GATED for w in self.last_windows)
 
     def stream(self, pcm16k: np.ndarray, max_calls: int | None = None):
         """Yield (is_final, text, n_samples_used, audio_ctx, token dicts) per transcribe call."""
@@ -348,6 +384,10 @@ class CaptureStreamToText(SpeechToText):
             tokens = self.transcribe(acc, "", audio_ctx)
             calls += 1
             if not tokens:
+                continue
+            if self._gated(tokens):
+                if max_calls is not None and calls >= max_calls:
+                    return
                 continue
             text = remove_special_characters(tokens.pop(0).decode("utf-8", errors="replace"))
             n_tok = len(tokens)
@@ -415,6 +455,10 @@ class CaptureStreamToText(SpeechToText):
                 calls += 1
                 if not tokens:
                     return                                                          # push_warning("No tokens generated") (:88-90)
+                if self._gated(tokens):
+                    if max_calls is not None and calls >= max_calls:
+                        return
+                    continue
                 full_text = tokens.pop(0).decode("utf-8", errors="replace")
                 finish = total_time > maximum_sentence_time
                 text = remove_special_characters("".join(t["text"].decode("utf-8", errors="replace") for t in tokens))

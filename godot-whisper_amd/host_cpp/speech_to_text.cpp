@@ -28,6 +28,14 @@ void SpeechToText::set_language_model(const uint8_t * data, size_t size) {   // 
     if (data == nullptr || size == 0) return;
     const whisper_context_params context_params{ settings.use_gpu };
     context_instance = whisper_init_from_buffer_with_params((void *) data, size, context_params);
+    if (context_instance && no_speech != 0) (void) wmi_set_no_speech(context_instance, no_speech);
+}
+
+int SpeechToText::set_no_speech(int mode) {
+    const int prev = no_speech;
+    no_speech = mode < 0 ? 0 : (mode > 3 ? 3 : mode);
+    if (context_instance) (void) wmi_set_no_speech(context_instance, no_speech);
+    return prev;
 }
 
 std::vector<float> SpeechToText::resample(const std::vector<float> & interleaved_xy, InterpolatorType interpolator_type, int mix_rate) {   // src/speech_to_text.cpp:353-376
@@ -79,12 +87,14 @@ Transcription SpeechToText::collect() const {                            // src/
     for (int i = 0; i < n_segments; ++i) {
         const int n_tokens = whisper_full_n_tokens(context_instance, i);
         out.full_text += whisper_full_get_segment_text(context_instance, i);
+        const float no_speech_prob = wmi_full_get_segment_no_speech_prob(context_instance, i);
         for (int j = 0; j < n_tokens; ++j) {
             const whisper_token_data token = whisper_full_get_token_data(context_instance, i, j);
             Token t;
             t.text = whisper_full_get_token_text(context_instance, i, j);
             t.id = token.id; t.p = token.p; t.plog = token.plog; t.pt = token.pt; t.ptsum = token.ptsum;
             t.t0 = token.t0; t.t1 = token.t1; t.tid = token.tid; t.vlen = token.vlen;
+            t.no_speech_prob = no_speech_prob;
             out.tokens.push_back(std::move(t));
         }
     }

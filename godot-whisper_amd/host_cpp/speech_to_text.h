@@ -33,6 +33,7 @@ struct Token {
     int32_t id = 0, tid = 0;
     float   p = 0, plog = 0, pt = 0, ptsum = 0, vlen = 0;
     int64_t t0 = 0, t1 = 0;
+    float   no_speech_prob = -1.0f;   // not in the reference: of the token's segment (wmi_full_get_segment_no_speech_prob; -1 with set_no_speech(0))
 };
 // the Array itself: element 0 is the full text, the rest are the token dictionaries (:447)
 struct Transcription {
@@ -55,6 +56,10 @@ public:
     int  get_language() const { return language; }
     // set_language_model(Ref<WhisperResource>) + _load_model(): the resource's bytes (src/resource_whisper.h)
     void set_language_model(const uint8_t * data, size_t size);
+    // not in the reference: the context's no-speech mode (include/wmi_device.h wmi_set_no_speech: 0 off, 1 report, 2 drop, 3 gate), kept
+    // across set_language_model.  Returns the previous mode.
+    int  set_no_speech(int mode);
+    int  get_no_speech() const { return no_speech; }
 
     // src/speech_to_text.h:151-156, :162 — resample(PackedVector2Array buffer, InterpolatorType): stereo capture frames at the mix rate
     // -> mono 16 kHz.  The reference folds on the CPU and calls libsamplerate's src_simple; here both steps run on the device
@@ -81,6 +86,7 @@ protected:
 
     TranscribeSettings settings;
     int language = English;
+    int no_speech = 0;
     whisper_context * context_instance = nullptr;
 };
 

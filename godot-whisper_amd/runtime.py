@@ -107,6 +107,16 @@ DEVICE_API = [
     ("wmi_selftest_qkv_encoder_q", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                              C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("wmi_selftest_lockstep_sets", C.c_int, [C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    ("wmi_set_no_speech", C.c_int, [C.c_void_p, C.c_int]),
+    ("wmi_full_n_windows", C.c_int, [C.c_void_p]),
+    ("wmi_full_get_window", C.c_int, [C.c_void_p, C.c_int, C.POINTER(abi.wmi_window)]),
+    ("wmi_full_get_segment_no_speech_prob", C.c_float, [C.c_void_p, C.c_int]),
+    ("wmi_full_n_windows_from_state", C.c_int, [C.c_void_p]),
+    ("wmi_full_get_window_from_state", C.c_int, [C.c_void_p, C.c_int, C.POINTER(abi.wmi_window)]),
+    ("wmi_full_get_segment_no_speech_prob_from_state", C.c_float, [C.c_void_p, C.c_int]),
+    ("wmi_selftest_no_speech_rule", C.c_int, [C.c_int, C.c_float, C.c_float, C.c_int, C.c_double, C.c_float]),
+    ("wmi_selftest_no_speech", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                         C.c_void_p, C.c_void_p]),
 ]
 
 _lib = None

@@ -508,6 +508,52 @@ WHISPER_API int wmi_selftest_seqsum(const float * x, int n, float * out_blocked,
  * — W/whisper.cpp:3600-3641).  -1: logits100 is NULL. */
 WHISPER_API int wmi_selftest_lang_probs(const float * logits100, float * probs100);
 
+/* The no-speech probability (OpenAI's no_speech_prob) and params.no_speech_thold.
+ * For every 30 s window: the decoder's RAW logits l at the prompt row that carries <sot> — no temperature, no filter, no ban; the row
+ * attends to whatever [prev ...] tokens precede it — and p = exp(l[nosp] - m) / sum_i exp(l[i] - m), m = max l, over the whole vocabulary.
+ * Computed on the device (csrc/k_nospeech.hip) with a fixed arithmetic: the l are the f32 logits of the vocabulary projection; the
+ * vocabulary is cut into blocks of 128 entries; a block keeps m_b = max l and s_b = sum exp(l - m_b), the difference in f32, exp and sums
+ * in double; the blocks are combined in ascending order, S = sum_b s_b exp(m_b - M) with M = max m_b (difference in f32 again),
+ * p = exp(l[nosp] - M) / S rounded to f32 once; an entry of -inf adds 0.  The same call twice gives the same bits.
+ *   wmi_set_no_speech   the context's mode, read at the START of every whisper_full* / wmi_full_* / wmi_capture_full* / wmi_pool_full call
+ *                       on it (wmi_pool_full: each pool context's own mode).  Returns the previous mode, -2 for a NULL context.
+ *     0  off (the default): nothing is launched, nothing is stored, every result is what it was without this interface
+ *     1  report: p is computed and stored; results otherwise as mode 0
+ *     2  drop (OpenAI's rule): at a window with p > params.no_speech_thold the temperature fallback is not taken, and the window is
+ *        dropped when its decoder failed or avg_logprobs < params.logprob_thold — no segments, seek += 3000, prompt_past untouched;
+ *        otherwise it is emitted as decoded
+ *     3  gate: a window with p > params.no_speech_thold ends right behind its <sot> step, with no sampling step — no segments, the same
+ *        seek advance, prompt_past untouched
+ *   wmi_full_n_windows / wmi_full_get_window   the windows of the last call (none in mode 0), in order; after wmi_batch_select /
+ *        wmi_pool_select those of that chunk.  wmi_full_get_window returns 0, -1 for a bad index.
+ *   wmi_full_get_segment_no_speech_prob        p of the window that emitted segment i_segment; -1.0f in mode 0 or for a bad index
+ * p is taken once per window (at the first temperature), also where the window falls back to higher temperatures. */
+struct wmi_window {
+    int32_t seek;            /* start of the window, 10 ms frames */
+    float   no_speech_prob;
+    int32_t outcome;         /* 0 emitted, 1 dropped, 2 gated */
+    int32_t i_segment;       /* its first segment (the segment count so far for a window without segments) */
+    int32_t n_segments;
+};
+WHISPER_API int   wmi_set_no_speech(struct whisper_context * ctx, int mode);
+WHISPER_API int   wmi_full_n_windows(struct whisper_context * ctx);
+WHISPER_API int   wmi_full_get_window(struct whisper_context * ctx, int i, struct wmi_window * out);
+WHISPER_API float wmi_full_get_segment_no_speech_prob(struct whisper_context * ctx, int i_segment);
+WHISPER_API int   wmi_full_n_windows_from_state(struct whisper_state * state);
+WHISPER_API int   wmi_full_get_window_from_state(struct whisper_state * state, int i, struct wmi_window * out);
+WHISPER_API float wmi_full_get_segment_no_speech_prob_from_state(struct whisper_state * state, int i_segment);
+/* The driver's rule on its own (host only, no device): what becomes of a window in `mode` whose <sot> row said p, given the best
+ * decoder's failed flag and avg_logprob.  0 emit, 1 fall back to the next temperature (where one is left), 2 drop, 3 gate. */
+WHISPER_API int   wmi_selftest_no_speech_rule(int mode, float p, float thold, int failed, double avg_logprob, float logprob_thold);
+/* The no-speech kernels on caller data (no context; all host pointers).  rows in 1 .. 16 share one launch (the row on grid.y).
+ *   form 1  logits [rows][n_vocab] f32
+ *   form 0  the fused head: W f16 bit patterns [n_vocab][K], x f32 [rows][K]; logits = W . LayerNorm(x) with gain 1, bias 0, eps 1e-5,
+ *           made and reduced inside the launch, never written.  K % 8 == 0, 8 <= K <= 1536.  logits_out (optional, [rows][n_vocab])
+ *           receives the product's own one-row vocabulary projection (EPI_LOGITS) of the same rows — the same bits.
+ * p_out [rows].  Returns 0; -1 bad argument, before the device is touched; -2 / -3 device errors. */
+WHISPER_API int   wmi_selftest_no_speech(int device, int form, int rows, int n_vocab, int nosp, const float * logits, const uint16_t * W,
+                                         const float * x, int K, float * logits_out, float * p_out);
+
 /* Host worker pool self-test (no device needed): `reps` jobs of `n_tasks` tasks; returns reps * n_tasks * (n_tasks + 1) / 2
  * when every task of every job ran exactly once. */
 WHISPER_API int64_t wmi_selftest_pool(int n_tasks, int reps);
