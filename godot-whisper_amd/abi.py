@@ -193,6 +193,7 @@ class wmi_window(C.Structure):  # include/wmi_device.h: a 30 s window of a call 
 
 NO_SPEECH_OFF, NO_SPEECH_REPORT, NO_SPEECH_DROP, NO_SPEECH_GATE = range(4)       # wmi_set_no_speech modes
 WINDOW_EMITTED, WINDOW_DROPPED, WINDOW_GATED = range(3)                          # wmi_window.outcome
+TOKEN_DTW_OFF, TOKEN_DTW_ON = range(2)                                           # wmi_set_token_dtw modes
 
 
 class whisper_model_loader(C.Structure):  # W/whisper.h:108-114

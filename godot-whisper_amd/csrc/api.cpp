@@ -717,7 +717,19 @@ int wmi_get_tensor(struct whisper_context * ctx, const char * name, float * dst,
         if (!d.energy || !HIP_OK(hipMemcpy(dst, d.energy, (size_t) n * 4, hipMemcpyDeviceToHost))) return -1;
         return n;
     }
+    // the last window aligned on this state (wmi_set_token_dtw): A [R][M], the query rows used [n_pairs][n][64], the path's jumps [R]
+    if (nm == "dtw_jumps") {
+        const int cnt = (int) st.dtw_jumps.size();
+        if (!dst) return cnt;
+        if (n > cnt) n = cnt;
+        for (int i = 0; i < n; ++i) dst[i] = (float) st.dtw_jumps[i];
+        return n < 0 ? 0 : n;
+    }
     if (nm == "mel")            { src = d.mel; count = (size_t) st.mel.n_len * st.mel.n_mel; }
+    // the last text layer's scaled cross query of the last whisper_decode / prompt batch: [rows][n_text_state] f16
+    else if (nm == "dec_cross_q") { src = d.dq; count = (size_t) d.dec_n * hp.n_text_state; is_half = true; }
+    else if (nm == "dtw_matrix") { src = d.dtw.A; count = (size_t) st.dtw_last.R * st.dtw_last.M; }
+    else if (nm == "dtw_q")      { src = d.dtw.q; count = (size_t) st.dtw_last.n_pairs * st.dtw_last.n * k::ALIGN_HEAD_DIM; is_half = true; }
     else if (nm == "embd_conv") { src = d.embd_conv; count = (size_t) T * S; }
     else if (nm == "embd_enc")  { src = d.enc_out; count = (size_t) T * S; }
     else if (nm == "enc_x")     { src = d.x; count = (size_t) T * S; }
@@ -1077,6 +1089,76 @@ int wmi_selftest_no_speech(int device, int form, int rows, int n_vocab, int nosp
     if (!ok) return -3;
     if (!HIP_OK(hipStreamSynchronize(b.st)) || !HIP_OK(hipGetLastError())) return -3;
     for (int r = 0; r < rows; ++r) { if (out[r].tag != tag) return -3; p_out[r] = out[r].p; }
+    return 0;
+}
+
+namespace {
+struct AlignSelf {                                            // the hooks' device buffers, freed on every way out
+    std::vector<void *> dev; void * host = nullptr; hipStream_t st = nullptr;
+    ~AlignSelf() { if (st) (void) hipStreamDestroy(st); for (void * q : dev) (void) hipFree(q); if (host) (void) hipHostFree(host); }
+    void * get(size_t bytes) { void * q = nullptr; if (!HIP_OK(hipMalloc(&q, bytes ? bytes : 1))) return nullptr; dev.push_back(q); return q; }
+};
+}
+
+int wmi_selftest_dtw_matrix(int device, int L, int S, int H, int n, int n_sot, int M, int T, const uint16_t * q, const uint16_t * kk,
+                            const int32_t * layer_head, int n_pairs, float * A_out) {
+    if (L < 1 || !q || !kk || !layer_head || !A_out || n_pairs < 1 || T < M || T > k::ALIGN_MAX_M || H > k::ALIGN_MAX_HEADS ||
+        !k::align_shape_ok(n, n_sot, M, S, H)) return -1;
+    int nh_max = 0;
+    for (int i = 0, run = 0; i < n_pairs; ++i) {
+        const int32_t l = layer_head[2 * i], h = layer_head[2 * i + 1];
+        if (l < 0 || l >= L || h < 0 || h >= H) return -1;
+        if (i > 0 && (l < layer_head[2 * i - 2] || (l == layer_head[2 * i - 2] && h <= layer_head[2 * i - 1]))) return -1;
+        run = (i > 0 && l == layer_head[2 * i - 2]) ? run + 1 : 1;
+        nh_max = std::max(nh_max, run);
+    }
+    if (!HIP_OK(hipSetDevice(device))) return -2;
+    const int R = n - n_sot - 1;
+    AlignSelf b;
+    k::AlignBufs ab{};
+    ab.w = (float *) b.get(k::align_w_floats(nh_max, n, M) * 4); ab.mu = (float *) b.get((size_t) nh_max * M * 4); ab.sigma = (float *) b.get((size_t) nh_max * M * 4);
+    ab.A = (float *) b.get((size_t) R * M * 4); ab.cost = (float *) b.get(k::align_cost_floats(R, M) * 4); ab.q = nullptr;
+    __half * d_q = (__half *) b.get((size_t) L * n * S * 2), * d_k = (__half *) b.get((size_t) L * T * S * 2);
+    if (!ab.w || !ab.mu || !ab.sigma || !ab.A || !ab.cost || !d_q || !d_k || !HIP_OK(hipStreamCreate(&b.st))) return -3;
+    if (!HIP_OK(hipMemcpyAsync(d_q, q, (size_t) L * n * S * 2, hipMemcpyHostToDevice, b.st)) ||
+        !HIP_OK(hipMemcpyAsync(d_k, kk, (size_t) L * T * S * 2, hipMemcpyHostToDevice, b.st))) return -3;
+    for (int i = 0; i < n_pairs; ) {                          // layer by layer, as decode()'s hook does
+        k::AlignHeads hs{};
+        const int l = layer_head[2 * i], pair0 = i;
+        while (i < n_pairs && layer_head[2 * i] == l) hs.head[hs.n++] = layer_head[2 * i++ + 1];
+        if (!k::align_layer(ab, d_q + (size_t) l * n * S, n, S, d_k + (size_t) l * T * S, M, hs, pair0, n_sot, b.st)) return -3;
+    }
+    if (!k::align_finish(ab, R, M, n_pairs, b.st)) return -3;
+    if (!HIP_OK(hipMemcpyAsync(A_out, ab.A, (size_t) R * M * 4, hipMemcpyDeviceToHost, b.st)) || !HIP_OK(hipStreamSynchronize(b.st)) ||
+        !HIP_OK(hipGetLastError())) return -3;
+    return 0;
+}
+
+int wmi_selftest_dtw_path(int device, int R, int M, const float * A, int32_t * jumps, int32_t * path, int * n_path) {
+    if (R < 1 || M < 1 || !A || !jumps || !path || !n_path) return -1;
+    if (device < 0) { dtw_path_host(R, M, A, jumps, path, n_path); return 0; }
+    if (R > k::ALIGN_MAX_R) return -1;
+    if (!HIP_OK(hipSetDevice(device))) return -2;
+    AlignSelf b;
+    float * d_A = (float *) b.get((size_t) R * M * 4), * d_cost = (float *) b.get(k::align_cost_floats(R, M) * 4);
+    uint8_t * d_tr = (uint8_t *) b.get((size_t) R * M);
+    int32_t * d_path = (int32_t *) b.get((size_t) (R + M) * 2 * 4);
+    const size_t hb = sizeof(k::AlignOut) + k::ALIGN_DTW_THREADS * sizeof(int32_t);
+    if (!d_A || !d_cost || !d_tr || !d_path || !HIP_OK(hipHostMalloc(&b.host, hb, hipHostMallocDefault)) || !HIP_OK(hipStreamCreate(&b.st))) return -3;
+    memset(b.host, 0, hb);
+    k::AlignOut * out = (k::AlignOut *) b.host;
+    const int32_t tag = 0x5eed;
+    if (!HIP_OK(hipMemcpyAsync(d_A, A, (size_t) R * M * 4, hipMemcpyHostToDevice, b.st))) return -3;
+    k::align_cost_from_matrix(d_A, R, M, d_cost, b.st);
+    if (!k::align_dtw(d_cost, R, M, d_tr, d_path, (int32_t *) (out + 1), out, tag, b.st)) return -3;
+    std::vector<int32_t> hp_((size_t) (R + M) * 2);
+    if (!HIP_OK(hipMemcpyAsync(hp_.data(), d_path, hp_.size() * 4, hipMemcpyDeviceToHost, b.st)) || !HIP_OK(hipStreamSynchronize(b.st)) ||
+        !HIP_OK(hipGetLastError())) return -3;
+    if (out->tag != tag || out->n_path < 1 || out->n_path > R + M) return -3;
+    const int np = out->n_path;
+    memcpy(path, hp_.data() + 2 * (size_t) (R + M - np), (size_t) np * 2 * 4);
+    memcpy(jumps, out + 1, (size_t) R * 4);
+    *n_path = np;
     return 0;
 }
 

@@ -12,6 +12,7 @@
 #include "wmi.h"
 #include "kernels.h"
 
+#include <algorithm>
 #include <cstring>
 #include <fstream>
 #include <thread>
@@ -287,6 +288,55 @@ int wmi_set_no_speech(struct whisper_context * ctx, int mode) {
     const int prev = ctx->no_speech_mode;
     ctx->no_speech_mode = mode < 0 ? 0 : (mode > 3 ? 3 : mode);
     return prev;
+}
+// token times by DTW (wmi_device.h)
+int wmi_set_token_dtw(struct whisper_context * ctx, int mode, const int32_t * layer_head, int n_pairs) {
+    if (!ctx) return -2;
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    const HParams & hp = ctx->model.hp;
+    if (n_pairs < 0 || (n_pairs > 0 && !layer_head)) return -1;
+    std::vector<std::pair<int32_t, int32_t>> pr;
+    for (int i = 0; i < n_pairs; ++i) {
+        const int32_t l = layer_head[2 * i], h = layer_head[2 * i + 1];
+        if (l < 0 || l >= hp.n_text_layer || h < 0 || h >= hp.n_text_head) return -1;
+        pr.emplace_back(l, h);
+    }
+    std::sort(pr.begin(), pr.end());
+    for (size_t i = 1; i < pr.size(); ++i) if (pr[i] == pr[i - 1]) return -1;
+    const int prev = ctx->token_dtw_mode;
+    ctx->token_dtw_mode = mode != 0 ? 1 : 0;
+    ctx->dtw_pairs.clear();
+    for (const auto & q : pr) { ctx->dtw_pairs.push_back(q.first); ctx->dtw_pairs.push_back(q.second); }
+    return prev;
+}
+int wmi_token_dtw_heads(struct whisper_context * ctx, int32_t * layer_head, int cap) {
+    if (!ctx) return -2;
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    const std::vector<int32_t> pr = ctx->dtw_pairs.empty() ? dtw_default_pairs(ctx->model.hp) : ctx->dtw_pairs;
+    const int n = (int) pr.size() / 2;
+    for (int i = 0; layer_head && i < n && i < cap; ++i) { layer_head[2 * i] = pr[2 * i]; layer_head[2 * i + 1] = pr[2 * i + 1]; }
+    return n;
+}
+int64_t wmi_full_get_token_dtw_from_state(struct whisper_state * state, int i_segment, int i_token) {
+    if (!state || i_segment < 0 || i_segment >= (int) S(state)->result_all.size()) return -1;
+    const Segment & seg = S(state)->result_all[i_segment];
+    if (i_token < 0 || i_token >= (int) seg.t_dtw.size()) return -1;
+    return seg.t_dtw[i_token];
+}
+int64_t wmi_full_get_token_dtw(struct whisper_context * ctx, int i_segment, int i_token) {
+    return ctx && ctx->state ? wmi_full_get_token_dtw_from_state(reinterpret_cast<struct whisper_state *>(ctx->state.get()), i_segment, i_token) : -1;
+}
+int wmi_token_dtw_dims(struct whisper_context * ctx, int * n, int * n_sot, int * R, int * M, int * n_pairs) {
+    if (!ctx || !ctx->state) return -1;
+    const State::DtwDims & dd = ctx->state->dtw_last;
+    if (dd.R < 1) return -1;
+    if (n) *n = dd.n; if (n_sot) *n_sot = dd.n_sot; if (R) *R = dd.R; if (M) *M = dd.M; if (n_pairs) *n_pairs = dd.n_pairs;
+    return 0;
+}
+void wmi_get_token_dtw_timings(struct whisper_context * ctx, int64_t * us, int32_t * n_windows) {
+    const bool have = ctx && ctx->state;
+    if (us) *us = have ? ctx->state->t_dtw_us : 0;
+    if (n_windows) *n_windows = have ? ctx->state->n_dtw : 0;
 }
 int wmi_selftest_no_speech_rule(int mode, float p, float thold, int failed, double avg_logprob, float logprob_thold) {
     return no_speech_rule(mode, p, thold, failed != 0, avg_logprob, logprob_thold);

@@ -791,7 +791,8 @@ int full_batch(whisper_context & ctx, whisper_full_params params, const float * 
     // a language to be detected: multilingual models detect every chunk in one lock-step step (below); English-only models keep the
     // one-at-a-time path, where full() decides what "auto" means for them
     const bool lang_ok = lang_known || (v.is_multilingual() && k::lang_head_usable(hp.n_text_state));
-    const bool lockstep = params.strategy == WHISPER_SAMPLING_GREEDY && params.temperature < 1e-6f &&
+    // (token alignment on: every chunk takes the general driver, which runs the alignment pass behind each window)
+    const bool lockstep = params.strategy == WHISPER_SAMPLING_GREEDY && params.temperature < 1e-6f && ctx.token_dtw_mode == 0 &&
                           lang_ok && !distilled && !params.speed_up && !params.logits_filter_callback && !params.grammar_rules && params.n_grammar_rules == 0 && !params.new_segment_callback &&
                           !params.progress_callback && !params.encoder_begin_callback && !params.abort_callback &&
                           ctx.model.n_loaded > 0 && (n_chunks > 1 || audio_ctx != nullptr || t_ordered);
@@ -825,7 +826,7 @@ int full_batch(whisper_context & ctx, whisper_full_params params, const float * 
                     if (w == 0) rc = run_alone(c);
                     else {
                         for (auto & dec : wc.state->decoders) dec.rng = std::mt19937(0);
-                        wc.no_speech_mode = nsm;
+                        wc.no_speech_mode = nsm; wc.token_dtw_mode = ctx.token_dtw_mode; wc.dtw_pairs = ctx.dtw_pairs;
                         rc = full(wc, params_of(c), on_device ? nullptr : pcm[c], on_device ? pcm[c] : nullptr, n_samples[c]);
                         if (rc == 0) { ctx.batch->results[c] = std::move(wc.state->result_all); ctx.batch->windows[c] = std::move(wc.state->windows); keep_lang(c, *wc.state); }
                         wc.state->result_all.clear(); wc.state->windows.clear();
@@ -923,7 +924,7 @@ int full_batch(whisper_context & ctx, whisper_full_params params, const float * 
                     whisper_context & wc = g == 0 ? ctx : *ctx.batch->replicas[g - 1];
                     (void) hipSetDevice(ctx.device);
                     if (g > 0 && wc.batch) wc.batch->groups_wanted = 1;
-                    wc.no_speech_mode = nsm;
+                    wc.no_speech_mode = nsm; wc.token_dtw_mode = ctx.token_dtw_mode; wc.dtw_pairs = ctx.dtw_pairs;
                     t_in_group = true;
                     struct Off { ~Off() { t_in_group = false; } } off;
                     const int cnt = c0[g + 1] - c0[g];

@@ -220,6 +220,9 @@ void destroy_state(State * st) {
     if (d.nsp_scratch) (void) hipFree(d.nsp_scratch);
     dfree(d.nsp_logits);
     if (d.nsp_host) (void) hipHostFree(d.nsp_host);
+    for (void * q : { (void *) d.dtw.w, (void *) d.dtw.mu, (void *) d.dtw.sigma, (void *) d.dtw.A, (void *) d.dtw.cost, (void *) d.dtw.trace, (void *) d.dtw.q })
+        if (q) (void) hipFree(q);
+    if (d.dtw_host) (void) hipHostFree(d.dtw_host);
     if (d.pinned) (void) hipHostFree(d.pinned);
     if (d.stream && d.stream_own_queue) own_queue_stream_put(st->device, d.stream);
     else if (d.stream) (void) hipStreamDestroy(d.stream);
@@ -545,6 +548,7 @@ bool decode(whisper_context & ctx, const Batch & batch, float * lang_logits) {
     // the device and pinned staging buffers hold n_text_ctx rows (the reference's decoder graph is measured for that many, W/whisper.cpp:3098-3110)
     if (n > hp.n_text_ctx) { WMI_ERR("%s: %d tokens in one batch, the model's text context is %d\n", __func__, n, hp.n_text_ctx); return false; }
     if (!kv_find_slot(kv, batch)) return false;                   // W/whisper.cpp:2540
+    d.dec_n = n;
     kv.n = (uint32_t) kv_cell_max(kv);
     const int n_kv = (int) kv.n, kv_head = (int) kv.head, n_ctx = (int) kv.size;
     const int S = hp.n_text_state, H = hp.n_text_head, Lt = hp.n_text_layer, NV = hp.n_vocab;
@@ -561,6 +565,13 @@ bool decode(whisper_context & ctx, const Batch & batch, float * lang_logits) {
     // d.logits when it is among the rows that asked for them (nsp_slot); otherwise its index rides behind theirs in the staging block
     const int nsp_row = d.nsp_row < n ? d.nsp_row : -1;
     d.nsp_row = -1;
+    // the alignment pass of a window (dtw_window), a request for this call only: the hook behind every layer's cross query, no row asks
+    // for logits, nothing goes to the host's logits image or into the reference's timers
+    const bool dtw = d.dtw_collect;
+    d.dtw_collect = false;
+    if (dtw && (lang_logits || !rows.empty() || nsp_row >= 0)) return false;
+    struct DtwActive { bool & f; ~DtwActive() { f = false; } } dtw_active{d.dtw_active};
+    d.dtw_active = dtw;
     int nsp_slot = -1;
     if (nsp_row >= 0) {
         if (lang_logits || !no_speech_ensure(ctx, d)) return false;
@@ -585,6 +596,7 @@ bool decode(whisper_context & ctx, const Batch & batch, float * lang_logits) {
         const bool nsp_own = nsp_row >= 0 && nsp_slot < 0;
         if (!decode_layers_q(ctx, n, n_kv, kv_head, Tc, rows, lang_pinned, nsp_own ? d.d_rows + rows.size() : nullptr, nsp_own ? d.nsp_logits : nullptr)) return false;
         if (nsp_row >= 0 && !(nsp_own ? no_speech_from_logits(ctx, d.nsp_logits, 0) : no_speech_from_logits(ctx, d.logits, nsp_slot))) return false;
+        if (dtw) return HIP_OK(hipGetLastError());           // (no wait here: dtw_window waits once, behind the path)
         HIP_TRY(hipStreamSynchronize(s));
         if (!HIP_OK(hipGetLastError())) return false;
         if (lang_logits) memcpy(lang_logits, lang_pinned, k::LANG_HEAD_N * sizeof(float));
@@ -629,6 +641,7 @@ bool decode(whisper_context & ctx, const Batch & batch, float * lang_logits) {
         proj(k::EPI_F32_BIAS_RESID, nullptr, nullptr, d.datt, S, S, l.w_o, l.b_o, d.dx, S, d.dx, nullptr, 0, nullptr, 0, 0.f);
         // cross-attention against the encoder K/V of this layer, no mask (W/whisper.cpp:2359-2433)
         proj(k::EPI_Q_SCALED, l.ln2_g, l.ln2_b, nullptr, S, S, l.w_cq, l.b_cq, d.dq, S, nullptr, nullptr, 0, nullptr, 0, kq_scale);
+        if (dtw && !dtw_layer(ctx, il, n, Tc)) return false;
         k::attn_cross_split(d.dq, n, S, H, d.kvc_k + (size_t) il * Tc * S, d.kvc_v + (size_t) il * Tc * S, Tc, d.xattn, d.datt, s);
         proj(k::EPI_F32_BIAS_RESID, nullptr, nullptr, d.datt, S, S, l.w_co, l.b_co, d.dx, S, d.dx, nullptr, 0, nullptr, 0, 0.f);
         // MLP
@@ -638,6 +651,7 @@ bool decode(whisper_context & ctx, const Batch & batch, float * lang_logits) {
 
     // final LN + logits = d_te . x for the rows that asked for them (the reference computes all rows
     // and copies out the flagged ones, W/whisper.cpp:2498, 2566-2572)
+    if (dtw) return HIP_OK(hipGetLastError());               // (no row asked for logits, the host's image is left alone; no wait here: dtw_window waits once, behind the path)
     if (lang_logits) k::lang_head(d.dx, 1, S, w.d_ln_g, w.d_ln_b, hp.eps, w.d_te + (size_t) (ctx.model.vocab.sot + 1) * S, lang_pinned, s);
     else st.logits.resize((size_t) n * NV);
     for (size_t r0 = 0; r0 < rows.size() && !lang_logits; r0 += 8) {
@@ -663,6 +677,88 @@ bool decode(whisper_context & ctx, const Batch & batch, float * lang_logits) {
     if (n == 1)      { st.t_decode_us += dt; st.n_decode++; }
     else if (n < 16) { st.t_batchd_us += dt; st.n_batchd += n; }
     else             { st.t_prompt_us += dt; st.n_prompt += n; }
+    return true;
+}
+
+// ------------------------------------------------------------------------------------------------ token alignment
+std::vector<int32_t> dtw_default_pairs(const HParams & hp) {
+    std::vector<int32_t> p;
+    for (int l = hp.n_text_layer / 2; l < hp.n_text_layer; ++l) for (int h = 0; h < hp.n_text_head; ++h) { p.push_back(l); p.push_back(h); }
+    return p;
+}
+
+// grow-only: slot i of dtw_cap is the bytes held at the i-th buffer
+bool dtw_ensure(DeviceState & d, int nh, int n, int R, int M, int n_pairs) {
+    auto grow = [&](void ** p, int slot, size_t bytes) {
+        if (d.dtw_cap[slot] >= bytes && *p) return true;
+        if (*p) { (void) hipFree(*p); *p = nullptr; d.dtw_cap[slot] = 0; }
+        if (!HIP_OK(hipMalloc(p, bytes))) return false;
+        d.dtw_cap[slot] = bytes;
+        return true;
+    };
+    if (!grow((void **) &d.dtw.w, 0, k::align_w_floats(nh, n, M) * 4) || !grow((void **) &d.dtw.mu, 1, (size_t) nh * M * 4) ||
+        !grow((void **) &d.dtw.sigma, 2, (size_t) nh * M * 4) || !grow((void **) &d.dtw.A, 3, (size_t) R * M * 4) ||
+        !grow((void **) &d.dtw.cost, 4, k::align_cost_floats(R, M) * 4) || !grow((void **) &d.dtw.trace, 5, (size_t) R * M) ||
+        !grow((void **) &d.dtw.q, 6, (size_t) n_pairs * n * k::ALIGN_HEAD_DIM * 2)) {
+        WMI_ERR("%s: device allocation failed (n = %d, M = %d, %d pairs)\n", __func__, n, M, n_pairs);
+        return false;
+    }
+    if (!d.dtw_host) {
+        void * h = nullptr;
+        HIP_TRY(hipHostMalloc(&h, sizeof(k::AlignOut) + k::ALIGN_DTW_THREADS * sizeof(int32_t), hipHostMallocDefault));
+        memset(h, 0, sizeof(k::AlignOut) + k::ALIGN_DTW_THREADS * sizeof(int32_t));
+        d.dtw_host = h;
+    }
+    return true;
+}
+
+bool dtw_layer(whisper_context & ctx, int il, int n, int Tc) {
+    DeviceState & d = ctx.state->dev; const HParams & hp = ctx.model.hp;
+    const std::vector<int32_t> & pr = ctx.state->dtw_pairs_call;
+    k::AlignHeads hs{}; int pair0 = -1;
+    for (size_t i = 0; i + 1 < pr.size(); i += 2) {
+        if (pr[i] != il) continue;
+        if (pair0 < 0) pair0 = (int) (i / 2);
+        if (hs.n >= k::ALIGN_MAX_HEADS) return false;
+        hs.head[hs.n++] = pr[i + 1];
+    }
+    if (hs.n == 0) return true;
+    if (d.dtw_M < 1 || d.dtw_M > Tc) return false;
+    return k::align_layer(d.dtw, d.dq, n, hp.n_text_state, d.kvc_k + (size_t) il * Tc * hp.n_text_state, d.dtw_M, hs, pair0, d.dtw_n_sot, d.stream);
+}
+
+bool dtw_window(whisper_context & ctx, const std::vector<int32_t> & x, int n_sot, int M) {
+    State & st = *ctx.state; DeviceState & d = st.dev; const HParams & hp = ctx.model.hp;
+    const int64_t t0 = time_us();
+    const int n = (int) x.size(), R = n - n_sot - 1, n_pairs = (int) st.dtw_pairs_call.size() / 2;
+    if (n_pairs < 1 || n > hp.n_text_ctx || !k::align_shape_ok(n, n_sot, M, hp.n_text_state, hp.n_text_head)) {
+        WMI_ERR("%s: the alignment does not cover this window (n = %d, M = %d, n_text_state = %d, n_text_head = %d)\n", __func__, n, M, hp.n_text_state, hp.n_text_head);
+        return false;
+    }
+    int nh_max = 0;
+    for (size_t i = 0, run = 0; i + 1 < st.dtw_pairs_call.size(); i += 2) {
+        run = (i > 0 && st.dtw_pairs_call[i] == st.dtw_pairs_call[i - 2]) ? run + 1 : 1;
+        nh_max = std::max(nh_max, (int) run);
+    }
+    if (!dtw_ensure(d, nh_max, n, R, M, n_pairs)) return false;
+    kv_clear(st.kv_self);
+    st.batch.prep_legacy(x.data(), n, 0, 0);
+    st.batch.logits[n - 1] = 0;
+    d.dtw_collect = true; d.dtw_n_sot = n_sot; d.dtw_M = M;
+    const bool ok = decode(ctx, st.batch);
+    d.dtw_collect = false;
+    if (!ok) return false;
+    k::AlignOut * out = (k::AlignOut *) d.dtw_host;
+    int32_t * jumps = (int32_t *) (out + 1);
+    d.dtw_seq = d.dtw_seq >= 0x7fffffff ? 1 : d.dtw_seq + 1;
+    if (!k::align_finish(d.dtw, R, M, n_pairs, d.stream) ||
+        !k::align_dtw(d.dtw.cost, R, M, d.dtw.trace, nullptr, jumps, out, d.dtw_seq, d.stream)) return false;
+    HIP_TRY(hipStreamSynchronize(d.stream));                 // the window's one wait
+    if (!HIP_OK(hipGetLastError())) return false;
+    if (((volatile k::AlignOut *) out)->tag != d.dtw_seq) { WMI_ERR("%s: the path's record did not arrive\n", __func__); return false; }
+    st.dtw_jumps.assign(jumps, jumps + R);
+    st.dtw_last.n = n; st.dtw_last.n_sot = n_sot; st.dtw_last.R = R; st.dtw_last.M = M; st.dtw_last.n_pairs = n_pairs;
+    st.t_dtw_us += time_us() - t0; st.n_dtw++;
     return true;
 }
 

@@ -201,9 +201,11 @@ bool decode_layers_q(whisper_context & ctx, int n, int n_kv, int kv_head, int Tc
         if (rows_fit(n, S)) {                     // the out projection combines the key-slice partials in its prologue (one launch fewer)
             const float * po = nullptr, * pl = nullptr, * pm = nullptr; int ns = 0;
             // the cross query inside the attention launch (one launch fewer again), else as its own launch
-            if (!k::qattn_cross_qsplit_partials(d.dx, l.ln2_g, l.ln2_b, hp.eps, l.q_cq, l.b_cq, kq_scale, n, S, H, d.kvc_k + (size_t) il * Tc * S,
+            // (an alignment pass needs the layer's query in d.dq: the two-launch form, the same bits — kernels.h)
+            if (d.dtw_active || !k::qattn_cross_qsplit_partials(d.dx, l.ln2_g, l.ln2_b, hp.eps, l.q_cq, l.b_cq, kq_scale, n, S, H, d.kvc_k + (size_t) il * Tc * S,
                                                 d.kvc_v + (size_t) il * Tc * S, Tc, d.xattn, &po, &pl, &pm, &ns, s, 0, pfW ? *pfW : k::QMat{}, pfN, pfK)) {
                 proj(k::EPI_Q_SCALED, ln2, S, S, l.q_cq, l.b_cq, d.dq, S, nullptr, nullptr, 0, nullptr, 0, kq_scale);
+                if (d.dtw_active && !dtw_layer(ctx, il, n, Tc)) return false;
                 k::attn_cross_split_partials(d.dq, n, S, H, d.kvc_k + (size_t) il * Tc * S, d.kvc_v + (size_t) il * Tc * S, Tc, d.xattn, &po, &pl, &pm, &ns, s);
             }
             k::GemvArgs g{};
@@ -213,6 +215,7 @@ bool decode_layers_q(whisper_context & ctx, int n, int n_kv, int kv_head, int Tc
             k::qrows(g, nullptr, l.q_co, s);
         } else {
         proj(k::EPI_Q_SCALED, ln2, S, S, l.q_cq, l.b_cq, d.dq, S, nullptr, nullptr, 0, nullptr, 0, kq_scale);
+        if (d.dtw_active && !dtw_layer(ctx, il, n, Tc)) return false;
         k::attn_cross_split(d.dq, n, S, H, d.kvc_k + (size_t) il * Tc * S, d.kvc_v + (size_t) il * Tc * S, Tc, d.xattn, nullptr, s, 0, d.datt32);
         proj(k::EPI_F32_BIAS_RESID, att, S, S, l.q_co, l.b_co, d.dx, S, d.dx, nullptr, 0, nullptr, 0, 0.f);
         }
@@ -231,6 +234,7 @@ bool decode_layers_q(whisper_context & ctx, int n, int n_kv, int kv_head, int Tc
         return true;
     }
     // final LN + logits for the flagged rows
+    if (d.dtw_active) return true;                          // (an alignment pass: no row asked, and the host's image is left alone)
     st.logits.resize((size_t) n * NV);
     for (size_t r0 = 0; r0 < rows.size(); r0 += 8) {
         const int nr = (int) std::min<size_t>(8, rows.size() - r0);

@@ -43,6 +43,7 @@ void emit_segment(whisper_context & ctx, State & st, const whisper_full_params &
     }
     Segment seg{tt0, tt1, text, {}, speaker_turn_next};
     seg.tokens.assign(toks.begin() + i0, toks.begin() + i1_excl);
+    seg.i_tok0 = i0;
     st.result_all.push_back(std::move(seg));
     int n_new = 1;
     if (params.token_timestamps) {
@@ -56,6 +57,8 @@ void emit_segment(whisper_context & ctx, State & st, const whisper_full_params &
 
 } // namespace
 
+bool align_window(whisper_context & ctx, State & st, int seek, int seek_end, const std::vector<int32_t> & prompt_init, const Decoder & best, int32_t seg0);
+
 int full(whisper_context & ctx, whisper_full_params params, const float * samples, const float * d_samples, int n_samples) {
     BusyScope busy(ctx.device);                                      // (see wmi.h: kernels that wait inside a launch are used by a lone transcription only)
     State & st = *ctx.state;
@@ -67,6 +70,10 @@ int full(whisper_context & ctx, whisper_full_params params, const float * sample
     // the no-speech mode of this call (wmi_set_no_speech; 0: nothing below launches or stores anything)
     const int nsm = ctx.no_speech_mode;
     st.windows.clear();
+    // token alignment (wmi_set_token_dtw; 0: nothing below launches or stores anything): the mode and the pairs of this call
+    const bool dtw = ctx.token_dtw_mode != 0 && ctx.model.n_loaded > 0;
+    if (dtw) st.dtw_pairs_call = ctx.dtw_pairs.empty() ? dtw_default_pairs(hp) : ctx.dtw_pairs;
+    st.dtw_last = State::DtwDims{}; st.dtw_jumps.clear();
     // the envelope kernel reads the caller's samples on a side stream: never return while it is in flight
     struct EnvelopeGuard { State & st; ~EnvelopeGuard() { (void) signal_energy_wait(st); } } envelope_guard{st};
     static const bool defer_phases = getenv("WMI_PHASE_SYNC") == nullptr;
@@ -483,10 +490,43 @@ int full(whisper_context & ctx, whisper_full_params params, const float * sample
             emit_window(ctx, st, params, seek, prompt, prompt_init.size(), best);
             if (st.ts_failed) { WMI_ERR("%s: failed to refine the token timestamps on the device\n", __func__); return -9; }
             if (nsm != 0) st.windows.push_back(WindowRec{ seek, p_win, WINDOW_EMITTED, seg0, (int32_t) st.result_all.size() - seg0 });
+            if (dtw && (int32_t) st.result_all.size() > seg0 && !align_window(ctx, st, seek, seek_end, prompt_init, best, seg0)) {
+                WMI_ERR("%s: failed to align the window's tokens\n", __func__);
+                return -7;
+            }
             seek += best.seek_delta;
         }
     }
     return 0;
+}
+
+// Token times by DTW for the window whose segments start at seg0: x = [start tokens, text tokens, eot] teacher-forced over
+// the window's first M key frames; text token r gets seek + 2 jump[r].  A window without a text token is left unaligned.
+bool align_window(whisper_context & ctx, State & st, int seek, int seek_end, const std::vector<int32_t> & prompt_init, const Decoder & best, int32_t seg0) {
+    const Vocab & v = ctx.model.vocab; const HParams & hp = ctx.model.hp;
+    const auto & toks = best.sequence.tokens;
+    std::vector<int32_t> x;
+    x.push_back(v.sot);
+    if (v.is_multilingual()) { x.push_back(prompt_init[1]); x.push_back(prompt_init[2]); }
+    const int n_sot = (int) x.size();
+    x.push_back(v.not_);
+    std::vector<int> rank(toks.size(), -1);                   // result token -> its row among the text tokens
+    int n_text = 0;
+    for (size_t i = 0; i < toks.size(); ++i) if (toks[i].id < v.eot) { rank[i] = n_text++; x.push_back(toks[i].id); }
+    x.push_back(v.eot);
+    if (n_text == 0) return true;
+    const int Tc = st.enc_n_ctx > 0 ? st.enc_n_ctx : (st.exp_n_audio_ctx > 0 ? st.exp_n_audio_ctx : hp.n_audio_ctx);
+    const int M = std::max(1, std::min(Tc, std::min(std::min(3000, seek_end - seek), best.seek_delta) / 2));
+    if (!dtw_window(ctx, x, n_sot, M)) return false;
+    for (size_t s = (size_t) seg0; s < st.result_all.size(); ++s) {
+        Segment & seg = st.result_all[s];
+        seg.t_dtw.assign(seg.tokens.size(), -1);
+        for (size_t j = 0; j < seg.tokens.size(); ++j) {
+            const size_t i = (size_t) seg.i_tok0 + j;
+            if (i < rank.size() && rank[i] >= 0 && rank[i] < (int) st.dtw_jumps.size()) seg.t_dtw[j] = seek + 2 * (int64_t) st.dtw_jumps[rank[i]];
+        }
+    }
+    return true;
 }
 
 void emit_window(whisper_context & ctx, State & st, const whisper_full_params & params, int seek, const std::vector<int32_t> & prompt,
@@ -878,6 +918,8 @@ int wrap_segment(whisper_context & ctx, State & st, int max_len, bool split_on_w
             last.text = std::move(text); last.t1 = tok.t0; last.tokens.resize(i); last.speaker_turn_next = false;
             Segment next{tok.t0, seg.t1, std::string(), {}, seg.speaker_turn_next};
             next.tokens.assign(seg.tokens.begin() + i, seg.tokens.end());
+            next.i_tok0 = seg.i_tok0 + i;                      // (and a segment's DTW times move with its tokens)
+            if (!seg.t_dtw.empty()) { next.t_dtw.assign(seg.t_dtw.begin() + i, seg.t_dtw.end()); last.t_dtw.resize(i); }
             st.result_all.push_back(std::move(next));
             acc = 0; text.clear();
             seg = st.result_all.back();

@@ -320,6 +320,39 @@ int no_speech_rule(int mode, float p, float thold, bool failed, double avg_logpr
     return poor ? NSP_FALLBACK : NSP_EMIT;
 }
 
+// ------------------------------------------------------------------ DTW path (OpenAI's timing.py: dtw_cpu + backtrace)
+void dtw_path_host(int R, int M, const float * A, int32_t * jumps, int32_t * path, int * n_path) {
+    const size_t W = (size_t) M + 1;
+    std::vector<float> D((size_t) (R + 1) * W, INFINITY);
+    std::vector<uint8_t> tr((size_t) (R + 1) * W, 0);
+    D[0] = 0.0f;
+    for (int j = 1; j <= M; ++j)
+        for (int i = 1; i <= R; ++i) {
+            const float c0 = D[(size_t) (i - 1) * W + j - 1], c1 = D[(size_t) (i - 1) * W + j], c2 = D[(size_t) i * W + j - 1];
+            float c; uint8_t t;
+            if (c0 < c1 && c0 < c2) { c = c0; t = 0; } else if (c1 < c0 && c1 < c2) { c = c1; t = 1; } else { c = c2; t = 2; }
+            D[(size_t) i * W + j] = -A[(size_t) (i - 1) * M + j - 1] + c;
+            tr[(size_t) i * W + j] = t;
+        }
+    for (int j = 0; j <= M; ++j) tr[j] = 2;
+    for (int i = 0; i <= R; ++i) tr[(size_t) i * W] = 1;
+    std::vector<int32_t> rev;
+    int i = R, j = M;
+    while (i > 0 || j > 0) {
+        rev.push_back(i - 1); rev.push_back(j - 1);
+        const uint8_t t = tr[(size_t) i * W + j];
+        if (t == 0) { --i; --j; } else if (t == 1) --i; else --j;
+    }
+    const int np = (int) rev.size() / 2;
+    for (int r = 0; jumps && r < R; ++r) jumps[r] = -1;
+    for (int k = 0; k < np; ++k) {                         // from the first point on
+        const int32_t r = rev[2 * (size_t) (np - 1 - k)], t = rev[2 * (size_t) (np - 1 - k) + 1];
+        if (path) { path[2 * (size_t) k] = r; path[2 * (size_t) k + 1] = t; }
+        if (jumps && r >= 0 && r < R && jumps[r] < 0) jumps[r] = t;
+    }
+    if (n_path) *n_path = np;
+}
+
 // ------------------------------------------------------------------ language detection (W/whisper.cpp:3569-3650)
 int lang_auto_detect(whisper_context & ctx, int offset_ms, float * lang_probs) {
     State & st = *ctx.state;

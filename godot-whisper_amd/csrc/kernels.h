@@ -411,6 +411,33 @@ bool no_speech_logits(const float * logits, int ld, const NoSpeechRows & rows, i
 bool no_speech_head(const float * x, int rows, int S, const float * ln_g, const float * ln_b, float eps, const __half * te, int n_vocab, int nosp,
                     void * scratch, NoSpeechOut * out, int32_t tag, hipStream_t st);
 
+// Token alignment (k_align.hip): DTW over the cross-attention of chosen (layer, head) pairs.  For a pass of n rows over
+// M key frames and a pair (l, h): s[i][t] = sum_{c < 64} q_l[i][64 h + c] k_l[t][64 h + c] (f16 operands as stored — both carry
+// d^-1/4 —, f32 sum), w = soft-max over exactly the first M keys, z = (w - mean) / sigma per (pair, t) over all n rows (population
+// sigma; sigma == 0 gives 0), a median of 7 along t with reflect padding (none for M <= 3), A[r][t] = mean over the pairs of
+// z[n_sot + r][t], r < R = n - n_sot - 1, the pairs added in ascending (layer, head) order and divided by their count once.
+//   align_layer:  the layer's heads (ascending) into A — scores + soft-max into w [heads][n][M], column statistics, normalise + median +
+//                 accumulate; pair0 = the pairs of earlier layers (0: A starts from zero).  q [n][S], kc [>= M][S], S = 64 H.  The query
+//                 rows used go to b.q [pairs][n][64] when it is not null.
+//   align_finish: A /= pairs, and -A diagonal-major into b.cost: element (r, t) at [r + t][r]
+//   align_dtw:    D[0][0] = 0, the other border cells +inf; D[i][j] = c[i-1][j-1] + min(D[i-1][j-1], D[i-1][j], D[i][j-1]) in f32 with
+//                 OpenAI's tie rule (diagonal only if strictly below both, then up only if strictly below both, else left); one workgroup,
+//                 a thread per row, anti-diagonals; thread 0 walks the step bytes back from (R, M).  jumps[r] = first frame of row r and
+//                 out = {path length, tag} are stored with plain vector stores, usually into pinned host memory; path (device, may be null)
+//                 takes the (row, frame) points, the LAST point at [R + M - 1], the first at [R + M - n_path].
+// Workgroups are independent inside every launch; no atomics.
+constexpr int ALIGN_HEAD_DIM = 64, ALIGN_MAX_HEADS = 32, ALIGN_MAX_M = 1500, ALIGN_DTW_THREADS = 512, ALIGN_MAX_R = ALIGN_DTW_THREADS - 1;
+struct AlignHeads { int n; int head[ALIGN_MAX_HEADS]; };
+struct AlignOut { int32_t n_path; int32_t tag; };
+struct AlignBufs { float * w, * mu, * sigma, * A, * cost; uint8_t * trace; __half * q; };
+size_t align_w_floats(int nh, int n, int M);                    // w; mu and sigma hold nh * M each, A R * M, trace R * M bytes
+size_t align_cost_floats(int R, int M);
+bool align_shape_ok(int n, int n_sot, int M, int S, int H);
+bool align_layer(const AlignBufs & b, const __half * q, int n, int S, const __half * kc, int M, const AlignHeads & hs, int pair0, int n_sot, hipStream_t st);
+bool align_finish(const AlignBufs & b, int R, int M, int n_pairs, hipStream_t st);
+bool align_dtw(const float * cost, int R, int M, uint8_t * trace, int32_t * path, int32_t * jumps, AlignOut * out, int32_t tag, hipStream_t st);
+void align_cost_from_matrix(const float * A, int R, int M, float * cost, hipStream_t st);      // -A diagonal-major (the path hook)
+
 // One decoder MLP of the one-row step as ONE launch: x += W2 . gelu(W1 . LN(x) + b1) + b2 (k_mlp_pair, k_dec.hip).  The hidden row goes
 // from the workgroups that produce it to every workgroup of the same launch through data-tagged 8-byte granules ({two f16, tag}, written
 // and read past the caches): no launch boundary between the two projections.  `hand` holds 2 S granules (16 S bytes, zeroed once),

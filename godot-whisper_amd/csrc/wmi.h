@@ -175,7 +175,12 @@ struct Decoder {
     std::vector<float> probs, logits, logprobs;
     std::mt19937 rng{0};
 };
-struct Segment { int64_t t0, t1; std::string text; std::vector<whisper_token_data> tokens; bool speaker_turn_next; };
+struct Segment {
+    int64_t t0, t1; std::string text; std::vector<whisper_token_data> tokens; bool speaker_turn_next;
+    // wmi_set_token_dtw: per token its DTW time in 10 ms units, -1 for a token that is no text (empty: the window was not aligned);
+    // i_tok0 = the index of tokens[0] among the window's result tokens (what full() maps the path's rows by)
+    std::vector<int64_t> t_dtw; int32_t i_tok0 = 0;
+};
 
 struct Mel { int n_len = 0, n_len_org = 0, n_mel = 0; };
 // one 30 s window of a transcription call made with a no-speech mode (wmi_set_no_speech): what wmi_full_get_window reports
@@ -257,6 +262,13 @@ struct DeviceState {
     // records of up to k::NSP_MAX_ROWS rows, the tag of the last launch; nsp_row >= 0 asks the next decode() for the head on that batch row
     void  * nsp_scratch = nullptr; float * nsp_logits = nullptr; void * nsp_host = nullptr; int32_t nsp_seq = 0; int nsp_row = -1;
     int     step_seen_T = -1;                                          // encoder length of recent steps (StepGraph::seen counts them)
+    // token alignment (device.cpp: dtw_*; kernels.h: align_*), all made on first use: the layer's weights and column statistics, A, the
+    // diagonal-major cost, the step bytes, the query rows used, and a pinned block {AlignOut, jumps[ALIGN_DTW_THREADS]}.
+    // dtw_collect asks the next decode() to be the alignment pass of a window (n_sot rows of start tokens, M key frames): the hook
+    // behind every layer's cross query, no logits, no reference timers; dtw_active is that request while decode() runs
+    k::AlignBufs dtw{}; size_t dtw_cap[7] = {}; void * dtw_host = nullptr; int32_t dtw_seq = 0;
+    bool dtw_collect = false, dtw_active = false; int dtw_n_sot = 0, dtw_M = 0;
+    int dec_n = 0;                                                     // rows of the last decode() batch (wmi_get_tensor "dec_cross_q")
 };
 
 struct State {
@@ -274,6 +286,10 @@ struct State {
     std::vector<float> logits;                    // [n_tokens][n_vocab] host copy (flagged rows only)
     std::vector<Segment> result_all;
     std::vector<WindowRec> windows;               // its windows (empty in mode 0)
+    // the last window aligned on this state (wmi_token_dtw_dims; the tensors stay in dev.dtw until the next one), the alignment's own timer
+    struct DtwDims { int n = 0, n_sot = 0, R = 0, M = 0, n_pairs = 0; } dtw_last; std::vector<int32_t> dtw_jumps;
+    int64_t t_dtw_us = 0; int32_t n_dtw = 0;
+    std::vector<int32_t> dtw_pairs_call;          // the pairs of the transcription call in progress (full() copies the context's at its start)
     std::vector<int32_t> prompt_past;
     int     lang_id = 0;
     std::vector<float> lang_probs;                // the language probabilities of the last full() that detected its language (empty: it did not)
@@ -374,6 +390,8 @@ struct whisper_context {
     bool           weights_pending = false;
     wmi::BatchWork * batch = nullptr;   // lazily created by wmi_full_batch
     int            no_speech_mode = 0;  // wmi_set_no_speech: 0 off, 1 report, 2 drop, 3 gate; read at the start of every transcription call
+    // wmi_set_token_dtw: 0 off, 1 on; the (layer, head) pairs in effect, ascending, flattened {l, h, l, h, ..}; read at the start of every transcription call
+    int            token_dtw_mode = 0; std::vector<int32_t> dtw_pairs;
     // streams with a hardware queue of their own, made together with the context's first stream and handed to replica contexts later
     // (init_state: it is the ORDER in which the queues are created that decides whether the replicas run beside each other)
     std::vector<hipStream_t> spare_streams;
@@ -478,6 +496,15 @@ bool no_speech_read(State & st, float * p);
 // best decoder's.  0 emit, 1 fall back to the next temperature (where there is one), 2 drop, 3 gate.
 enum { NSP_EMIT = 0, NSP_FALLBACK = 1, NSP_DROP = 2, NSP_GATE = 3 };
 int  no_speech_rule(int mode, float p, float thold, bool failed, double avg_logprob, float logprob_thold);
+// Token alignment (kernels.h: align_*).  dtw_default_pairs: every head of the upper half of the text layers.
+// dtw_layer is decode()'s hook behind layer il's cross query (d.dq holds it); dtw_window runs the pass for the window full() has just
+// emitted (x = start tokens + text + eot, M key frames), waits once and leaves jumps [R] in st.dtw_jumps; false on a device error.
+// dtw_path_host is the sequential restatement of the path: the definition (jumps [R], path [(R + M)][2] from the first point on).
+std::vector<int32_t> dtw_default_pairs(const HParams & hp);
+bool dtw_ensure(DeviceState & d, int nh, int n, int R, int M, int n_pairs);
+bool dtw_layer(whisper_context & ctx, int il, int n, int Tc);
+bool dtw_window(whisper_context & ctx, const std::vector<int32_t> & x, int n_sot, int M);
+void dtw_path_host(int R, int M, const float * A, int32_t * jumps, int32_t * path, int * n_path);
 // k draws per row from the filtered distribution of logits row `rows[r]` of the last decode() (keep_logits_on_device), r < n_rows <= 8;
 // u [n_rows][k] uniform numbers in [0, 1) from the decoders' generators.  out [n_rows][k].
 bool sample_rows_device(whisper_context & ctx, const StepFilter * f, const int * rows, int n_rows, float temperature, int k,

@@ -37,12 +37,16 @@ def _fptr(a: np.ndarray):
 class SpeechToText:
     """One `whisper_context` per node (src/speech_to_text.h:135); not re-entrant."""
 
-    def __init__(self, lib: C.CDLL, settings: dict | None = None, no_speech: int = 0):
-        """no_speech (product library only, include/wmi_device.h wmi_set_no_speech): 0 off — the reference's behaviour —, 1 report the
+    def __init__(self, lib: C.CDLL, settings: dict | None = None, no_speech: int = 0, token_dtw=False):
+        """token_dtw (product library only, include/wmi_device.h wmi_set_token_dtw): True — DTW token times over the default alignment
+        heads — or a list of (layer, head) pairs; every token dictionary then gains "t_dtw" (10 ms units, -1 for a token that is no text).
+        "t0" / "t1" stay the reference's.
+        no_speech (product library only, include/wmi_device.h wmi_set_no_speech): 0 off — the reference's behaviour —, 1 report the
         windows' no-speech probability, 2 drop (OpenAI's rule), 3 gate.  The windows of a call are in last_windows after collect()."""
         self.lib = lib
         self.ctx = None
         self.no_speech = int(no_speech)
+        self.token_dtw = token_dtw
         self.last_windows = []
         self.language = "en"  # Language enum -> code, src/speech_to_text.cpp:117-324
         self.settings = dict(SETTINGS)
@@ -61,6 +65,17 @@ class SpeechToText:
         self.ctx = self.lib.whisper_init_from_buffer_with_params(C.cast(buf, C.c_void_p), len(model_bytes), cp)
         del buf  # the loader only borrows the buffer during the call (W/whisper.cpp:3231-3240)
         self.set_no_speech(self.no_speech)
+        self.set_token_dtw(self.token_dtw)
+
+    def set_token_dtw(self, token_dtw) -> int:
+        """The context's alignment mode from the next transcription call on (False, True or (layer, head) pairs); returns the previous
+        mode, -1 for pairs the model does not have (nothing changed), 0 without a context."""
+        self.token_dtw = token_dtw
+        if not self.ctx or not (token_dtw or hasattr(self.lib, "wmi_set_token_dtw")):
+            return 0
+        pairs = [] if isinstance(token_dtw, bool) or not token_dtw else [int(v) for lh in token_dtw for v in lh]
+        arr = (C.c_int32 * max(1, len(pairs)))(*pairs)
+        return self.lib.wmi_set_token_dtw(self.ctx, 1 if token_dtw else 0, arr if pairs else None, len(pairs) // 2)
 
     def set_no_speech(self, mode: int) -> int:
         """The context's no-speech mode from the next transcription call on; returns the previous one (0 without a context)."""
@@ -121,6 +136,8 @@ class SpeechToText:
                     "text": lib.whisper_full_get_token_text(ctx, i, j), "id": t.id, "p": t.p, "plog": t.plog,
                     "pt": t.pt, "ptsum": t.ptsum, "t0": t.t0, "t1": t.t1, "tid": t.tid, "vlen": t.vlen,
                 })
+                if self.token_dtw:
+                    out[-1]["t_dtw"] = lib.wmi_full_get_token_dtw(ctx, i, j)
         out.insert(0, full_text)
         self.last_windows = self.windows()
         return out

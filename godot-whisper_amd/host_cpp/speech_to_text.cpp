@@ -29,6 +29,13 @@ void SpeechToText::set_language_model(const uint8_t * data, size_t size) {   // 
     const whisper_context_params context_params{ settings.use_gpu };
     context_instance = whisper_init_from_buffer_with_params((void *) data, size, context_params);
     if (context_instance && no_speech != 0) (void) wmi_set_no_speech(context_instance, no_speech);
+    if (context_instance && token_dtw) (void) wmi_set_token_dtw(context_instance, 1, token_dtw_pairs.data(), (int) token_dtw_pairs.size() / 2);
+}
+
+int SpeechToText::set_token_dtw(bool on, const std::vector<int32_t> & layer_head) {
+    token_dtw = on; token_dtw_pairs = layer_head;
+    if (!context_instance) return 0;
+    return wmi_set_token_dtw(context_instance, on ? 1 : 0, token_dtw_pairs.data(), (int) token_dtw_pairs.size() / 2);
 }
 
 int SpeechToText::set_no_speech(int mode) {
@@ -95,6 +102,7 @@ Transcription SpeechToText::collect() const {                            // src/
             t.id = token.id; t.p = token.p; t.plog = token.plog; t.pt = token.pt; t.ptsum = token.ptsum;
             t.t0 = token.t0; t.t1 = token.t1; t.tid = token.tid; t.vlen = token.vlen;
             t.no_speech_prob = no_speech_prob;
+            t.t_dtw = wmi_full_get_token_dtw(context_instance, i, j);
             out.tokens.push_back(std::move(t));
         }
     }

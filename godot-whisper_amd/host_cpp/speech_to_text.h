@@ -34,6 +34,7 @@ struct Token {
     float   p = 0, plog = 0, pt = 0, ptsum = 0, vlen = 0;
     int64_t t0 = 0, t1 = 0;
     float   no_speech_prob = -1.0f;   // not in the reference: of the token's segment (wmi_full_get_segment_no_speech_prob; -1 with set_no_speech(0))
+    int64_t t_dtw = -1;               // not in the reference: the token's DTW time in 10 ms units (wmi_full_get_token_dtw; -1 without set_token_dtw, or for a token that is no text)
 };
 // the Array itself: element 0 is the full text, the rest are the token dictionaries (:447)
 struct Transcription {
@@ -60,6 +61,10 @@ public:
     // across set_language_model.  Returns the previous mode.
     int  set_no_speech(int mode);
     int  get_no_speech() const { return no_speech; }
+    // not in the reference: DTW token times (include/wmi_device.h wmi_set_token_dtw) over the default alignment heads, or over the
+    // given {layer, head, layer, head, ..} list; kept across set_language_model.  Returns what wmi_set_token_dtw does (0 without a context).
+    int  set_token_dtw(bool on, const std::vector<int32_t> & layer_head = {});
+    bool get_token_dtw() const { return token_dtw; }
 
     // src/speech_to_text.h:151-156, :162 — resample(PackedVector2Array buffer, InterpolatorType): stereo capture frames at the mix rate
     // -> mono 16 kHz.  The reference folds on the CPU and calls libsamplerate's src_simple; here both steps run on the device
@@ -87,6 +92,7 @@ protected:
     TranscribeSettings settings;
     int language = English;
     int no_speech = 0;
+    bool token_dtw = false; std::vector<int32_t> token_dtw_pairs;
     whisper_context * context_instance = nullptr;
 };
 

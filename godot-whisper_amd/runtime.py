@@ -117,6 +117,14 @@ DEVICE_API = [
     ("wmi_selftest_no_speech_rule", C.c_int, [C.c_int, C.c_float, C.c_float, C.c_int, C.c_double, C.c_float]),
     ("wmi_selftest_no_speech", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                          C.c_void_p, C.c_void_p]),
+    ("wmi_set_token_dtw", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_int]),
+    ("wmi_token_dtw_heads", C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int]),
+    ("wmi_full_get_token_dtw", C.c_int64, [C.c_void_p, C.c_int, C.c_int]),
+    ("wmi_full_get_token_dtw_from_state", C.c_int64, [C.c_void_p, C.c_int, C.c_int]),
+    ("wmi_token_dtw_dims", C.c_int, [C.c_void_p] + [C.POINTER(C.c_int)] * 5),
+    ("wmi_get_token_dtw_timings", None, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
+    ("wmi_selftest_dtw_matrix", C.c_int, [C.c_int] * 8 + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    ("wmi_selftest_dtw_path", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
 ]
 
 _lib = None

@@ -293,6 +293,8 @@ WHISPER_API int wmi_set_audio_ctx(struct whisper_context * ctx, int n_audio_ctx)
  *   "cross_v"    [n_text_layer][n_ctx][n_state] cross-attention values (reference holds [state][ctx])
  *   "self_k" / "self_v"  [n_text_layer][3*n_text_ctx][n_state]
  *   "enc_x"      [n_ctx][n_state]               residual stream after the last encoder block
+ *   "dec_cross_q" [rows][n_state]               the last text layer's scaled cross query of the last whisper_decode / prompt batch (f16)
+ *   "dtw_matrix" / "dtw_q" / "dtw_jumps"        the last aligned window (wmi_set_token_dtw below)
  */
 WHISPER_API int wmi_get_tensor(struct whisper_context * ctx, const char * name, float * dst, int n);
 WHISPER_API int wmi_mel_dims(struct whisper_context * ctx, int * n_len, int * n_len_org, int * n_mel);
@@ -553,6 +555,46 @@ WHISPER_API int   wmi_selftest_no_speech_rule(int mode, float p, float thold, in
  * p_out [rows].  Returns 0; -1 bad argument, before the device is touched; -2 / -3 device errors. */
 WHISPER_API int   wmi_selftest_no_speech(int device, int form, int rows, int n_vocab, int nosp, const float * logits, const uint16_t * W,
                                          const float * x, int K, float * logits_out, float * p_out);
+
+/* Token times by dynamic time warping over the cross-attention of alignment heads (OpenAI's word_timestamps, whisper.cpp's t_dtw).
+ * For every window that emitted segments and has a text token: x = [sot, (language, task), notimestamps, text tokens .., eot] — the best
+ * decoder's result tokens with id < eot, no timestamp tokens, no [prev ..] context — is decoded once more, teacher-forced, as one batch on a
+ * cleared self cache.  n = len(x), n_sot = 1 or 3, R = n - n_sot - 1 rows enter the path (the rows that PREDICT text_0 .. text_{N-1}, eot),
+ * M = clamp(min(3000, seek_end - seek, seek_delta) / 2, 1, audio_ctx in effect) key frames.  Per (layer, head) pair the cross-attention
+ * weights w = soft-max over exactly the first M keys of q . k (f16 operands as stored, f32 sums) are normalised per key frame over all n
+ * rows (population sigma; sigma == 0 gives 0), median-filtered along time (width 7, reflect padding; none for M <= 3) and averaged over
+ * the pairs in ascending (layer, head) order: A [R][M].  The path is the DTW of -A in f32 with OpenAI's tie rule (csrc/k_align.hip,
+ * DESIGN.md section 5); text token r gets t_dtw = seek + 2 * (first frame of row r), in 10 ms units.
+ *   wmi_set_token_dtw   mode 0 off (default: every result, counter and launch as without this interface), 1 on; layer_head = n_pairs
+ *                       {layer, head} pairs, n_pairs = 0: every head of the upper half of the text layers (OpenAI's default mask).  Per-model
+ *                       presets are not shipped.  Read at the START of every transcription call.  Returns the previous mode; -2 NULL context;
+ *                       -1, nothing changed: a layer or head out of range, a duplicate pair, a NULL list with n_pairs > 0.  Needs the
+ *                       hyper-parameters only: works on a host-only context.
+ *   wmi_token_dtw_heads the pairs in effect (the default resolved), ascending, up to cap pairs into layer_head; returns their count
+ *   wmi_full_get_token_dtw   t_dtw of token i_token of segment i_segment; -1 in mode 0, for a token that is no text, a bad index, or a
+ *                       window that was not aligned.  Follows wmi_batch_select / wmi_pool_select like the other accessors.  t0 / t1 of
+ *                       whisper_token_data stay the reference's.
+ *   wmi_token_dtw_dims  the last window aligned on the context's state; returns 0, -1 when there is none
+ *   wmi_get_tensor      "dtw_matrix" A [R][M], "dtw_q" [n_pairs][n][64] the query rows the pass used, "dtw_jumps" [R], of that window
+ *   wmi_get_token_dtw_timings   the alignment's own timer (pass + matrix + path + the window's one wait; not part of wmi_get_timings)
+ * While the mode is on, the chunks of wmi_full_batch* / wmi_capture_full_batch / wmi_pool_full take the general driver (chunk mode 1), and
+ * the self cache after a call holds the alignment pass's rows, not the last decoding step's. */
+WHISPER_API int     wmi_set_token_dtw(struct whisper_context * ctx, int mode, const int32_t * layer_head, int n_pairs);
+WHISPER_API int     wmi_token_dtw_heads(struct whisper_context * ctx, int32_t * layer_head, int cap);
+WHISPER_API int64_t wmi_full_get_token_dtw(struct whisper_context * ctx, int i_segment, int i_token);
+WHISPER_API int64_t wmi_full_get_token_dtw_from_state(struct whisper_state * state, int i_segment, int i_token);
+WHISPER_API int     wmi_token_dtw_dims(struct whisper_context * ctx, int * n, int * n_sot, int * R, int * M, int * n_pairs);
+WHISPER_API void    wmi_get_token_dtw_timings(struct whisper_context * ctx, int64_t * us, int32_t * n_windows);
+/* The alignment kernels on caller data (no context; all host pointers; f16 as bit patterns), in the product's layouts.
+ *   wmi_selftest_dtw_matrix  q [L][n][S], k [L][T][S] (only the first M keys of a layer may be read), layer_head n_pairs pairs in ascending
+ *                       order without duplicates, layers < L, heads < H; S = 64 H, H <= 32, 1 <= M <= T <= 1500, R = n - n_sot - 1 in
+ *                       1 .. 511.  A_out [R][M].
+ *   wmi_selftest_dtw_path    A [R][M] -> jumps [R], path [(R + M)][2] {row, frame} from the first point on, *n_path points.  device = -1: the
+ *                       sequential host restatement (the definition; no GPU needed, any R >= 1); device >= 0: the kernel (R <= 511).
+ * Return 0; -1 bad argument, before the device is touched; -2 / -3 device errors. */
+WHISPER_API int     wmi_selftest_dtw_matrix(int device, int L, int S, int H, int n, int n_sot, int M, int T, const uint16_t * q, const uint16_t * k,
+                                            const int32_t * layer_head, int n_pairs, float * A_out);
+WHISPER_API int     wmi_selftest_dtw_path(int device, int R, int M, const float * A, int32_t * jumps, int32_t * path, int * n_path);
 
 /* Host worker pool self-test (no device needed): `reps` jobs of `n_tasks` tasks; returns reps * n_tasks * (n_tasks + 1) / 2
  * when every task of every job ran exactly once. */
