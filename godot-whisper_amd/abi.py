@@ -191,6 +191,16 @@ class wmi_window(C.Structure):  # include/wmi_device.h: a 30 s window of a call 
                 ("n_segments", C.c_int32)]
 
 
+class wmi_long_params(C.Structure):  # include/wmi_device.h: the plan parameters of wmi_full_long (wmi_long_default_params has the defaults)
+    _fields_ = [("thold", C.c_float), ("floor", C.c_float), ("min_silence_ms", C.c_int32), ("pad_ms", C.c_int32),
+                ("max_gap_ms", C.c_int32), ("max_piece_ms", C.c_int32), ("fit_audio_ctx", C.c_int32)]
+
+
+class wmi_long_piece(C.Structure):  # include/wmi_device.h: one piece of the last wmi_full_long call
+    _fields_ = [("frame0", C.c_int32), ("frame1", C.c_int32), ("audio_ctx", C.c_int32), ("mode", C.c_int32),
+                ("i_segment", C.c_int32), ("n_segments", C.c_int32)]
+
+
 NO_SPEECH_OFF, NO_SPEECH_REPORT, NO_SPEECH_DROP, NO_SPEECH_GATE = range(4)       # wmi_set_no_speech modes
 WINDOW_EMITTED, WINDOW_DROPPED, WINDOW_GATED = range(3)                          # wmi_window.outcome
 TOKEN_DTW_OFF, TOKEN_DTW_ON = range(2)                                           # wmi_set_token_dtw modes

@@ -702,6 +702,7 @@ void free_batch(whisper_context & ctx) {
     if (w.lang_host) (void) hipHostFree(w.lang_host);
     if (w.nsp_scratch) (void) hipFree(w.nsp_scratch);
     if (w.nsp_host) (void) hipHostFree(w.nsp_host);
+    free_long(w);
     for (size_t i = 1; i < w.lanes.size(); ++i) free_lane_state(w.lanes[i]);
     for (whisper_context * r : w.replicas) free_replica(r);
     delete ctx.batch;

@@ -438,6 +438,12 @@ bool align_finish(const AlignBufs & b, int R, int M, int n_pairs, hipStream_t st
 bool align_dtw(const float * cost, int R, int M, uint8_t * trace, int32_t * path, int32_t * jumps, AlignOut * out, int32_t tag, hipStream_t st);
 void align_cost_from_matrix(const float * A, int R, int M, float * cost, hipStream_t st);      // -A diagonal-major (the path hook)
 
+// Frame energies (k_segment.hip): the detector in front of wmi_full_long.  x [n] 16 kHz f32 PCM on the device, e [ceil(n / 160)]:
+//   e[f] = sum over i in [160 f, min(160 f + 160, n)) of | x[i] - x[i - 1] |, x[-1] := 0 — f32 throughout, the sum left to right from 0.0f.
+// A workgroup owns SEG_STAGE_FRAMES frames (its staging extent in LDS); nothing is shared between workgroups.  false: bad argument / launch error.
+constexpr int SEG_FRAME = 160, SEG_STAGE_FRAMES = 64;
+bool frame_energy(const float * x, int n, float * e, hipStream_t st);
+
 // One decoder MLP of the one-row step as ONE launch: x += W2 . gelu(W1 . LN(x) + b1) + b2 (k_mlp_pair, k_dec.hip).  The hidden row goes
 // from the workgroups that produce it to every workgroup of the same launch through data-tagged 8-byte granules ({two f16, tag}, written
 // and read past the caches): no launch boundary between the two projections.  `hand` holds 2 S granules (16 S bytes, zeroed once),

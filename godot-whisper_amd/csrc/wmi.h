@@ -348,6 +348,13 @@ struct BatchWork {
     std::vector<whisper_context *> replicas; int replicas_wanted = -1;      // -1: default (WMI_BATCH_REPLICAS, 3)
     int groups_wanted = 0, groups_last = 1;                  // lock-step groups side by side (0: default = WMI_LOCKSTEP_GROUPS, 2); how many the last call used
     int64_t t_mel_us = 0, t_encode_us = 0, t_decode_us = 0, t_emit_us = 0; int n_steps = 0, n_chained = 0;
+    // wmi_full_long (long.cpp): the one PCM buffer of a host-PCM call and the energies (grow-only; pinned mirror), the plan of the last
+    // call, its merged result (piece i's own is results[i]) and the front's timers {upload, energies, plan}
+    struct Long {
+        float * pcm = nullptr; size_t pcm_cap = 0; float * e = nullptr, * e_host = nullptr; size_t e_cap = 0;
+        std::vector<wmi_long_piece> pieces; std::vector<Segment> merged; std::vector<WindowRec> windows; int lang_id = -1; bool valid = false;
+        int64_t t_us[3] = {0, 0, 0}; int32_t n_frames = 0;
+    } lng;
 };
 
 } // namespace wmi
@@ -558,6 +565,14 @@ int  lockstep_sets(const int * eff_T, int n, bool quantised, bool per_row, int *
 int  full_batch(whisper_context & ctx, whisper_full_params params, const float * const * pcm, const int * n_samples, int n_chunks, bool on_device,
                 const int * audio_ctx = nullptr);       // audio_ctx: an encoder length per chunk (0 = the model's) instead of params.audio_ctx
 void free_batch(whisper_context & ctx);
+// the front of wmi_full_long (segment.cpp, host only): the sequential definition of the frame energies, the parameter check, the frames
+// offset_ms / duration_ms leave, and the plan — pieces in order (frame0, frame1, audio_ctx), their count, -1 on a bad argument
+void frame_energy_host(const float * x, int n, float * e);
+wmi_long_params long_default_params();
+bool long_params_ok(const wmi_long_params & p);
+int  long_window(int n_samples, int offset_ms, int duration_ms, int * f0, int * f1, int * n_sub);
+int  long_plan(const float * e, int F, int n, const wmi_long_params & lp, int n_audio_ctx, std::vector<wmi_long_piece> & out);
+void free_long(BatchWork & w);                          // long.cpp: the device / pinned buffers of BatchWork::lng
 int  ensure_replicas(whisper_context & ctx, int n);     // create up to n replica contexts now; returns how many exist (<= n)
 void trim_replicas(whisper_context & ctx, int keep);         // release the replicas beyond `keep` (states, streams back to the pool)
 // segment emission of one decoded window: updates prompt_past and appends to state.result_all (W/whisper.cpp:5682-5796)

@@ -198,6 +198,40 @@ class SpeechToText:
             self.last_batch_windows.append(self.last_windows)
         return out
 
+    # -- a whole recording (product library only: include/wmi_device.h wmi_full_long): cut at its silences on the device, the pieces
+    #    decoded in lock-step, one merged result with times relative to the recording.
+    def transcribe_long(self, buffer, params=None, long_params=None, device_ptr: int | None = None) -> list:
+        """-> the merged result in collect()'s form.  Leaves last_pieces (frame0, frame1, audio_ctx, mode, i_segment, n_segments per
+        piece), last_modes (wmi_batch_chunk_mode per piece), last_segments ((t0, t1, text) of the merged segments) and last_windows.
+        long_params: an abi.wmi_long_params (None: the library's defaults).  device_ptr: the PCM is on the device, `buffer` its sample count."""
+        self.last_pieces, self.last_modes, self.last_segments = [], [], []
+        if not self.ctx:
+            return []
+        p = params if params is not None else self.full_params()
+        lp = C.byref(long_params) if long_params is not None else None
+        if device_ptr is None:
+            buffer = np.ascontiguousarray(buffer, dtype=np.float32)
+            ret = self.lib.wmi_full_long(self.ctx, p, buffer.ctypes.data_as(C.c_void_p), int(buffer.size), 0, lp)
+        else:
+            ret = self.lib.wmi_full_long(self.ctx, p, C.c_void_p(device_ptr), int(buffer), 1, lp)
+        self.last_ret = ret
+        if ret != 0:
+            return []
+        for i in range(self.lib.wmi_long_n_pieces(self.ctx)):
+            pc = abi.wmi_long_piece()
+            assert self.lib.wmi_long_get_piece(self.ctx, i, C.byref(pc)) == 0
+            self.last_pieces.append({name: getattr(pc, name) for name, _ in abi.wmi_long_piece._fields_})
+            self.last_modes.append(pc.mode)
+        out = self.collect()
+        self.last_segments = self.segments()
+        return out
+
+    def segments(self) -> list:
+        """(t0, t1, text) of the segments the accessors show now (10 ms units)."""
+        lib, ctx = self.lib, self.ctx
+        return [(lib.whisper_full_get_segment_t0(ctx, i), lib.whisper_full_get_segment_t1(ctx, i), lib.whisper_full_get_segment_text(ctx, i))
+                for i in range(lib.whisper_full_n_segments(ctx))]
+
     # -- resample (src/speech_to_text.cpp:353-376): stereo capture frames at the mix rate -> mono 16 kHz.  The reference goes through
     #    libsamplerate on the CPU; here both steps run on the device (wmi_downmix_stereo, wmi_resample).
     SRC_SINC_BEST_QUALITY, SRC_SINC_MEDIUM_QUALITY, SRC_SINC_FASTEST = 0, 1, 2        # src/speech_to_text.h:151-156
@@ -341,8 +375,10 @@ class CaptureSession:
 class AudioStreamToText(SpeechToText):
     """addon/audio_stream_to_text.gd: one-shot "transcribe this WAV" node."""
 
-    def get_text(self, pcm: np.ndarray, initial_prompt: str = "") -> str:
-        tokens = self.transcribe(pcm, initial_prompt, 0)
+    def get_text(self, pcm: np.ndarray, initial_prompt: str = "", long_form: bool = False) -> str:
+        """long_form (product library only): the recording is cut at its silences and the pieces decoded in lock-step (transcribe_long)
+        instead of whisper_full's walk window by window."""
+        tokens = self.transcribe_long(pcm, self.full_params(initial_prompt, 0)) if long_form else self.transcribe(pcm, initial_prompt, 0)
         if not tokens:
             return ""
         text = tokens.pop(0).decode("utf-8", errors="replace")

@@ -1,6 +1,7 @@
 // Command-line driver of the C++ host mirror (tests/test_host_cpp.py):
 //   wmi_host_demo <model.ggml> <pcm.f32> <mode> [language] [initial_prompt] [audio_ctx]
-// mode: transcribe | vad | stream | batch (pcm file = several buffers, see below) | resample (pcm file = interleaved stereo frames;
+// mode: transcribe | vad | stream | batch (pcm file = several buffers, see below) | long (a whole recording through transcribe_long, default
+//       plan parameters, audio_ctx = max_piece_ms when > 0: {"transcription": .., "pieces": [[frame0, frame1], ..]}) | resample (pcm file = interleaved stereo frames;
 //       language = mix rate, prompt = interpolator type: prints the frame count, an FNV-1a hash of the frames' bits and the error string)
 //       | capture (pcm file = interleaved stereo frames; language = mix rate, prompt = "session" or "calls", audio_ctx = the largest number of
 //       transcribe calls: the node's own loop, CaptureStreamToText::stream_capture)
@@ -117,6 +118,15 @@ int main(int argc, char ** argv) {
         return 0;
     }
     std::vector<float> pcm((const float *) raw.data(), (const float *) raw.data() + raw.size() / 4);
+    if (mode == "long") {
+        wmi_long_params lp = wmi_long_default_params();
+        if (audio_ctx > 0) lp.max_piece_ms = audio_ctx;
+        printf("{\"transcription\": "); json_transcription(node.transcribe_long(pcm, prompt, &lp));
+        printf(", \"pieces\": [");
+        for (size_t i = 0; i < node.last_pieces.size(); ++i) printf("%s[%d, %d]", i ? ", " : "", node.last_pieces[i].frame0, node.last_pieces[i].frame1);
+        printf("]}\n");
+        return 0;
+    }
     json_transcription(node.transcribe(pcm, prompt, audio_ctx));
     printf("\n");
     return 0;

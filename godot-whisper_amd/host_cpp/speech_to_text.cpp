@@ -149,6 +149,27 @@ std::vector<Transcription> SpeechToText::transcribe_batch(const std::vector<std:
     return out;
 }
 
+Transcription SpeechToText::transcribe_long(const std::vector<float> & buffer, const std::string & initial_prompt,
+                                            const wmi_long_params * long_params) {
+    const whisper_full_params whisper_params = make_params(initial_prompt, 0);
+    last_pieces.clear();
+    if (!context_instance) {
+        fprintf(stderr, "ERROR: Context instance is null\n");
+        return Transcription();
+    }
+    const int ret = wmi_full_long(context_instance, whisper_params, buffer.data(), (int) buffer.size(), 0, long_params);
+    last_return = ret;
+    if (ret != 0) {
+        fprintf(stderr, "ERROR: Failed to process audio, returned %d\n", ret);
+        return Transcription();
+    }
+    for (int i = 0; i < wmi_long_n_pieces(context_instance); ++i) {
+        wmi_long_piece pc{};
+        if (wmi_long_get_piece(context_instance, i, &pc) == 0) last_pieces.push_back(pc);
+    }
+    return collect();                                  // the call leaves the merged result selected
+}
+
 // ------------------------------------------------------------------------------------------------ VAD
 void high_pass_filter(std::vector<float> & data, float cutoff, float sample_rate) {          // src/speech_to_text.cpp:53-66
     const float rc = 1.0f / (2.0f * 3.14159265358979323846 * cutoff);      // Math_PI is a double in the reference: double arithmetic, rounded to float

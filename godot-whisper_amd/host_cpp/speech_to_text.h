@@ -79,6 +79,12 @@ public:
     // what transcribe(buffers[c], initial_prompt, audio_ctx) returns on a fresh context
     std::vector<Transcription> transcribe_batch(const std::vector<std::vector<float>> & buffers, const std::string & initial_prompt,
                                                 int audio_ctx);
+    // not in the reference: a whole recording cut at its silences on the device, the pieces decoded in lock-step (include/wmi_device.h:
+    // wmi_full_long); one merged result, times relative to the recording.  long_params = nullptr: the library's defaults.
+    // last_pieces has the plan of the call.
+    Transcription transcribe_long(const std::vector<float> & buffer, const std::string & initial_prompt = "",
+                                  const wmi_long_params * long_params = nullptr);
+    std::vector<wmi_long_piece> last_pieces;
 
     whisper_context * context() { return context_instance; }
     int last_return = 0;          // whisper_full's code of the last transcribe()

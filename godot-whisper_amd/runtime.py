@@ -125,6 +125,17 @@ DEVICE_API = [
     ("wmi_get_token_dtw_timings", None, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     ("wmi_selftest_dtw_matrix", C.c_int, [C.c_int] * 8 + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     ("wmi_selftest_dtw_path", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
+    ("wmi_long_default_params", abi.wmi_long_params, []),
+    ("wmi_full_long", C.c_int, [C.c_void_p, abi.whisper_full_params, C.c_void_p, C.c_int, C.c_int, C.POINTER(abi.wmi_long_params)]),
+    ("wmi_long_n_pieces", C.c_int, [C.c_void_p]),
+    ("wmi_long_get_piece", C.c_int, [C.c_void_p, C.c_int, C.POINTER(abi.wmi_long_piece)]),
+    ("wmi_long_select", C.c_int, [C.c_void_p, C.c_int]),
+    ("wmi_get_long_timings", None, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
+    ("wmi_selftest_frame_energy", C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    ("wmi_long_stage_samples", C.c_int, []),
+    ("wmi_selftest_long_window", C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    ("wmi_selftest_long_plan", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(abi.wmi_long_params), C.c_int,
+                                         C.POINTER(abi.wmi_long_piece), C.c_int]),
 ]
 
 _lib = None

@@ -596,6 +596,77 @@ WHISPER_API int     wmi_selftest_dtw_matrix(int device, int L, int S, int H, int
                                             const int32_t * layer_head, int n_pairs, float * A_out);
 WHISPER_API int     wmi_selftest_dtw_path(int device, int R, int M, const float * A, int32_t * jumps, int32_t * path, int * n_path);
 
+/* Long recordings: cut at silences on the device, decode the pieces in lock-step.
+ * whisper_full walks a long signal window by window (each seek comes from the previous window's timestamps); whisper_full_parallel cuts it
+ * into equal pieces wherever the arithmetic lands.  wmi_full_long looks at the signal first:
+ *   energies  e[f] = sum over i in [160 f, min(160 f + 160, n)) of | x[i] - x[i-1] |, x[-1] := 0, for every 10 ms frame f < F = ceil(n / 160):
+ *             f32 throughout, the sum left to right from 0.0f (csrc/k_segment.hip; the first difference stands in for the node's freq_thold
+ *             high-pass without its serial chain).  They come back in one copy behind one wait.
+ *   plan      host only, deterministic, all in frames (csrc/segment.cpp; DESIGN.md section 5 has the rules in full): frames below
+ *             thold x the mean level or below floor per sample are quiet; quiet runs of >= min_silence_ms are gaps, the runs between
+ *             them islands; islands are widened by pad_ms, never past the midpoint of the gap to the neighbouring island; pieces absorb
+ *             islands left to right while the gap in front is shorter than max_gap_ms and the piece stays within max_piece_ms; an island
+ *             longer than max_piece_ms is cut at the frame of least energy in the last third of that length; pieces below 1 s are
+ *             extended to 1 s where the neighbours leave room.  Gaps of max_gap_ms and more are decoded by no piece.
+ *   decoding  the pieces go to wmi_full_batch (fit_audio_ctx: wmi_full_batch_ctx with min(n_audio_ctx, (frames + 1) / 2 + 128) per piece, the
+ *             node's total_time * 50 + 128) as device pointers into the ONE PCM buffer: host PCM is uploaded once, device PCM not copied.
+ *             Every piece is whisper_full on a fresh context with offset_ms = duration_ms = 0 and no_context, as every lock-step chunk;
+ *             params.offset_ms / duration_ms restrict the frames the plan sees ([offset_ms / 10, + duration_ms / 10) clipped to F).
+ *   result    the pieces' segments in order with t0 / t1, the tokens' t0 / t1 (where set: >= 0), every t_dtw >= 0 and every wmi_window.seek
+ *             shifted by the piece's frame0, every window's i_segment rebased.  Pieces are disjoint: nothing is clamped.  The call leaves the
+ *             merged result selected; wmi_long_select(piece) shows one piece with piece-relative times as wmi_batch_select does,
+ *             wmi_long_select(-1) the merged result again.  whisper_full_lang_id of the merged view is the FIRST piece's; with "auto" every
+ *             piece is detected on its own, as wmi_full_batch does (wmi_batch_lang_id(piece) has each).  The no-speech and token-DTW modes
+ *             pass through untouched.  The piece views stay valid until the next transcription call on the context.
+ * The defaults below are starting values: they have been tried on synthetic signals only.  Embedders tune them.
+ * Returns wmi_full_batch's codes; 0 with no piece and no segment for a signal without an island (nothing is decoded).  -1 before any device
+ * work: a NULL context / pcm, n_samples < 0, a field of wmi_long_params out of range (thold or floor negative or not finite,
+ * min_silence_ms < 10, pad_ms < 0, max_gap_ms < 0, max_piece_ms outside 1000 .. 30000), or new_segment_callback, progress_callback,
+ * encoder_begin_callback or logits_filter_callback set (their times and indices would be piece-relative: out of scope).  n_samples == 0: -3, as
+ * whisper_full.  Host-only and weights-pending contexts: -2, as wmi_full_batch.
+ * wmi_get_batch_timings keeps its meaning (the decoding of the pieces); wmi_get_long_timings has the front's own times, microseconds:
+ * us3 = { upload of host PCM, energies (kernel + copy + the wait), plan }, n2 = { frames, pieces }. */
+struct wmi_long_params {
+    float   thold;            /* 0.25   a frame is quiet below this multiple of the mean level */
+    float   floor;            /* 1e-4   or below this absolute level per sample (the node's 0.0001) */
+    int32_t min_silence_ms;   /* 300    a quiet run this long is a gap */
+    int32_t pad_ms;           /* 100    speech is widened by this much into the gaps */
+    int32_t max_gap_ms;       /* 2000   gaps at least this long are left out of the pieces */
+    int32_t max_piece_ms;     /* 30000  in 1000 .. 30000 */
+    int32_t fit_audio_ctx;    /* 0      1: an encoder length per piece */
+};
+struct wmi_long_piece {
+    int32_t frame0, frame1;   /* the piece is the samples [160 frame0, min(160 frame1, n_samples)) */
+    int32_t audio_ctx;        /* its encoder length (0 = the model's n_audio_ctx); without fit_audio_ctx: params.audio_ctx (the plan hook: 0) */
+    int32_t mode;             /* wmi_batch_chunk_mode of the piece */
+    int32_t i_segment;        /* its first segment in the merged result */
+    int32_t n_segments;
+};
+WHISPER_API struct wmi_long_params wmi_long_default_params(void);
+WHISPER_API int  wmi_full_long(struct whisper_context * ctx, struct whisper_full_params params, const float * pcm, int n_samples,
+                               int pcm_on_device, const struct wmi_long_params * long_params);      /* NULL: the defaults */
+WHISPER_API int  wmi_long_n_pieces(struct whisper_context * ctx);                                   /* of the last wmi_full_long; -1 without a context */
+WHISPER_API int  wmi_long_get_piece(struct whisper_context * ctx, int i, struct wmi_long_piece * out);   /* 0, -1 for a bad index */
+WHISPER_API int  wmi_long_select(struct whisper_context * ctx, int piece);     /* -1: the merged result; returns the segment count, -1 for a bad index / no result */
+WHISPER_API void wmi_get_long_timings(struct whisper_context * ctx, int64_t * us3, int32_t * n2);
+/* Test hooks (no context; host pointers; argument errors are decided before the device is touched).
+ *   wmi_selftest_frame_energy  the energies of x [n] into e_out [F = ceil(n / 160)]; device = -1: the sequential host restatement (the definition).
+ *                              device >= 0: e_out holds F + 64 floats; all of them go to the device as the caller filled them (a sentinel), the
+ *                              kernel runs once, all of them come back — the 64 behind F as they were unless the kernel wrote there.
+ *                              Returns 0; -1 bad argument (NULL, n < 1, device < -1); -2 / -3 device errors.
+ *   wmi_long_stage_samples     the kernel's staging extent in samples (a workgroup's run of frames): where its hand-over between workgroups lies
+ *   wmi_selftest_long_window   the frames [*f0, *f1) of an n_samples signal that offset_ms / duration_ms leave to the plan, and in *n_sub the
+ *                              samples they hold.  Returns 0; -1 bad argument (n_samples < 1, negative times, NULL).
+ *   wmi_selftest_long_plan     the plan for the energies e [F] of an n_samples signal (F = ceil(n_samples / 160)) on a model with that
+ *                              n_audio_ctx: up to cap pieces into out (frame0, frame1, audio_ctx; the other fields 0); returns the piece count
+ *                              (which may exceed cap), -1 on a bad argument.  wmi_full_long plans with the same function, on the frames the
+ *                              window leaves: e + f0, f1 - f0 frames, n_sub samples, frame numbers shifted back by f0. */
+WHISPER_API int  wmi_selftest_frame_energy(int device, const float * x, int n, float * e_out);
+WHISPER_API int  wmi_long_stage_samples(void);
+WHISPER_API int  wmi_selftest_long_window(int n_samples, int offset_ms, int duration_ms, int * f0, int * f1, int * n_sub);
+WHISPER_API int  wmi_selftest_long_plan(const float * e, int F, int n_samples, const struct wmi_long_params * long_params, int n_audio_ctx,
+                                        struct wmi_long_piece * out, int cap);
+
 /* Host worker pool self-test (no device needed): `reps` jobs of `n_tasks` tasks; returns reps * n_tasks * (n_tasks + 1) / 2
  * when every task of every job ran exactly once. */
 WHISPER_API int64_t wmi_selftest_pool(int n_tasks, int reps);
