@@ -11,6 +11,19 @@ typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef _Float16 half4 __attribute__((ext_vector_type(4)));
 typedef float    floatx4 __attribute__((ext_vector_type(4)));
 
+// Leading arguments of k_gemm: 13 dwords that arrive in SGPRs with the wavefront (kernarg preload) — both operands with their
+// strides, the three extents, the lab bits and the q|k|v split width that decide the tile's path, and the probe pointer behind the first
+// stamp: everything a workgroup needs to request its first tiles.  The kernel rebuilds a GemmArgs from them and the trailing by-value
+// `cold` struct (read from the argument segment where the epilogue uses it; its copies of the leading fields are not read).
+// k_gemm8 keeps the struct alone: its K loop counts its own vector-memory waits, and its flat form gave one differing tile in one run of
+// tests/test_gpu_gemm.py's direct 128-row case that was not explained (profiles/r14a_kernarg_preload.txt item 7).
+#define WMI_GEMM_FLAT_PARAMS const __half * A, const __half * W, unsigned long long * probe, int lda, int ldw, int M, int N, int K, int no_glds, int S
+#define WMI_GEMM_FLAT_ARGS(a) (a).A, (a).W, (a).probe, (a).lda, (a).ldw, (a).M, (a).N, (a).K, (a).no_glds, (a).S
+__device__ __forceinline__ GemmArgs gemm_args(WMI_GEMM_FLAT_PARAMS, const GemmArgs & cold) {
+    GemmArgs a = cold;
+    a.A = A; a.W = W; a.probe = probe; a.lda = lda; a.ldw = ldw; a.M = M; a.N = N; a.K = K; a.no_glds = no_glds; a.S = S;
+    return a;
+}
 
 __device__ __forceinline__ float round_f16(float x) { return __half2float(f2h(x)); }
 

@@ -855,11 +855,17 @@ __global__ __launch_bounds__(256) void k_xattn_fused(const float * __restrict__ 
 // publishes the head's 64 values as 32 granules {f16 pair, tag}; the first S / 16 workgroups sweep the S / 2 granules of the row and
 // take four rows of the projection per wavefront (weights requested at the start).  Per value the operations and their order are the two
 // launches'.  4 <= ns <= 8 key slices, S <= 512.  Tags, spins, status word: MlpPairArgs.  The partials still go to part_o / part_l / pmax.
-__global__ __launch_bounds__(256) void k_xback(const XbackArgs a_in, const Stamp sp) {
+__global__ __launch_bounds__(256) void k_xback(const float * x, const float * ln_g, const float * ln_b, const __half * wq, const __half * kc, const __half * vc,
+                                               const uint32_t dims, const uint32_t keys_tk, const XbackArgs cold, const Stamp sp) {
+    // the leading dwords arrive in SGPRs with the wavefront (kernarg preload): the row, gain / bias, the query weights, the cross cache,
+    // dims = S | par << 15 | ns << 16 | STAMP_ON_BIT and keys_tk = T | ks << 16 — the addresses of the first loads below; `cold` is read from the argument
+    // segment where it is used (its copies of the leading fields are not read)
+    XbackArgs a = cold;
+    a.x = x; a.ln_g = ln_g; a.ln_b = ln_b; a.wq = wq; a.kc = kc; a.vc = vc;
+    a.S = (int) (dims & 0x7fffu); a.par = (int) ((dims >> 15) & 1u); a.ns = (int) ((dims >> 16) & 0x7fffu);      // (bit 31 is the stamp switch)
+    a.T = (int) (keys_tk & 0xffffu); a.ks = (int) (keys_tk >> 16);
     // lock-step rows: row z is a one-row problem of its own: shift the per-row operands, everything below is the one-row kernel
-    XbackArgs a = a_in;
-    {
-        const int z = blockIdx.z;
+    if (const int z = blockIdx.z) {                         // (row 0 — the one-row step — waits for no stride of `cold` in front of its loads)
         a.x += (size_t) z * a.S; a.xout += (size_t) z * a.S;
         a.kc += (int64_t) z * a.kv_row_stride; a.vc += (int64_t) z * a.kv_row_stride;
         a.gp += (size_t) z * XBACK_ROW_GRANULES; a.ga += (size_t) z * XBACK_ROW_GRANULES;
@@ -868,7 +874,7 @@ __global__ __launch_bounds__(256) void k_xback(const XbackArgs a_in, const Stamp
     __shared__ float red[4], lred[4];
     __shared__ float ored[4][64];
     __shared__ __attribute__((aligned(16))) __half act[512];
-    const unsigned long long ts0 = stamp_t0(sp.base);
+    const unsigned long long ts0 = stamp_t0_if(dims & STAMP_ON_BIT);
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int head = blockIdx.x, slice = blockIdx.y, H = gridDim.x, ns = a.ns, S = a.S, K = S;
     const int lin = head + H * slice;
@@ -1222,7 +1228,10 @@ void xback(XbackArgs a, int H, float * scratch, hipStream_t st) {
     const int n = a.rows > 1 ? a.rows : 1;
     const XLayout L = xattn_layout(n, H, a.T, scratch);
     a.ks = L.ks; a.ns = L.ns; a.pmax = L.pmax; a.part_o = L.part_o; a.part_l = L.part_l;
-    hipLaunchKernelGGL(k_xback, dim3(H, L.ns, n), dim3(256), 0, st, a, stamp_next());
+    // (S <= 512, ns <= 8, T = ns ks < 65536: xback_usable)
+    const Stamp sp = stamp_next();
+    const uint32_t dims = (uint32_t) a.S | (uint32_t) (a.par & 1) << 15 | (uint32_t) a.ns << 16 | (sp.base ? STAMP_ON_BIT : 0u), keys_tk = (uint32_t) a.T | (uint32_t) a.ks << 16;
+    hipLaunchKernelGGL(k_xback, dim3(H, L.ns, n), dim3(256), 0, st, a.x, a.ln_g, a.ln_b, a.wq, a.kc, a.vc, dims, keys_tk, a, sp);
 }
 
 size_t attn_cross_scratch_floats(int n, int H, int T) {

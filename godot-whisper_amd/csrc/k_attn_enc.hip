@@ -60,6 +60,13 @@ __global__ __launch_bounds__(QW * KS * 64) void k_attn_enc2(const __half * __res
     //  per CU, which is what the registers allow, instead of three)
     constexpr size_t TB_OFF = KS == 1 ? 0 : ((RING_B + EXTRA_B) > COMB_B ? (RING_B + EXTRA_B) : COMB_B);
     constexpr float LOG2E = 1.44269504088896340736f;
+    // The arguments behind the preloaded dwords and the grid's size, in one batch of scalar loads (kernels.h: WMI_ARG_NOW's idea, as ONE
+    // statement: one per value made hipcc wait for each grid word by itself): taken where they are first used — the order switch, the grid,
+    // a row's own length — they were four dependent round trips in front of the first tile
+    {
+        const unsigned gx = gridDim.x, gy = gridDim.y, gz = gridDim.z;
+        asm volatile("" :: "s"(xcd_order), "s"(qk_rows), "s"(out_rows), "s"(lens.n), "s"(gx), "s"(gy), "s"(gz));
+    }
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // wave-uniform: scalar branches
     const int grp = KS == 1 ? 0 : wave / QW, qw = wave - grp * QW;
     const int i = lane & 31, g = lane >> 5;

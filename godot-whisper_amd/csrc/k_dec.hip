@@ -18,6 +18,7 @@
 #include "ln_row.h"
 #include <type_traits>
 
+#include <cassert>
 #include <cstdlib>
 #include <algorithm>
 
@@ -799,15 +800,23 @@ __global__ __launch_bounds__(256) void k_gemv(const GemvArgs a) {
 // compile time: the decode step's six hot combinations get kernels without the other kinds' code and without the dispatch on
 // kernel arguments (a launch on the step's critical path pays for every instruction and scalar load in front of its first
 // memory request); -1 keeps the run-time dispatch.
+constexpr uint32_t GEMV1_LANES_BIT = 1u << 30;          // k_gemv1's dims: lock-step rows (GemvArgs::lanes != 0)
 template <int RIF, int NCH, bool NT, int PRO = -1, int EPI = -1, int HPW = 0, int WPB = 4, bool FS = false>
-__global__ __launch_bounds__(64 * WPB) void k_gemv1(const GemvArgs a_in) {
+__global__ __launch_bounds__(64 * WPB) void k_gemv1(const float * x32, const float * ln_g, const float * ln_b, const __half * a16, const __half * W, const float * bias,
+                                                    const uint32_t dims, const GemvArgs cold) {
+    // the 13 leading dwords arrive in SGPRs with the wavefront (kernarg preload): the activation row in either form, gain / bias of the
+    // LayerNorm prologue, the weights, the bias and dims = K | N << 13 | GEMV1_LANES_BIT | STAMP_ON_BIT — the addresses of the LayerNorm and
+    // plain prologues' first loads and of the weight rows; `cold` (the attention prologues' operands among it) is read from the argument
+    // segment where it is used (its copies of the leading fields are not read)
+    GemvArgs a = cold;
+    a.x32 = x32; a.ln_g = ln_g; a.ln_b = ln_b; a.a16 = a16; a.W = W; a.bias = bias;
+    a.K = (int) (dims & 0x1fffu); a.N = (int) ((dims >> 13) & 0x1ffffu);
     // Lock-step chunk rows (a_in.lanes != 0, grid.y = rows): row y IS a one-row problem — its own activation row, its own self cache
     // and step record, its own slice of the cross-attention partials — so the arguments are shifted to row y and everything below is
     // the one-row kernel, bit for bit.  The weight rows are read once per row instead of once: grid.x is a multiple of 8, so the
     // workgroups of ALL rows that stream a given weight tile share one XCD (workgroup id % 8 = tile % 8) and the tile comes out of
     // that XCD's L2 for rows 1..n-1 (7.3 MB per decoder layer, 4 MB of L2 per XCD).
-    GemvArgs a = a_in;
-    if (a_in.lanes) {
+    if (dims & GEMV1_LANES_BIT) {
         const int y = blockIdx.y;
         const int epi_ = EPI < 0 ? a.epi : EPI;
         if (a.x32) a.x32 += (size_t) y * a.K;
@@ -823,8 +832,9 @@ __global__ __launch_bounds__(64 * WPB) void k_gemv1(const GemvArgs a_in) {
             const size_t hs = (size_t) y * (a.K >> 6) * a.comb_ns;                       // partials of row y: [head][slice]
             a.comb_o += hs * 64; a.comb_l += hs; if (a.comb_m) a.comb_m += hs;
         }
-        a.lanes = 0; a.n = 1;
+        a.n = 1;
     }
+    a.lanes = 0;
     const bool pro_ln = PRO < 0 ? a.ln_g != nullptr : PRO == 1;
     const bool pro_sa = PRO < 0 ? a.sa_q != nullptr : PRO == 2;
     const bool pro_comb = PRO < 0 ? a.comb_o != nullptr : PRO == 3;
@@ -832,7 +842,7 @@ __global__ __launch_bounds__(64 * WPB) void k_gemv1(const GemvArgs a_in) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __half * act = (__half *) smem;                         // [K], attention prologues only
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const unsigned long long ts0 = stamp_t0(a.stamps);
+    const unsigned long long ts0 = stamp_t0_if(dims & STAMP_ON_BIT);
     const int K = a.K;
     int nblk = gridDim.x;
     if constexpr (PRO <= 0 && (EPI < 0 || EPI == EPI_F32_BIAS_RESID)) {
@@ -1184,7 +1194,9 @@ void launch_gemv1(const GemvArgs & a, hipStream_t st, int max_blocks = 512) {
     if (PRO <= 0 && (EPI < 0 || EPI == EPI_F32_BIAS_RESID) && a.step_copy_src) blocks += 1;       // the step-record mirror (see the kernel)
     int rows = 1;
     if (a.lanes) { rows = a.n; blocks = (blocks + 7) & ~7; }      // lock-step rows: grid.y = row, grid.x a multiple of 8 (see the kernel)
-    hipLaunchKernelGGL((k_gemv1<RIF, NCH, NT, PRO, EPI, HPW, WPB, FS>), dim3(blocks, rows), dim3(64 * WPB), smem, st, a);
+    assert(a.K >= 0 && a.K < (1 << 13) && a.N >= 0 && a.N < (1 << 17));       // dims' fields (K <= 512 NCH; the vocabulary is the largest N)
+    const uint32_t dims = (uint32_t) a.K | (uint32_t) a.N << 13 | (a.lanes ? GEMV1_LANES_BIT : 0u) | (a.stamps ? STAMP_ON_BIT : 0u);
+    hipLaunchKernelGGL((k_gemv1<RIF, NCH, NT, PRO, EPI, HPW, WPB, FS>), dim3(blocks, rows), dim3(64 * WPB), smem, st, a.x32, a.ln_g, a.ln_b, a.a16, a.W, a.bias, dims, a);
 }
 
 // the decode step's hot (prologue, epilogue) combinations at one row; false = no specialised kernel for these arguments
@@ -1805,10 +1817,18 @@ int gemv_fused_parts(const GemvArgs & a) {
 // workgroups start at different times and the early ones poll (profiles/r05g_* §9).
 // NCH1 / NCH2: 512-column chunks of a row of W1 (S columns) / of W2 (4 S columns): (1, 3) tiny, (1, 4) base, (2, 6) small, (2, 8) medium, (3, 10) large
 template <int NCH1, int NCH2, int WPB>
-__global__ __launch_bounds__(64 * WPB) void k_mlp_pair(const MlpPairArgs a, float * __restrict__ xio, int G, const Stamp sp) {
+__global__ __launch_bounds__(64 * WPB) void k_mlp_pair(float * __restrict__ xio, const float * ln_g, const float * ln_b, const __half * W1, const __half * W2,
+                                                       uint32_t * epoch, const uint32_t dims, const MlpPairArgs cold, const Stamp sp) {
+    // the 13 leading dwords arrive in SGPRs with the wavefront (kernarg preload): the row, gain / bias, both weight bases, the tag words and
+    // dims = S | par << 15 | G << 16 | STAMP_ON_BIT — every address of the loads at the top; `cold` is read from the argument segment where it is used
+    // (its copies of the leading fields are not read)
+    MlpPairArgs a = cold;
+    a.ln_g = ln_g; a.ln_b = ln_b; a.W1 = W1; a.W2 = W2; a.epoch = epoch;
+    a.S = (int) (dims & 0x7fffu); a.par = (int) ((dims >> 15) & 1u);
+    const int G = (int) ((dims >> 16) & 0x7fffu);           // (bit 31 is the stamp switch)
     __shared__ __attribute__((aligned(16))) uint32_t hrow[NCH2 * 256];       // the hidden row as f16 pairs
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const unsigned long long ts0 = stamp_t0(sp.base);
+    const unsigned long long ts0 = stamp_t0_if(dims & STAMP_ON_BIT);
     if ((int) blockIdx.x == G) {                            // chained greedy steps: the host's step record -> device (see k_gemv1)
         if (tid < (int) (sizeof(DecStep) / 4)) ((int32_t *) a.step_copy_dst)[tid] = ((const volatile int32_t *) a.step_copy_src)[tid];
         return;
@@ -1967,12 +1987,17 @@ __global__ __launch_bounds__(64 * WPB) void k_mlp_pair(const MlpPairArgs a, floa
 // step's slot is never taken from the cache (other workgroups of this launch write it): its k / v are the granules'.  Dynamic LDS:
 // front_long_lds(cap) bytes.  Phases 1 and 3 are the short form's.
 template <int NCH, int WPB, bool LONG = false>
-__global__ __launch_bounds__(64 * WPB) void k_front(const FrontArgs a_in, const Stamp sp) {
+__global__ __launch_bounds__(64 * WPB) void k_front(const float * x, const float * ln_g, const float * ln_b, const __half * Wqkv, __half * ck, __half * cv,
+                                                    const uint32_t dims, const int cap, const FrontArgs cold, const Stamp sp) {
     static_assert(!LONG || WPB == 4, "the long form's quarters are four wavefronts");
+    // the leading dwords arrive in SGPRs with the wavefront (kernarg preload): the row, gain / bias, the q|k|v weights, the self cache,
+    // dims = S | par << 15 | STAMP_ON_BIT and the cache's cells — the addresses of the first loads below; `cold` is read from the argument segment where
+    // it is used (its copies of the leading fields are not read)
+    FrontArgs a = cold;
+    a.x = x; a.ln_g = ln_g; a.ln_b = ln_b; a.Wqkv = Wqkv; a.ck = ck; a.cv = cv; a.cap = cap;
+    a.S = (int) (dims & 0x7fffu); a.par = (int) ((dims >> 15) & 1u);
     // lock-step rows: row y is a one-row problem of its own (k_gemv1's convention): shift the per-row operands, everything below is the one-row kernel
-    FrontArgs a = a_in;
-    {
-        const int y = blockIdx.y;
+    if (const int y = blockIdx.y) {                         // (row 0 — the one-row step — waits for no stride of `cold` in front of its loads)
         a.x += (size_t) y * a.S; a.xout += (size_t) y * a.S; a.q16 += (size_t) y * a.S;
         a.ck += (int64_t) y * a.cache_row_stride; a.cv += (int64_t) y * a.cache_row_stride;
         a.kv_head += (size_t) y * a.step_stride; a.n_kv += (size_t) y * a.step_stride;
@@ -1983,7 +2008,7 @@ __global__ __launch_bounds__(64 * WPB) void k_front(const FrontArgs a_in, const 
     __shared__ __attribute__((aligned(16))) __half hatt[64];
     __shared__ __attribute__((aligned(16))) float wscr[64];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), wg = blockIdx.x;
-    const unsigned long long ts0 = stamp_t0(sp.base);
+    const unsigned long long ts0 = stamp_t0_if(dims & STAMP_ON_BIT);
     const int S = a.S, K = S, H = S >> 6, N1 = 3 * S;
     const int gw = wg * WPB + wave;
     constexpr int R3 = WPB == 8 ? 2 : 4;                    // rows of the out projection per wavefront
@@ -2394,7 +2419,8 @@ void mlp_pair(const MlpPairArgs & a, float * x_inout, hipStream_t st) {
     const int blocks = G + (a.step_copy_src ? 1 : 0);
     const int nch2 = (4 * S + 511) / 512;
     const Stamp sp = stamp_next();
-#define WMI_PAIR_GO(N1, N2, W) hipLaunchKernelGGL((k_mlp_pair<N1, N2, W>), dim3(blocks), dim3(64 * W), 0, st, a, x_inout, G, sp)
+    const uint32_t dims = (uint32_t) S | (uint32_t) (a.par & 1) << 15 | (uint32_t) G << 16 | (sp.base ? STAMP_ON_BIT : 0u);       // (S <= 1024: mlp_pair_usable)
+#define WMI_PAIR_GO(N1, N2, W) hipLaunchKernelGGL((k_mlp_pair<N1, N2, W>), dim3(blocks), dim3(64 * W), 0, st, x_inout, a.ln_g, a.ln_b, a.W1, a.W2, a.epoch, dims, a, sp)
     WMI_PAIR_TABLE(S, nch2, WMI_PAIR_GO);
 #undef WMI_PAIR_GO
 }
@@ -2442,24 +2468,28 @@ bool front_usable(int S, int rows, int long_cap) {
     }
     return (3 * S / (wpb == 4 ? 16 : 32)) * std::max(rows, 1) <= v - 1;
 }
+// k_front's leading arguments (S <= 1024: front_usable)
+#define FRONT_FLAT(a) (a).x, (a).ln_g, (a).ln_b, (a).Wqkv, (a).ck, (a).cv, (uint32_t) (a).S | (uint32_t) ((a).par & 1) << 15 | (sp.base ? STAMP_ON_BIT : 0u), (a).cap
 void front(const FrontArgs & a, hipStream_t st, bool long_kv) {
+    const Stamp sp = stamp_next();
     const int rows = a.rows > 1 ? a.rows : 1;
     if (long_kv) {                                          // (front_usable(S, 1, cap): one row, four wavefronts)
         const dim3 grid(3 * a.S / 16, 1);
         const size_t lds = front_long_lds(a.cap);
-        if (a.S <= 512) hipLaunchKernelGGL((k_front<1, 4, true>), grid, dim3(256), lds, st, a, stamp_next());
-        else            hipLaunchKernelGGL((k_front<2, 4, true>), grid, dim3(256), lds, st, a, stamp_next());
+        if (a.S <= 512) hipLaunchKernelGGL((k_front<1, 4, true>), grid, dim3(256), lds, st, FRONT_FLAT(a), a, sp);
+        else            hipLaunchKernelGGL((k_front<2, 4, true>), grid, dim3(256), lds, st, FRONT_FLAT(a), a, sp);
     } else
     if (front_wpb(rows) == 4) {
         const dim3 grid(3 * a.S / 16, rows);
-        if (a.S <= 512) hipLaunchKernelGGL((k_front<1, 4>), grid, dim3(256), 0, st, a, stamp_next());
-        else            hipLaunchKernelGGL((k_front<2, 4>), grid, dim3(256), 0, st, a, stamp_next());
+        if (a.S <= 512) hipLaunchKernelGGL((k_front<1, 4>), grid, dim3(256), 0, st, FRONT_FLAT(a), a, sp);
+        else            hipLaunchKernelGGL((k_front<2, 4>), grid, dim3(256), 0, st, FRONT_FLAT(a), a, sp);
     } else {
         const dim3 grid(3 * a.S / 32, rows);
-        if (a.S <= 512) hipLaunchKernelGGL((k_front<1, 8>), grid, dim3(512), 0, st, a, stamp_next());
-        else            hipLaunchKernelGGL((k_front<2, 8>), grid, dim3(512), 0, st, a, stamp_next());
+        if (a.S <= 512) hipLaunchKernelGGL((k_front<1, 8>), grid, dim3(512), 0, st, FRONT_FLAT(a), a, sp);
+        else            hipLaunchKernelGGL((k_front<2, 8>), grid, dim3(512), 0, st, FRONT_FLAT(a), a, sp);
     }
 }
+#undef FRONT_FLAT
 
 void gemv(const GemvArgs & a, hipStream_t st) {
     const Stamp sp = stamp_next();

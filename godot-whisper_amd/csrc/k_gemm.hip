@@ -41,7 +41,8 @@ __device__ __forceinline__ uint32_t lds_off(int row, int chunk) {      // byte o
 // one workgroup per CU with a three-deep 48 KB ring = 96 KB in flight per CU against 2 x 32 KB for two 128 x 128 workgroups, and
 // 25 % fewer operand bytes through L2 -> LDS)
 template <int BM, int BN, int EPI, int NST = 2, int NW = 4>
-__global__ __launch_bounds__(NW * 64) void k_gemm(const GemmArgs a) {
+__global__ __launch_bounds__(NW * 64) void k_gemm(WMI_GEMM_FLAT_PARAMS, const GemmArgs cold) {
+    const GemmArgs a = gemm_args(A, W, probe, lda, ldw, M, N, K, no_glds, S, cold);
     constexpr int WN_ = NW / 2;                        // wavefronts along N (2 along M)
     constexpr int FM = BM / 32, FN = BN / (WN_ * 16);  // fragments per wavefront
     constexpr int LA = BM / (NW * 8), LB = BN / (NW * 8);   // 16-byte loads per thread per tile (register-staged path)
@@ -255,7 +256,7 @@ void launch_n(const GemmArgs & a, hipStream_t st) {
     const size_t smem = NST * (size_t) (BM + BN) * 128;
     static std::atomic<uint64_t> lds_ok{0};
     allow_full_lds((const void *) k_gemm<BM, BN, EPI, NST, NW>, lds_ok);
-    hipLaunchKernelGGL((k_gemm<BM, BN, EPI, NST, NW>), dim3(ntm * ntn), dim3(NW * 64), smem, st, a);
+    hipLaunchKernelGGL((k_gemm<BM, BN, EPI, NST, NW>), dim3(ntm * ntn), dim3(NW * 64), smem, st, WMI_GEMM_FLAT_ARGS(a), a);
 }
 // ---- the dispatch rule: which tile, ring and loop serve (epilogue, M, N, K).  Pure arithmetic: gemm_plan() below.
 GemmPlan tile(int epi, const GemmArgs & a, int bm, int bn, int ring, int waves = 4) {

@@ -20,9 +20,6 @@ __global__ __launch_bounds__(256) void k_layernorm(const float * __restrict__ x,
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
     const float * xr = x + (size_t) row * S;
-    // lock-step chunks: input rows chunk * rpc_in + t, output rows chunk * rpc_out + t (the q|k|v GEMM wants every chunk to start on a
-    // 16-row boundary, see batch.cpp); rpc_in = 0: the same row
-    const int orow = rpc_in > 0 ? (row / rpc_in) * rpc_out + row % rpc_in : row;
     // all loads of the row (x, gain, bias) first, from clamped columns: with the load inside the summation loop hipcc waited
     // for every 16 bytes before requesting the next (MAXV + 2 MAXV dependent round trips per row)
     float4 v[MAXV], gg[MAXV], bb[MAXV];
@@ -31,6 +28,11 @@ __global__ __launch_bounds__(256) void k_layernorm(const float * __restrict__ x,
         const int c = (i * 64 + lane) * 4, cc = c < S ? c : 0;
         v[i] = *(const float4 *) (xr + cc); gg[i] = *(const float4 *) (g + cc); bb[i] = *(const float4 *) (b + cc);
     }
+    __builtin_amdgcn_sched_barrier(0);
+    // lock-step chunks: input rows chunk * rpc_in + t, output rows chunk * rpc_out + t (the q|k|v GEMM wants every chunk to start on a
+    // 16-row boundary, see batch.cpp); rpc_in = 0: the same row.  Behind the loads: rpc_in / rpc_out lie past the preloaded argument
+    // dwords, and in front of them the row's loads waited for that scalar load
+    const int orow = rpc_in > 0 ? (row / rpc_in) * rpc_out + row % rpc_in : row;
     float sum = 0.0f;
 #pragma unroll
     for (int i = 0; i < MAXV; ++i) {

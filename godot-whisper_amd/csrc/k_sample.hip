@@ -113,7 +113,10 @@ __global__ __launch_bounds__(NT) void k_filter_stats(const float * __restrict__ 
 // 12: up to 768 from the vocabulary projection's fused epilogue — with PPL = 1 the arithmetic is exactly the one-partial form)
 template <int XU, int PPL>
 __global__ __launch_bounds__(64) void k_filter_pick(const Partial * __restrict__ part, int nparts, const DecStep * __restrict__ stp,
-                                                    SampleOut * __restrict__ out, SampleOut * __restrict__ out_host, const ChainNext chain, const Stamp sp) {
+                                                    SampleOut * __restrict__ out, SampleOut * __restrict__ out_host, unsigned long long * stamp_base, int stamp_slot,
+                                                    const ChainNext chain) {
+    // (the stamp as two leading parameters: behind the by-value ChainNext it was a scalar load and a wait in front of the partials' loads)
+    const Stamp sp = {stamp_base, stamp_slot};
     const unsigned long long ts0 = stamp_t0(sp.base);
     const int lane = threadIdx.x;
     part += (size_t) blockIdx.x * nparts; stp += blockIdx.x; out += blockIdx.x; if (out_host) out_host += blockIdx.x;
@@ -329,15 +332,16 @@ void filter_argmax(const float * logits, const uint8_t * static_ban, const DecSt
     const int xu = cn.step_rw ? (cn.S + 511) / 512 : 1;
     const int np = fused ? fused_parts : NB;
     constexpr int PF = FS_MAX_PARTS / 64;
+    const Stamp sp = stamp_next();
     if (fused) {
-        if (xu <= 1)      hipLaunchKernelGGL((k_filter_pick<1, PF>), dim3(1), dim3(64), 0, st, part, np, step, out, out_host, cn, stamp_next());
-        else if (xu == 2) hipLaunchKernelGGL((k_filter_pick<2, PF>), dim3(1), dim3(64), 0, st, part, np, step, out, out_host, cn, stamp_next());
-        else              hipLaunchKernelGGL((k_filter_pick<3, PF>), dim3(1), dim3(64), 0, st, part, np, step, out, out_host, cn, stamp_next());
+        if (xu <= 1)      hipLaunchKernelGGL((k_filter_pick<1, PF>), dim3(1), dim3(64), 0, st, part, np, step, out, out_host, sp.base, sp.slot, cn);
+        else if (xu == 2) hipLaunchKernelGGL((k_filter_pick<2, PF>), dim3(1), dim3(64), 0, st, part, np, step, out, out_host, sp.base, sp.slot, cn);
+        else              hipLaunchKernelGGL((k_filter_pick<3, PF>), dim3(1), dim3(64), 0, st, part, np, step, out, out_host, sp.base, sp.slot, cn);
         return;
     }
-    if (xu <= 1)      hipLaunchKernelGGL((k_filter_pick<1, 1>), dim3(n_rows), dim3(64), 0, st, part, np, step, out, out_host, cn, stamp_next());
-    else if (xu == 2) hipLaunchKernelGGL((k_filter_pick<2, 1>), dim3(n_rows), dim3(64), 0, st, part, np, step, out, out_host, cn, stamp_next());
-    else              hipLaunchKernelGGL((k_filter_pick<3, 1>), dim3(n_rows), dim3(64), 0, st, part, np, step, out, out_host, cn, stamp_next());
+    if (xu <= 1)      hipLaunchKernelGGL((k_filter_pick<1, 1>), dim3(n_rows), dim3(64), 0, st, part, np, step, out, out_host, sp.base, sp.slot, cn);
+    else if (xu == 2) hipLaunchKernelGGL((k_filter_pick<2, 1>), dim3(n_rows), dim3(64), 0, st, part, np, step, out, out_host, sp.base, sp.slot, cn);
+    else              hipLaunchKernelGGL((k_filter_pick<3, 1>), dim3(n_rows), dim3(64), 0, st, part, np, step, out, out_host, sp.base, sp.slot, cn);
 }
 size_t filter_scratch_bytes(int n_rows) { return (size_t) std::max(n_rows * NB, FS_MAX_PARTS) * sizeof(Partial); }
 

@@ -61,6 +61,10 @@ inline int cu_count_x8() {
 // half a dozen DEPENDENT scalar-load round trips to the kernarg segment (~0.25-0.3 us each, cold in the scalar cache at every launch)
 // before its first vector load goes out — 1.7 us of a 5.8 us launch in k_qrows (in-kernel stamps, profiles/r05c_*).  Naming a field as an
 // asm input makes it live here, so the loads of everything named leave together and one wait covers them.
+// The hot kernels (k_front, k_mlp_pair, k_gemv1, k_xback, k_gemm, k_filter_pick) go one step further: the operands of their first
+// loads are plain leading parameters, which arrive in SGPRs with the wavefront (kernarg preload, csrc/Makefile: 13 - 14 dwords; a by-value
+// struct in front gets none), followed by the argument struct by value for everything else.  The launchers pass both from the same host
+// struct; tests/test_kernarg_preload.py holds the layouts.
 #if defined(__HIPCC__)
 #define WMI_ARG_NOW(x) asm volatile("" :: "s"(x))
 #endif
@@ -78,6 +82,10 @@ Stamp stamp_next();                                     // {base, slot++} or {nu
 int   stamp_count();
 #if defined(__HIPCC__)
 __device__ __forceinline__ unsigned long long stamp_t0(const unsigned long long * base) { return base ? wall_clock64() : 0ull; }
+// the first stamp of a kernel whose leading arguments are preloaded: `on` = (base != null) travels as a bit of a preloaded word (STAMP_ON_BIT
+// of its `dims`), so the kernel's first instructions do not wait for Stamp, which sits behind the preloaded dwords in the argument segment
+constexpr uint32_t STAMP_ON_BIT = 1u << 31;
+__device__ __forceinline__ unsigned long long stamp_t0_if(bool on) { return on ? wall_clock64() : 0ull; }
 __device__ __forceinline__ void stamp_end(unsigned long long * base, int slot, int widx, unsigned long long t0,
                                           unsigned long long tm1 = 0, unsigned long long tm2 = 0) {
     if (base && (threadIdx.x & 63) == 0 && widx < STAMP_WAVES) {
