@@ -1234,6 +1234,150 @@ int wmi_selftest_qkv_encoder(int device, int M, int S, int Tpad, int rows_per_ch
     return ok ? 0 : -3;
 }
 
+namespace {
+// the identity out projection of the decoder attention hooks: with no bias and a zero residual, EPI_F32_BIAS_RESID returns the f16 attention
+// row the prologue computed, exactly (one product by 1 and exact zeros in every f32 sum)
+std::vector<uint16_t> identity_f16(int S) {
+    std::vector<uint16_t> w((size_t) S * S, 0);
+    for (int i = 0; i < S; ++i) w[(size_t) i * S + i] = 0x3C00;
+    return w;
+}
+std::vector<unsigned char> sentinel_image(size_t n, bool f32, uint32_t sentinel) {
+    std::vector<unsigned char> pre(n * (f32 ? 4 : 2));
+    const uint16_t s16 = (uint16_t) sentinel;
+    for (size_t i = 0; i < n; ++i) { if (f32) memcpy(pre.data() + 4 * i, &sentinel, 4); else memcpy(pre.data() + 2 * i, &s16, 2); }
+    return pre;
+}
+}
+
+int wmi_selftest_attn_decoder(int device, int form, int n, int S, int H, int cap, int cache_rows, const int32_t * n_kv, const float * mask,
+                              int via_dev, int long_cache, int want_f32, const uint16_t * q, const uint16_t * kc, const uint16_t * vc,
+                              uint32_t sentinel, int out_rows, void * out) {
+    // everything the product cannot launch is refused before the device is touched
+    if (form < 0 || form > 2 || n < 1 || H < 1 || S != 64 * H || S > 1280 || cap < 1 || cap > 448 || out_rows < n || !q || !kc || !vc || !out || !n_kv) return -1;
+    if (form == 0) {
+        if (n > cap || cache_rows != 1 || !mask || long_cache || n_kv[0] < n || n_kv[0] > cap) return -1;
+    } else {
+        if (n > 16 || cache_rows != n || via_dev) return -1;
+        int longest = 0;
+        for (int r = 0; r < n; ++r) { if (n_kv[r] < 1 || n_kv[r] > cap) return -1; longest = std::max(longest, n_kv[r]); }
+        if (long_cache && longest <= 64) return -1;           // the long form is launched where the host knows a row has more than 64 cells
+    }
+    if (form == 2 && (!want_f32 || long_cache)) return -1;
+    constexpr int STEP_WORDS = (int) (sizeof(k::DecStep) / 4);   // n_kv of row r at word r * STEP_WORDS, as the rows' step records hold it
+    k::GemvArgs g{};
+    if (form == 2) {                                           // as device.cpp (one row) and batch.cpp (lock-step rows) set the out projection up
+        g.n = n; g.K = S; g.N = S; g.epi = k::EPI_F32_BIAS_RESID; g.ldc = S; g.ldr = S; g.S = S; g.sa_cap = cap;
+        if (n > 1) { g.lanes = 1; g.step_stride = STEP_WORDS; g.cache_row_stride = (int64_t) cap * S; }
+        if (n > 1 && !k::gemv_rows_take_self_attention(g)) return -1;
+    }
+    if (!HIP_OK(hipSetDevice(device))) return -2;
+    const size_t n_q = (size_t) n * S, n_c = (size_t) cache_rows * cap * S, n_out = (size_t) out_rows * S, out_bytes = n_out * (want_f32 ? 4 : 2);
+    const int mask_ld = form == 0 ? n_kv[0] : 0;
+    std::vector<int32_t> steps((size_t) n * STEP_WORDS, 1);
+    for (int r = 0; r < (form == 0 ? 1 : n); ++r) steps[(size_t) r * STEP_WORDS] = n_kv[r];
+    const std::vector<unsigned char> pre = sentinel_image(n_out, want_f32 != 0, sentinel);
+    AlignSelf b;
+    __half * d_q = (__half *) b.get(n_q * 2), * d_k = (__half *) b.get(n_c * 2), * d_v = (__half *) b.get(n_c * 2);
+    unsigned char * d_o = (unsigned char *) b.get(out_bytes);
+    int32_t * d_n = (int32_t *) b.get(steps.size() * 4);
+    float * d_m = form == 0 ? (float *) b.get((size_t) n * mask_ld * 4) : nullptr;
+    __half * d_w = nullptr; float * d_r = nullptr;
+    if (!d_q || !d_k || !d_v || !d_o || !d_n || (form == 0 && !d_m) || !HIP_OK(hipStreamCreate(&b.st))) return -3;
+    if (!HIP_OK(hipMemcpy(d_q, q, n_q * 2, hipMemcpyHostToDevice)) || !HIP_OK(hipMemcpy(d_k, kc, n_c * 2, hipMemcpyHostToDevice)) ||
+        !HIP_OK(hipMemcpy(d_v, vc, n_c * 2, hipMemcpyHostToDevice)) || !HIP_OK(hipMemcpy(d_o, pre.data(), out_bytes, hipMemcpyHostToDevice)) ||
+        !HIP_OK(hipMemcpy(d_n, steps.data(), steps.size() * 4, hipMemcpyHostToDevice))) return -3;
+    if (form == 0 && !HIP_OK(hipMemcpy(d_m, mask, (size_t) n * mask_ld * 4, hipMemcpyHostToDevice))) return -3;
+    if (form == 2) {
+        const std::vector<uint16_t> w = identity_f16(S);
+        d_w = (__half *) b.get(w.size() * 2); d_r = (float *) b.get(n_q * 4);
+        if (!d_w || !d_r || !HIP_OK(hipMemcpy(d_w, w.data(), w.size() * 2, hipMemcpyHostToDevice)) || !HIP_OK(hipMemset(d_r, 0, n_q * 4))) return -3;
+    }
+    __half * o16 = want_f32 ? nullptr : (__half *) d_o; float * o32 = want_f32 ? (float *) d_o : nullptr;
+    if (form == 0)      k::attn_decoder(d_q, n, S, H, d_k, d_v, via_dev ? 0 : n_kv[0], d_m, mask_ld, o16, b.st, via_dev ? d_n : nullptr, via_dev ? cap : 0, o32);
+    else if (form == 1) k::self_attn_rows(d_q, n, S, d_k, d_v, (int64_t) cap * S, d_n, STEP_WORDS, cap, o16, b.st, o32, long_cache != 0);
+    else {
+        g.sa_q = d_q; g.sa_k = d_k; g.sa_v = d_v; g.sa_nkv = d_n; g.W = d_w; g.C = d_o; g.resid = d_r;
+        k::gemv(g, b.st);
+    }
+    if (!HIP_OK(hipStreamSynchronize(b.st)) || !HIP_OK(hipGetLastError()) || !HIP_OK(hipMemcpy(out, d_o, out_bytes, hipMemcpyDeviceToHost))) return -3;
+    return 0;
+}
+
+int wmi_selftest_attn_cross(int device, int form, int consumer, int n, int S, int H, int T, int kv_rows, const int32_t * row_lens, int want_f32,
+                            int lanes, const void * q, float qscale, const uint16_t * kc, const uint16_t * vc, uint32_t sentinel, int out_rows,
+                            void * out, float * pmax, float * part_l, float * part_o, int * info) {
+    if (form < 0 || form > 2 || consumer < 0 || consumer > 1 || n < 1 || n > 16 || H < 1 || S != 64 * H || S > 1280 || T < 1 || T > 1500) return -1;
+    if ((kv_rows != 1 && kv_rows != n) || out_rows < n || !q || !kc || !vc || !out || !info || !(qscale == qscale) || std::isinf(qscale)) return -1;
+    if (form != 1 && consumer != 0) return -1;
+    if (form != 0 && (!pmax || !part_l || !part_o)) return -1;
+    if (consumer == 1 && (!want_f32 || (lanes ? n < 2 : n > 8))) return -1;
+    if (consumer == 0 && lanes) return -1;
+    if (lanes && n > 8 && S > 512 && (S % 128) != 0) return -1;      // neither the one-row kernels per row, nor the matrix cores, nor k_gemv's eight rows
+    k::RowLens lens{};
+    if (row_lens) {
+        if (form == 0 || kv_rows != n) return -1;
+        int longest = 0;
+        for (int i = 0; i < n; ++i) { if (row_lens[i] < 1 || row_lens[i] > T) return -1; lens.t[i] = row_lens[i]; longest = std::max(longest, row_lens[i]); }
+        if (longest != T || !k::attn_cross_takes_row_lens(H, T)) return -1;
+        lens.n = n;
+    }
+    if (!HIP_OK(hipSetDevice(device))) return -2;
+    const size_t n_q = (size_t) n * S, n_c = (size_t) kv_rows * T * S, n_out = (size_t) out_rows * S, out_bytes = n_out * (want_f32 ? 4 : 2);
+    const size_t n_scr = k::attn_cross_scratch_floats(n, H, T);
+    const std::vector<unsigned char> pre = sentinel_image(n_scr, true, 0x7FC5A5A5u);      // the scratch starts as f32 NaNs whatever the output type: a partial read unwritten is loud
+    const std::vector<unsigned char> pre_out = sentinel_image(n_out, want_f32 != 0, sentinel);
+    const int64_t kv_stride = kv_rows > 1 ? (int64_t) T * S : 0;
+    AlignSelf b;
+    __half * d_k = (__half *) b.get(n_c * 2), * d_v = (__half *) b.get(n_c * 2);
+    unsigned char * d_o = (unsigned char *) b.get(out_bytes);
+    float * d_scr = (float *) b.get(n_scr * 4);
+    if (!d_k || !d_v || !d_o || !d_scr || !HIP_OK(hipStreamCreate(&b.st))) return -3;
+    if (!HIP_OK(hipMemcpy(d_k, kc, n_c * 2, hipMemcpyHostToDevice)) || !HIP_OK(hipMemcpy(d_v, vc, n_c * 2, hipMemcpyHostToDevice)) ||
+        !HIP_OK(hipMemcpy(d_o, pre_out.data(), out_bytes, hipMemcpyHostToDevice)) || !HIP_OK(hipMemcpy(d_scr, pre.data(), n_scr * 4, hipMemcpyHostToDevice))) return -3;
+    __half * o16 = want_f32 ? nullptr : (__half *) d_o; float * o32 = want_f32 ? (float *) d_o : nullptr;
+    const float * po = nullptr, * pl = nullptr, * pm = nullptr; int ns = 0;
+    const k::XattnPlan plan = k::attn_cross_plan(n, H, T, d_scr);
+    if (form == 2) {
+        // the projection inside the score kernel, made to return a known query: LN gain 0 and bias 0 (the normalised row is 0 whatever x
+        // holds), W_cq = 0, so q = f16((0 + bias) * qscale) with bias = the caller's f32 row, the same for every row of the launch
+        float * d_x = (float *) b.get(n_q * 4), * d_g = (float *) b.get((size_t) S * 4), * d_lb = (float *) b.get((size_t) S * 4), * d_bq = (float *) b.get((size_t) S * 4);
+        __half * d_wq = (__half *) b.get((size_t) S * S * 2);
+        if (!d_x || !d_g || !d_lb || !d_bq || !d_wq || !HIP_OK(hipMemset(d_x, 0, n_q * 4)) || !HIP_OK(hipMemset(d_g, 0, (size_t) S * 4)) ||
+            !HIP_OK(hipMemset(d_lb, 0, (size_t) S * 4)) || !HIP_OK(hipMemset(d_wq, 0, (size_t) S * S * 2)) ||
+            !HIP_OK(hipMemcpy(d_bq, q, (size_t) S * 4, hipMemcpyHostToDevice))) return -3;
+        k::attn_cross_qsplit_partials(d_x, d_g, d_lb, 1e-5f, d_wq, d_bq, qscale, n, S, H, d_k, d_v, T, d_scr, &po, &pl, &pm, &ns, b.st, kv_stride,
+                                      row_lens ? &lens : nullptr);
+    } else {
+        __half * d_q = (__half *) b.get(n_q * 2);
+        if (!d_q || !HIP_OK(hipMemcpy(d_q, q, n_q * 2, hipMemcpyHostToDevice))) return -3;
+        if (form == 0) k::attn_cross_split(d_q, n, S, H, d_k, d_v, T, d_scr, o16, b.st, kv_stride, o32);
+        else k::attn_cross_split_partials(d_q, n, S, H, d_k, d_v, T, d_scr, &po, &pl, &pm, &ns, b.st, kv_stride, row_lens ? &lens : nullptr);
+    }
+    if (form != 0) {
+        if (!po || !pl || ns != plan.ns) return -3;
+        if (consumer == 0) k::attn_cross_combine(po, pl, pm, ns, n, S, H, o16, b.st, o32);
+        else {
+            const std::vector<uint16_t> w = identity_f16(S);
+            __half * d_w = (__half *) b.get(w.size() * 2); float * d_r = (float *) b.get(n_q * 4);
+            if (!d_w || !d_r || !HIP_OK(hipMemcpy(d_w, w.data(), w.size() * 2, hipMemcpyHostToDevice)) || !HIP_OK(hipMemset(d_r, 0, n_q * 4))) return -3;
+            k::GemvArgs g{};                                  // as device.cpp / device_q.cpp (rows) and batch.cpp (lock-step rows) set the out projection up
+            g.comb_o = po; g.comb_l = pl; g.comb_m = pm; g.comb_ns = ns; g.n = n; g.K = S; g.N = S; g.W = d_w; g.epi = k::EPI_F32_BIAS_RESID;
+            g.C = d_o; g.ldc = S; g.resid = d_r; g.ldr = S; g.S = S; g.eps = 1e-5f;
+            if (lanes) g.lanes = 1;
+            k::gemv(g, b.st);
+        }
+    }
+    if (!HIP_OK(hipStreamSynchronize(b.st)) || !HIP_OK(hipGetLastError()) || !HIP_OK(hipMemcpy(out, d_o, out_bytes, hipMemcpyDeviceToHost))) return -3;
+    info[0] = plan.ns; info[1] = plan.fused ? 1 : 0;
+    if (form != 0) {
+        const size_t np = (size_t) n * H * plan.ns;
+        if (!HIP_OK(hipMemcpy(pmax, plan.pmax, np * 4, hipMemcpyDeviceToHost)) || !HIP_OK(hipMemcpy(part_l, plan.part_l, np * 4, hipMemcpyDeviceToHost)) ||
+            !HIP_OK(hipMemcpy(part_o, plan.part_o, np * 64 * 4, hipMemcpyDeviceToHost))) return -3;
+    }
+    return 0;
+}
+
 static void gemm_plan_out(const k::GemmPlan & p, int * out) {
     const int v[10] = {p.kernel, p.bm, p.bn, p.waves, p.ring, p.ring_w, p.dma, p.orient, p.ks, p.epi};
     for (int i = 0; i < 10; ++i) out[i] = v[i];

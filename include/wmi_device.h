@@ -419,6 +419,35 @@ WHISPER_API int wmi_selftest_attn_encoder(int device, int B, int T, int Tpad, in
  * touched: S % 64, Tpad % 64, rows_per_chunk > Tpad or not dividing M, out_rows < M); -2 / -3 on a device error. */
 WHISPER_API int wmi_selftest_qkv_encoder(int device, int M, int S, int Tpad, int rows_per_chunk, const uint16_t * xn, const uint16_t * W,
                                          const float * bias, uint32_t sentinel, int out_rows, uint16_t * q, uint16_t * k, uint16_t * vt);
+/* The decoder's self-attention kernels on caller operands (tests/test_gpu_attn_decoder.py; no context).  All host pointers; q [n][S] and the
+ * caches kc, vc [cache_rows][cap][S] are f16 bit patterns, uploaded as given.  `out` — [out_rows][S], f16 or, with want_f32, f32 — is filled
+ * with `sentinel` (its low 16 bits for f16) first, one launch on one stream, all of `out` comes back.
+ *   form 0   attn_decoder: n rows against ONE cache (cache_rows = 1) of n_kv[0] cells with the additive mask [n][n_kv[0]] (f32, as given);
+ *            via_dev: n_kv travels through device memory with n_kv_max = cap (the graph-replay route)
+ *   form 1   self_attn_rows: row r against its own cache (cache_rows = n <= 16, cache_row_stride = cap S) with n_kv[r] cells, read from
+ *            step records sizeof(DecStep) apart; long_cache: the four-wavefront form (some row must have more than 64 cells)
+ *   form 2   gemv with the sa_* prologue and EPI_F32_BIAS_RESID as the out projection is set up (one row: device.cpp; n rows: `lanes`, where
+ *            gemv_rows_take_self_attention says yes), W_o = identity, no bias, a zero residual: the f32 result (want_f32 must be set) IS
+ *            the f16 attention row
+ * Returns 0; -1 for what the product never launches (S != 64 H, S > 1280, cap > 448, a cell count outside [1, cap], form 0: n > cap or
+ * n_kv < n; forms 1, 2: n > 16, ...) — decided before the device is touched; -2 / -3 on a device error. */
+WHISPER_API int wmi_selftest_attn_decoder(int device, int form, int n, int S, int H, int cap, int cache_rows, const int32_t * n_kv, const float * mask,
+                                          int via_dev, int long_cache, int want_f32, const uint16_t * q, const uint16_t * kc, const uint16_t * vc,
+                                          uint32_t sentinel, int out_rows, void * out);
+/* The decoder's cross-attention on caller operands: kc, vc [kv_rows][T][S] f16 (kv_rows = 1, or n with kv_row_stride = T S), `out` as above.
+ *   form 0   attn_cross_split (q [n][S] f16)
+ *   form 1   attn_cross_split_partials, then consumer 0 = attn_cross_combine, 1 = gemv with comb_* and an identity out projection as above
+ *            (want_f32; lanes = 0: one row takes k_gemv1, 2 .. 8 rows k_gemv; lanes = 1: lock-step rows — the one-row kernel per row up to
+ *            S = 512, k_rows_mfma above)
+ *   form 2   attn_cross_qsplit_partials with LN gain 0, W_cq = 0 and q [S] f32 as the projection's bias — every row's query is
+ *            f16(q * qscale) — then attn_cross_combine
+ * row_lens (forms 1, 2; NULL or n entries in [1, T], the largest equal to T, kv_rows = n): a length per row, as lock-step chunks have.  The
+ * scratch starts as f32 NaNs (0x7FC5A5A5), whatever `sentinel` and the output type.  pmax, part_l [n][H][ns] and part_o [n][H][ns][64] (forms 1, 2; room for ns = 16) take the raw partials,
+ * info[2] = {ns, 1 one-launch form / 0 two launches (WMI_XATTN_TWO_PASS)}.  Returns as above (T <= 1500, n <= 16, per-row lengths need the
+ * one-launch form, ...). */
+WHISPER_API int wmi_selftest_attn_cross(int device, int form, int consumer, int n, int S, int H, int T, int kv_rows, const int32_t * row_lens,
+                                        int want_f32, int lanes, const void * q, float qscale, const uint16_t * kc, const uint16_t * vc,
+                                        uint32_t sentinel, int out_rows, void * out, float * pmax, float * part_l, float * part_o, int * info);
 /* gemm()'s decision without a launch (host only, no device): the plan for epilogue `epi` (kernels.h Epi: 0 F16_BIAS, 1 F16_BIAS_GELU,
  * 2 F32_BIAS_RESID, 3 CONV2, 4 QKV_ENC, 5 QKV_DEC, 6 CROSS_KV, 7 Q_SCALED) at (M, N, K), split width S, on a device of n_cu compute units,
  * with none of the WMI_GEMM_* lab switches.  out[10] = {kernel (1 k_gemm, 8 k_gemm8), BM, BN, wavefronts, ring depth (k_gemm8: of the A
