@@ -201,9 +201,15 @@ class wmi_long_piece(C.Structure):  # include/wmi_device.h: one piece of the las
                 ("i_segment", C.c_int32), ("n_segments", C.c_int32)]
 
 
+class wmi_grammar_status(C.Structure):  # include/wmi_device.h: the counters and capacities of the grammar's device route (wmi_set_grammar_device)
+    _fields_ = [("steps_device", C.c_int32), ("rows_host", C.c_int32), ("cap_stacks", C.c_int32), ("cap_depth", C.c_int32),
+                ("cap_words", C.c_int32), ("reject_us", C.c_float)]
+
+
 NO_SPEECH_OFF, NO_SPEECH_REPORT, NO_SPEECH_DROP, NO_SPEECH_GATE = range(4)       # wmi_set_no_speech modes
 WINDOW_EMITTED, WINDOW_DROPPED, WINDOW_GATED = range(3)                          # wmi_window.outcome
 TOKEN_DTW_OFF, TOKEN_DTW_ON = range(2)                                           # wmi_set_token_dtw modes
+GRAMMAR_HOST, GRAMMAR_DEVICE = range(2)                                          # wmi_set_grammar_device modes
 
 
 class whisper_model_loader(C.Structure):  # W/whisper.h:108-114

@@ -892,6 +892,110 @@ int wmi_process_logits(struct whisper_context * ctx, struct whisper_full_params 
     return nv;
 }
 
+// the decoder whose grammar state follows `params` and a token history, exactly as wmi_process_logits builds it
+static Grammar grammar_after(whisper_context & ctx, const whisper_full_params & params, const whisper_token * hist, int n_hist) {
+    Grammar g = params.grammar_rules ? grammar_init(params.grammar_rules, params.n_grammar_rules, params.i_start_rule) : Grammar{};
+    for (int i = 0; i < n_hist; ++i) grammar_accept_token(ctx, g, hist[i]);
+    return g;
+}
+
+int wmi_selftest_grammar(struct whisper_context * ctx, struct whisper_full_params params, int where, int n_rows, const whisper_token * hist,
+                         const int * n_hist, uint8_t * reject_out, uint32_t * overflow_out) {
+    if (!ctx || !n_hist || !reject_out || !overflow_out || where < 0 || where > 1 || n_rows < 1 || n_rows > 8 || !params.grammar_rules) return -1;
+    for (int r = 0; r < n_rows; ++r) if (n_hist[r] < 0 || (n_hist[r] > 0 && !hist)) return -1;
+    const Vocab & v = ctx->model.vocab;
+    const int NV = v.n_vocab;
+    std::vector<Grammar> gs;
+    for (int r = 0; r < n_rows; ++r) { gs.push_back(grammar_after(*ctx, params, hist, n_hist[r])); hist += n_hist[r]; }
+    const GrammarFlat gf = grammar_flatten(gs[0]);
+    std::vector<ge::RowState> states(n_rows);
+    memset(reject_out, 0, (size_t) n_rows * NV);
+    for (int r = 0; r < n_rows; ++r) overflow_out[r] = (gf.ok && grammar_row_state(gs[r], gf, states[r])) ? 0u : 1u;
+    if (where == 0) {                                     // grammar_eval.h on the host: no device, none touched
+        std::vector<uint8_t> bytes; std::vector<uint32_t> off;
+        grammar_vocab_flat(v, bytes, off);
+        for (int r = 0; r < n_rows; ++r)
+            if (!overflow_out[r] && !grammar_eval_host(gf, bytes, off, states[r], reject_out + (size_t) r * NV, NV)) {
+                overflow_out[r] = 1u; memset(reject_out + (size_t) r * NV, 0, (size_t) NV);
+            }
+        return 0;
+    }
+    if (!ctx->state) return -1;
+    CtxScope lk(ctx);
+    if (!compute_ready(*ctx, __func__)) return -2;
+    (void) hipSetDevice(ctx->device);
+    if (!grammar_device_begin(*ctx, gf)) return -3;
+    DeviceState & d = ctx->state->dev;
+    if (d.gram.n_rules == 0) return 0;                   // nothing the kernel could evaluate: every row reports overflow
+    for (int r = 0; r < n_rows; ++r) if (overflow_out[r]) states[r].n_stacks = -1;
+    uint32_t * d_over = nullptr;
+    if (!HIP_OK(hipMalloc(&d_over, 8 * sizeof(uint32_t)))) return -3;
+    hipStream_t s = d.stream;
+    const k::GrammarDev gd{ (const ge::Elem *) d.gram.rules, (const uint32_t *) (d.gram.rules + (size_t) d.gram.n_elems * sizeof(ge::Elem)), d.gram.n_rules,
+                            d.gram.vbytes, d.gram.voff, v.eot };
+    std::vector<uint32_t> over(8, 0);
+    bool ok = HIP_OK(hipMemsetAsync(d_over, 0, 8 * sizeof(uint32_t), s)) && HIP_OK(hipMemsetAsync(d.gram.reject, 0, (size_t) n_rows * NV, s)) &&
+              HIP_OK(hipMemcpyAsync(d.gram.states, states.data(), (size_t) n_rows * sizeof(ge::RowState), hipMemcpyHostToDevice, s));
+    hipEvent_t ev[2] = { nullptr, nullptr };             // the launch's own time (wmi_grammar_status: reject_us)
+    ok = ok && HIP_OK(hipEventCreate(&ev[0])) && HIP_OK(hipEventCreate(&ev[1]));
+    if (ok) {
+        (void) hipEventRecord(ev[0], s);
+        k::grammar_reject(gd, d.gram.states, n_rows, NV, d.gram.reject, d_over, s);
+        (void) hipEventRecord(ev[1], s);
+        ok = HIP_OK(hipGetLastError()) && HIP_OK(hipMemcpyAsync(reject_out, d.gram.reject, (size_t) n_rows * NV, hipMemcpyDeviceToHost, s)) &&
+             HIP_OK(hipMemcpyAsync(over.data(), d_over, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, s)) && HIP_OK(hipStreamSynchronize(s));
+    }
+    float ms = 0.0f;
+    if (ok && HIP_OK(hipEventElapsedTime(&ms, ev[0], ev[1]))) ctx->state->gram_reject_us = 1e3f * ms;
+    for (hipEvent_t e : ev) if (e) (void) hipEventDestroy(e);
+    (void) hipFree(d_over);
+    if (!ok) return -3;
+    for (int r = 0; r < n_rows; ++r) if (over[r]) { overflow_out[r] = 1u; memset(reject_out + (size_t) r * NV, 0, (size_t) NV); }
+    return 0;
+}
+
+// the product's grammar sampling route on caller logits: the rows of logits go where decode() leaves them (DeviceState::logits), the
+// step filters and the grammar states come from `params` and the histories, sample_rows_grammar_device does the rest
+int wmi_selftest_grammar_sample(struct whisper_context * ctx, struct whisper_full_params params, int mode, int n_rows, const float * logits,
+                                const whisper_token * hist, const int * n_hist, const int * has_ts, const int * seek_delta, float temperature,
+                                const double * u, int k, int tid_default, whisper_token_data * out) {
+    if (!ctx || !ctx->state || !out || !logits || !n_hist || !has_ts || !seek_delta || (mode != 0 && mode != 2) || !params.grammar_rules ||
+        params.n_grammar_rules == 0) return -1;
+    if (n_rows < 1 || n_rows > 8 || (mode == 2 && (k < 1 || k > 8 || !u))) return -1;
+    if (mode == 0) k = 1;
+    for (int r = 0; r < n_rows; ++r) if (n_hist[r] < 0 || (n_hist[r] > 0 && !hist)) return -1;
+    const Vocab & v = ctx->model.vocab; const HParams & hp = ctx->model.hp;
+    const int NV = v.n_vocab;
+    CtxScope lk(ctx);
+    if (!compute_ready(*ctx, __func__)) return -2;
+    try {
+        (void) hipSetDevice(ctx->device);
+        DeviceState & d = ctx->state->dev;
+        if (d.logits_rows_cap < n_rows) return -1;
+        std::vector<Grammar> gs; std::vector<StepFilter> fl; std::vector<const Grammar *> gr; std::vector<int> rows;
+        for (int r = 0; r < n_rows; ++r) {
+            Decoder dec;
+            for (int i = 0; i < n_hist[r]; ++i) dec.sequence.tokens.push_back(whisper_token_data{ hist[i], 0, 0.f, 0.f, 0.f, 0.f, -1, -1, 0.f });
+            dec.has_ts = has_ts[r] != 0; dec.seek_delta = seek_delta[r];
+            fl.push_back(make_step_filter(v, hp, params, dec));
+            gs.push_back(grammar_after(*ctx, params, hist, n_hist[r]));
+            hist += n_hist[r]; rows.push_back(r);
+        }
+        for (int r = 0; r < n_rows; ++r) gr.push_back(&gs[r]);
+        const GrammarFlat gf = grammar_flatten(gs[0]);
+        if (!upload_static_ban(*ctx, params) || !grammar_device_begin(*ctx, gf)) return -3;
+        if (!HIP_OK(hipMemcpyAsync(d.logits, logits, (size_t) n_rows * NV * 4, hipMemcpyHostToDevice, d.stream)) || !HIP_OK(hipStreamSynchronize(d.stream))) return -3;
+        std::vector<whisper_token_data> res((size_t) n_rows * k);
+        if (!sample_rows_grammar_device(*ctx, gf, gr.data(), params.grammar_penalty, fl.data(), rows.data(), n_rows, temperature, k, mode == 0, u, tid_default,
+                                        res.data())) return -3;
+        for (size_t i = 0; i < res.size(); ++i) out[i] = res[i];
+        return 0;
+    } catch (const std::exception & e) {
+        WMI_ERR("%s: %s\n", __func__, e.what());
+        return -3;
+    }
+}
+
 // worker-pool self-test (no device needed): reps jobs of n_tasks tasks, each task adds its index + 1 once; returns the total
 int64_t wmi_selftest_pool(int n_tasks, int reps) {
     std::vector<int> hits((size_t) std::max(n_tasks, 0), 0);

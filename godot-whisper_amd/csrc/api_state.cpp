@@ -289,6 +289,22 @@ int wmi_set_no_speech(struct whisper_context * ctx, int mode) {
     ctx->no_speech_mode = mode < 0 ? 0 : (mode > 3 ? 3 : mode);
     return prev;
 }
+// the grammar on the device (wmi_device.h)
+int wmi_set_grammar_device(struct whisper_context * ctx, int mode) {
+    if (!ctx) return -2;
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    const int prev = ctx->grammar_device_mode;
+    ctx->grammar_device_mode = mode != 0 ? 1 : 0;
+    return prev;
+}
+int wmi_grammar_status(struct whisper_context * ctx, struct wmi_grammar_status * out) {
+    if (!ctx || !out) return -2;
+    out->steps_device = ctx->state ? ctx->state->gram_steps_dev : 0;
+    out->rows_host = ctx->state ? ctx->state->gram_rows_host : 0;
+    out->reject_us = ctx->state ? ctx->state->gram_reject_us : 0.0f;
+    out->cap_stacks = ge::MAX_STACKS; out->cap_depth = ge::MAX_DEPTH; out->cap_words = ge::WS_WORDS;
+    return 0;
+}
 // token times by DTW (wmi_device.h)
 int wmi_set_token_dtw(struct whisper_context * ctx, int mode, const int32_t * layer_head, int n_pairs) {
     if (!ctx) return -2;

@@ -827,7 +827,7 @@ int full_batch(whisper_context & ctx, whisper_full_params params, const float * 
                     if (w == 0) rc = run_alone(c);
                     else {
                         for (auto & dec : wc.state->decoders) dec.rng = std::mt19937(0);
-                        wc.no_speech_mode = nsm; wc.token_dtw_mode = ctx.token_dtw_mode; wc.dtw_pairs = ctx.dtw_pairs;
+                        wc.no_speech_mode = nsm; wc.token_dtw_mode = ctx.token_dtw_mode; wc.dtw_pairs = ctx.dtw_pairs; wc.grammar_device_mode = ctx.grammar_device_mode;
                         rc = full(wc, params_of(c), on_device ? nullptr : pcm[c], on_device ? pcm[c] : nullptr, n_samples[c]);
                         if (rc == 0) { ctx.batch->results[c] = std::move(wc.state->result_all); ctx.batch->windows[c] = std::move(wc.state->windows); keep_lang(c, *wc.state); }
                         wc.state->result_all.clear(); wc.state->windows.clear();
@@ -925,7 +925,7 @@ int full_batch(whisper_context & ctx, whisper_full_params params, const float * 
                     whisper_context & wc = g == 0 ? ctx : *ctx.batch->replicas[g - 1];
                     (void) hipSetDevice(ctx.device);
                     if (g > 0 && wc.batch) wc.batch->groups_wanted = 1;
-                    wc.no_speech_mode = nsm; wc.token_dtw_mode = ctx.token_dtw_mode; wc.dtw_pairs = ctx.dtw_pairs;
+                    wc.no_speech_mode = nsm; wc.token_dtw_mode = ctx.token_dtw_mode; wc.dtw_pairs = ctx.dtw_pairs; wc.grammar_device_mode = ctx.grammar_device_mode;
                     t_in_group = true;
                     struct Off { ~Off() { t_in_group = false; } } off;
                     const int cnt = c0[g + 1] - c0[g];

@@ -215,6 +215,9 @@ void destroy_state(State * st) {
     if (d.filter_scratch) (void) hipFree(d.filter_scratch);
     if (d.draw_scratch) (void) hipFree(d.draw_scratch);
     if (d.draw_host) (void) hipHostFree(d.draw_host);
+    dfree(d.gram.vbytes); dfree(d.gram.voff); dfree(d.gram.rules); dfree(d.gram.states); dfree(d.gram.reject);
+    if (d.gram.scratch) (void) hipFree(d.gram.scratch);
+    if (d.gram.host) (void) hipHostFree(d.gram.host);
     if (d.step_host) (void) hipHostFree(d.step_host);
     if (d.sample_host) (void) hipHostFree(d.sample_host);
     if (d.nsp_scratch) (void) hipFree(d.nsp_scratch);
@@ -920,6 +923,110 @@ bool sample_rows_device(whisper_context & ctx, const StepFilter * f, const int *
         k::filter_draw(d.logits + (size_t) rows[r] * NV, d.ban_dev, ds + r, du + r * k, k, dout + r * k, d.draw_scratch, s, 1, tid_default);
     k::SampleOut * hout = (k::SampleOut *) ((char *) d.draw_host + OFF_OUT);
     HIP_TRY(hipStreamSynchronize(s));
+    for (int i = 0; i < n_rows * k; ++i)
+        out[i] = whisper_token_data{ hout[i].id, hout[i].tid, hout[i].p, hout[i].plog, hout[i].pt, hout[i].ptsum, -1, -1, 0.0f };
+    st.t_sample_us += time_us() - t0; st.n_sample += n_rows;
+    return true;
+}
+
+// ---- the grammar on the device (wmi_set_grammar_device)
+bool grammar_device_begin(whisper_context & ctx, const GrammarFlat & gf) {
+    State & st = *ctx.state; DeviceState & d = st.dev; const Vocab & v = ctx.model.vocab;
+    DeviceState::GrammarBufs & g = d.gram;
+    hipStream_t s = d.stream;
+    if (!g.host) {
+        std::vector<uint8_t> bytes; std::vector<uint32_t> off;
+        grammar_vocab_flat(v, bytes, off);
+        if (!dalloc(g.vbytes, bytes.size()) || !dalloc(g.voff, off.size()) || !dalloc(g.states, 8) || !dalloc(g.reject, (size_t) 8 * v.n_vocab) ||
+            !HIP_OK(hipMalloc(&g.scratch, k::grammar_sample_scratch_bytes(8)))) return false;
+        HIP_TRY(hipMemcpyAsync(g.vbytes, bytes.data(), bytes.size(), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(g.voff, off.data(), off.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemsetAsync(g.reject, 0, (size_t) 8 * v.n_vocab, s));          // (the bytes from eot on stay 0)
+        HIP_TRY(hipStreamSynchronize(s));
+        if (!HIP_OK(hipHostMalloc(&g.host, 8 * sizeof(ge::RowState) + 8 * sizeof(uint32_t), hipHostMallocDefault))) return false;
+    }
+    g.n_rules = 0; g.n_elems = 0;
+    if (!gf.ok) return true;
+    const size_t eb = gf.elems.size() * sizeof(ge::Elem), ob = gf.rule_off.size() * sizeof(uint32_t);
+    if (eb + ob > g.rules_cap) {
+        dfree(g.rules);
+        g.rules_cap = 0;
+        if (!dalloc(g.rules, eb + ob)) return false;
+        g.rules_cap = eb + ob;
+    }
+    HIP_TRY(hipMemcpyAsync(g.rules, gf.elems.data(), eb, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(g.rules + eb, gf.rule_off.data(), ob, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    g.n_rules = (int) gf.rule_off.size() - 1; g.n_elems = (int) gf.elems.size();
+    return true;
+}
+
+bool sample_rows_grammar_device(whisper_context & ctx, const GrammarFlat & gf, const Grammar * const * gr, float penalty, const StepFilter * f,
+                                const int * rows, int n_rows, float temperature, int k, bool best, const double * u, int tid_default,
+                                whisper_token_data * out) {
+    State & st = *ctx.state; DeviceState & d = st.dev; const Vocab & v = ctx.model.vocab;
+    DeviceState::GrammarBufs & g = d.gram;
+    if (best) k = 1;
+    if (n_rows < 1 || n_rows > 8 || k < 1 || k > 8 || !g.host || (!best && !u)) return false;
+    const int64_t t0 = time_us();
+    constexpr size_t OFF_U = 8 * sizeof(k::DecStep), OFF_OUT = OFF_U + 64 * sizeof(double), TOTAL = OFF_OUT + 64 * sizeof(k::SampleOut);
+    if (!d.draw_host) {
+        if (!HIP_OK(hipHostMalloc(&d.draw_host, TOTAL, hipHostMallocDefault)) ||
+            !HIP_OK(hipMalloc(&d.draw_scratch, k::filter_draw_scratch_bytes(8)))) return false;
+    }
+    hipStream_t s = d.stream;
+    const int NV = v.n_vocab;
+    int space_id = -1; { auto sp = v.token_to_id.find(" "); if (sp != v.token_to_id.end()) space_id = sp->second; }
+    k::DecStep * hs = (k::DecStep *) d.draw_host; double * hu = (double *) ((char *) d.draw_host + OFF_U);
+    for (int r = 0; r < n_rows; ++r) {
+        memset(&hs[r], 0, sizeof(k::DecStep));
+        hs[r].flags = (f[r].ban_blank ? 1 : 0) | (f[r].last_ts ? 2 : 0) | (f[r].penult_ts ? 4 : 0);
+        hs[r].space_id = space_id; hs[r].eot = v.eot; hs[r].beg = v.beg; hs[r].n_vocab = NV;
+        hs[r].ts_floor_end = f[r].ts_floor_end; hs[r].ts_initial_start = f[r].ts_initial_start;
+        hs[r].temperature = temperature > 0.0f ? temperature : 0.0f;
+        for (int c = 0; c < k; ++c) hu[r * k + c] = best ? 0.0 : u[r * k + c];
+    }
+    // the rows' parse states; a state over the capacities (or a grammar the flat form does not serve) takes the host's reject set
+    ge::RowState * hstate = (ge::RowState *) g.host; volatile uint32_t * hover = (volatile uint32_t *) (hstate + 8);
+    std::vector<uint8_t> mask;
+    auto host_row = [&](int r) {
+        mask.resize(NV);
+        grammar_reject_mask(ctx, *gr[r], mask.data());
+        st.gram_rows_host++;
+        return HIP_OK(hipMemcpyAsync(g.reject + (size_t) r * NV, mask.data(), (size_t) NV, hipMemcpyHostToDevice, s)) && HIP_OK(hipStreamSynchronize(s));
+    };
+    int n_dev = 0;
+    for (int r = 0; r < n_rows; ++r) {
+        hover[r] = 0;
+        if (g.n_rules > 0 && grammar_row_state(*gr[r], gf, hstate[r])) ++n_dev;
+        else { hstate[r].n_stacks = -1; if (!host_row(r)) return false; }
+    }
+    const k::DecStep * ds = (const k::DecStep *) d.draw_host; const double * du = (const double *) ((char *) d.draw_host + OFF_U);
+    k::SampleOut * dout = (k::SampleOut *) ((char *) d.draw_host + OFF_OUT);
+    if (n_dev > 0) {
+        HIP_TRY(hipMemcpyAsync(g.states, hstate, (size_t) n_rows * sizeof(ge::RowState), hipMemcpyHostToDevice, s));
+        const k::GrammarDev gd{ (const ge::Elem *) g.rules, (const uint32_t *) (g.rules + (size_t) g.n_elems * sizeof(ge::Elem)), g.n_rules, g.vbytes, g.voff, v.eot };
+        k::grammar_reject(gd, g.states, n_rows, NV, g.reject, (uint32_t *) (hstate + 8), s);
+        st.gram_steps_dev++;
+    }
+    bool contiguous = true;
+    for (int r = 0; r < n_rows; ++r) contiguous = contiguous && rows[r] == rows[0] + r;
+    auto sample = [&]() {
+        if (contiguous) {
+            if (best) k::grammar_argmax(d.logits + (size_t) rows[0] * NV, d.ban_dev, g.reject, penalty, ds, dout, g.scratch, s, n_rows);
+            else k::grammar_draw(d.logits + (size_t) rows[0] * NV, d.ban_dev, g.reject, penalty, ds, du, k, dout, g.scratch, s, n_rows, tid_default);
+        } else for (int r = 0; r < n_rows; ++r) {
+            if (best) k::grammar_argmax(d.logits + (size_t) rows[r] * NV, d.ban_dev, g.reject + (size_t) r * NV, penalty, ds + r, dout + r, g.scratch, s, 1);
+            else k::grammar_draw(d.logits + (size_t) rows[r] * NV, d.ban_dev, g.reject + (size_t) r * NV, penalty, ds + r, du + r * k, k, dout + r * k, g.scratch, s, 1, tid_default);
+        }
+        return HIP_OK(hipStreamSynchronize(s));
+    };
+    if (!sample()) return false;
+    // a token's working set overflowed somewhere in a row: exactness first — the host computes that row's set and the step is sampled again
+    bool again = false;
+    for (int r = 0; r < n_rows; ++r) if (hover[r]) { again = true; if (!host_row(r)) return false; }
+    if (again && !sample()) return false;
+    const k::SampleOut * hout = (const k::SampleOut *) ((char *) d.draw_host + OFF_OUT);
     for (int i = 0; i < n_rows * k; ++i)
         out[i] = whisper_token_data{ hout[i].id, hout[i].tid, hout[i].p, hout[i].plog, hout[i].pt, hout[i].ptsum, -1, -1, 0.0f };
     st.t_sample_us += time_us() - t0; st.n_sample += n_rows;

@@ -74,6 +74,11 @@ int full(whisper_context & ctx, whisper_full_params params, const float * sample
     const bool dtw = ctx.token_dtw_mode != 0 && ctx.model.n_loaded > 0;
     if (dtw) st.dtw_pairs_call = ctx.dtw_pairs.empty() ? dtw_default_pairs(hp) : ctx.dtw_pairs;
     st.dtw_last = State::DtwDims{}; st.dtw_jumps.clear();
+    // the grammar on the device (wmi_set_grammar_device; 0: nothing below allocates or launches anything): the rules of this call, flat
+    st.gram_steps_dev = 0; st.gram_rows_host = 0;
+    const bool gram_mode = ctx.grammar_device_mode == 1 && params.grammar_rules && params.n_grammar_rules > 0 && ctx.model.n_loaded > 0;
+    GrammarFlat gram_flat;
+    if (gram_mode) gram_flat = grammar_flatten(grammar_init(params.grammar_rules, params.n_grammar_rules, params.i_start_rule));
     // the envelope kernel reads the caller's samples on a side stream: never return while it is in flight
     struct EnvelopeGuard { State & st; ~EnvelopeGuard() { (void) signal_energy_wait(st); } } envelope_guard{st};
     static const bool defer_phases = getenv("WMI_PHASE_SYNC") == nullptr;
@@ -232,11 +237,17 @@ int full(whisper_context & ctx, whisper_full_params params, const float * sample
                               ctx.model.n_loaded > 0 && upload_static_ban(ctx, params);
             // Beam search and t > 0 (whisper_sample_token_topk / whisper_sample_token(best = false)): the filters, the soft-max and the
             // CDF search of the draws run on the device as well (device.cpp: sample_rows_device) — the decoders' mt19937 generators stay
-            // here and supply the uniform numbers.  User callbacks and grammars need the host arrays and keep the host path.
+            // here and supply the uniform numbers.  User callbacks need the host arrays and keep the host path; so do grammars, unless
+            // wmi_set_grammar_device is on: then every decoder's reject mask and the penalised second pass run on the device too
+            // (device.cpp: sample_rows_grammar_device), the greedy pick at t = 0 included.
             const bool no_dev_draw = k::knobs().host_draws;                           // debug / A-B and the tests (wmi_reload_knobs after a change)
-            const bool dev_draw = !fast && !no_dev_draw && (beam || t_cur > 0.0f) && n_cur <= MAX_DECODERS &&
-                                  !params.logits_filter_callback && !params.grammar_rules && params.n_grammar_rules == 0 &&
-                                  ctx.model.n_loaded > 0 && upload_static_ban(ctx, params);
+            const bool gram_dev = gram_mode && !fast && !no_dev_draw && n_cur <= MAX_DECODERS && !params.logits_filter_callback &&
+                                  upload_static_ban(ctx, params) && grammar_device_begin(ctx, gram_flat);
+            const bool gram_best = gram_dev && !beam && t_cur < 1e-6f;                // (sample_token(best = true): no uniform numbers are drawn)
+            const bool dev_draw = gram_dev ||
+                                  (!fast && !no_dev_draw && (beam || t_cur > 0.0f) && n_cur <= MAX_DECODERS &&
+                                   !params.logits_filter_callback && !params.grammar_rules && params.n_grammar_rules == 0 &&
+                                   ctx.model.n_loaded > 0 && upload_static_ban(ctx, params));
             st.dev.keep_logits_on_device = dev_draw;
             struct KeepOff { bool & f; ~KeepOff() { f = false; } } keep_off{st.dev.keep_logits_on_device};
             whisper_token_data fast_next{};      // token picked on the device for the upcoming sampling step
@@ -311,17 +322,20 @@ int full(whisper_context & ctx, whisper_full_params params, const float * sample
                     // uniform numbers exactly as std::discrete_distribution would take them from each decoder's generator
                     const int k = beam ? params.beam_search.beam_size : 1;
                     StepFilter fl[MAX_DECODERS]; int rows_[MAX_DECODERS], live[MAX_DECODERS]; double u[MAX_DECODERS * MAX_DECODERS];
+                    const Grammar * gr[MAX_DECODERS];
                     int nl = 0;
                     for (int j = 0; j < n_cur; ++j) {
                         Decoder & d = st.decoders[j];
                         if (d.completed || d.failed) continue;
-                        fl[nl] = step_filter(d); rows_[nl] = i == 0 ? 0 : d.i_batch; live[nl] = j;
-                        for (int c = 0; c < std::min(k, (int) MAX_DECODERS); ++c) u[nl * std::min(k, (int) MAX_DECODERS) + c] = std::generate_canonical<double, 53>(d.rng);
+                        fl[nl] = step_filter(d); rows_[nl] = i == 0 ? 0 : d.i_batch; live[nl] = j; gr[nl] = &d.grammar;
+                        for (int c = 0; c < std::min(k, (int) MAX_DECODERS) && !gram_best; ++c) u[nl * std::min(k, (int) MAX_DECODERS) + c] = std::generate_canonical<double, 53>(d.rng);
                         ++nl;
                     }
                     const int kk = std::min(k, (int) MAX_DECODERS);
                     std::vector<whisper_token_data> res((size_t) nl * kk);
-                    if (nl > 0 && !sample_rows_device(ctx, fl, rows_, nl, t_cur, kk, u, beam ? v.beg : 0, res.data())) {
+                    if (nl > 0 && !(gram_dev ? sample_rows_grammar_device(ctx, gram_flat, gr, params.grammar_penalty, fl, rows_, nl, t_cur, kk, gram_best, u,
+                                                                          beam ? v.beg : 0, res.data())
+                                             : sample_rows_device(ctx, fl, rows_, nl, t_cur, kk, u, beam ? v.beg : 0, res.data()))) {
                         WMI_ERR("%s: device sampling failed\n", __func__);
                         return -8;
                     }

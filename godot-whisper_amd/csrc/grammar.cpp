@@ -173,8 +173,10 @@ Grammar grammar_init(const whisper_grammar_element ** rules, size_t n_rules, siz
     return g;
 }
 
-void grammar_penalise(const whisper_context & ctx, const Grammar & g, float penalty, std::vector<float> & logits) {
-    if (g.rules.empty() || g.stacks.empty()) return;
+// the ids grammar_penalise penalises: the definition of the reject set
+static std::vector<int32_t> reject_ids(const whisper_context & ctx, const Grammar & g) {
+    std::vector<int32_t> ids;
+    if (g.rules.empty() || g.stacks.empty()) return ids;
     const Vocab & v = ctx.model.vocab;
     std::vector<Decoded> decoded;
     decoded.reserve(v.eot);
@@ -187,7 +189,84 @@ void grammar_penalise(const whisper_context & ctx, const Grammar & g, float pena
         cands.push_back(Candidate{ id, nullptr, decoded.back().tail });
     }
     for (size_t i = 0; i < cands.size(); ++i) cands[i].cp = decoded[i].cp.data();      // after the last push_back: stable addresses
-    for (const Candidate & c : rejects_for_all(g.rules, g.stacks, cands)) logits[c.id] -= penalty;
+    for (const Candidate & c : rejects_for_all(g.rules, g.stacks, cands)) ids.push_back(c.id);
+    return ids;
+}
+
+void grammar_penalise(const whisper_context & ctx, const Grammar & g, float penalty, std::vector<float> & logits) {
+    for (const int32_t id : reject_ids(ctx, g)) logits[id] -= penalty;
+}
+
+void grammar_reject_mask(const whisper_context & ctx, const Grammar & g, uint8_t * mask) {
+    memset(mask, 0, (size_t) ctx.model.vocab.n_vocab);
+    for (const int32_t id : reject_ids(ctx, g)) mask[id] = ge::REJECTED;
+}
+
+// ---- the flat form grammar_eval.h works on
+GrammarFlat grammar_flatten(const Grammar & g) {
+    GrammarFlat f;
+    const uint32_t n_rules = (uint32_t) g.rules.size();
+    for (const auto & rule : g.rules) {
+        f.rule_off.push_back((uint32_t) f.elems.size());
+        // alternative := (RULE_REF | class)*, class := (CHAR | CHAR_NOT) [RNG_UPPER] (CHAR_ALT [RNG_UPPER])*; anything else is malformed
+        // (the reference asserts on it): such a grammar keeps the host's logic
+        size_t i = 0;
+        const auto type = [&](size_t j) { return j < rule.size() ? (int) rule[j].type : (int) G_END; };
+        while (i + 1 < rule.size()) {
+            const int t = type(i);
+            if (t == G_ALT) { ++i; continue; }
+            if (t == G_RULE_REF) { if (rule[i].value >= n_rules) return f; ++i; continue; }
+            if (t != G_CHAR && t != G_CHAR_NOT) return f;
+            ++i;
+            if (type(i) == G_CHAR_RNG_UPPER) ++i;
+            while (type(i) == G_CHAR_ALT) { ++i; if (type(i) == G_CHAR_RNG_UPPER) ++i; }
+        }
+        if (rule.empty() || i + 1 != rule.size() || rule.back().type != G_END) return f;
+        for (const auto & e : rule) f.elems.push_back(ge::Elem{ (uint32_t) e.type, e.value });
+    }
+    f.rule_off.push_back((uint32_t) f.elems.size());
+    f.ok = f.elems.size() <= (size_t) ge::MAX_ELEMS;
+    return f;
+}
+
+bool grammar_row_state(const Grammar & g, const GrammarFlat & f, ge::RowState & out) {
+    out.partial_value = g.partial.value; out.partial_n_remain = g.partial.n_remain; out.n_stacks = 0; out.n_words = 0;
+    if (g.rules.empty() || g.stacks.empty()) return true;
+    out.n_stacks = -1;
+    if (!f.ok || g.stacks.size() > (size_t) ge::MAX_STACKS) return false;
+    int w = 0;
+    for (const Stack & s : g.stacks) {
+        if (s.size() > (size_t) ge::MAX_DEPTH) return false;
+        out.words[w++] = (uint16_t) s.size();
+        for (const GrammarPos & p : s) out.words[w++] = (uint16_t) (f.rule_off[p.rule] + (uint32_t) p.off);
+    }
+    out.n_words = w; out.n_stacks = (int32_t) g.stacks.size();
+    return true;
+}
+
+void grammar_vocab_flat(const Vocab & v, std::vector<uint8_t> & bytes, std::vector<uint32_t> & off) {
+    bytes.clear(); off.assign((size_t) v.eot + 1, 0);
+    for (int32_t id = 0; id < v.eot; ++id) {
+        const std::string & text = v.id_to_token[id];
+        off[id] = (uint32_t) bytes.size() | (text.empty() ? ~ge::OFF_MASK : 0u);
+        bytes.insert(bytes.end(), text.c_str(), text.c_str() + strlen(text.c_str()));      // the reference walks a C string
+    }
+    off[v.eot] = (uint32_t) bytes.size();
+    bytes.push_back(0);                                     // (never empty: the device copy has a size)
+}
+
+bool grammar_eval_host(const GrammarFlat & f, const std::vector<uint8_t> & bytes, const std::vector<uint32_t> & off, const ge::RowState & st,
+                       uint8_t * mask, int n_vocab) {
+    memset(mask, 0, (size_t) n_vocab);
+    const ge::Rules R{ f.elems.data(), f.rule_off.data(), (int) f.rule_off.size() - 1 };
+    const ge::Vocab V{ bytes.data(), off.data(), (int) off.size() - 1 };
+    uint16_t ws[2 * ge::WS_WORDS];
+    bool overflow = false;
+    for (int id = 0; id < V.n && id < n_vocab; ++id) {
+        const uint8_t r = ge::eval_token(R, V, st, id, ws, 1);
+        if (r == ge::OVERFLOW) overflow = true; else mask[id] = r;
+    }
+    return !overflow;
 }
 
 void grammar_accept_token(const whisper_context & ctx, Grammar & g, int32_t token) {

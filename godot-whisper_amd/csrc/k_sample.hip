@@ -343,6 +343,10 @@ void filter_argmax(const float * logits, const uint8_t * static_ban, const DecSt
     else if (xu == 2) hipLaunchKernelGGL((k_filter_pick<2, 1>), dim3(n_rows), dim3(64), 0, st, part, np, step, out, out_host, sp.base, sp.slot, cn);
     else              hipLaunchKernelGGL((k_filter_pick<3, 1>), dim3(n_rows), dim3(64), 0, st, part, np, step, out, out_host, sp.base, sp.slot, cn);
 }
+// the statistics pass on its own (k_grammar.hip: the unpenalised statistics in front of the grammar's second pass)
+void filter_stats(const float * logits, const uint8_t * static_ban, const DecStep * step, FsPartial * part, hipStream_t st, int n_rows) {
+    hipLaunchKernelGGL(k_filter_stats, dim3(NB, n_rows), dim3(NT), 0, st, logits, static_ban, step, part, Stamp{nullptr, 0});
+}
 size_t filter_scratch_bytes(int n_rows) { return (size_t) std::max(n_rows * NB, FS_MAX_PARTS) * sizeof(Partial); }
 
 }} // namespace wmi::k

@@ -8,6 +8,7 @@
 #include <hip/hip_fp16.h>
 #include <atomic>
 #include <cstdint>
+#include "grammar_eval.h"
 
 namespace wmi { namespace k {
 
@@ -558,6 +559,22 @@ size_t filter_scratch_bytes(int n_rows = 1);
 void filter_draw(const float * logits, const uint8_t * static_ban, const DecStep * step, const double * u, int k, SampleOut * out,
                  void * scratch, hipStream_t st, int n_rows, int tid_default);
 size_t filter_draw_scratch_bytes(int n_rows);
+void filter_stats(const float * logits, const uint8_t * static_ban, const DecStep * step, FsPartial * part, hipStream_t st, int n_rows);
+// Grammar-constrained decoding on the device (k_grammar.hip; the evaluator is grammar_eval.h).  grammar_reject: grid (ceil(eot / 256), rows),
+// one thread per token id — reject [n_rows][n_vocab] gets ge::REJECTED / ge::ACCEPTED for ids below eot (the bytes from eot on are never
+// written: the caller keeps them 0), overflow[row] = 1 (a plain store; the caller zeroes the words) when a token's working set exceeded its
+// capacity; a row whose state says n_stacks < 0 is left alone.  states: device memory.
+// grammar_argmax / grammar_draw: filter_argmax / filter_draw with the penalised second pass of W/whisper.cpp:4657-4709 — unless the
+// unpenalised timestamp mass beats every text token, every rejected, allowed, finite text logit loses `penalty` behind the temperature
+// division and the log-soft-max is taken again.  scratch: grammar_sample_scratch_bytes.
+struct GrammarDev { const ge::Elem * elems; const uint32_t * rule_off; int n_rules; const uint8_t * vbytes; const uint32_t * voff; int eot; };
+void grammar_reject(const GrammarDev & g, const ge::RowState * states, int n_rows, int n_vocab, uint8_t * reject, uint32_t * overflow,
+                    hipStream_t st);
+void grammar_argmax(const float * logits, const uint8_t * static_ban, const uint8_t * reject, float penalty, const DecStep * step,
+                    SampleOut * out, void * scratch, hipStream_t st, int n_rows);
+void grammar_draw(const float * logits, const uint8_t * static_ban, const uint8_t * reject, float penalty, const DecStep * step,
+                  const double * u, int k, SampleOut * out, void * scratch, hipStream_t st, int n_rows, int tid_default);
+size_t grammar_sample_scratch_bytes(int n_rows);
 // first kernel of a replayed step: fetch DecStep from pinned host memory, mirror it on the device, embed the token
 void dec_embed_step(const DecStep * host_step, DecStep * dev_step, int S, const __half * te, const float * pe, float * x, hipStream_t st,
                     int n_rows = 1);

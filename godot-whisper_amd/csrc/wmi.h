@@ -258,6 +258,13 @@ struct DeviceState {
     void  * draw_host = nullptr;                                   // DecStep[8] | u[8][8] | SampleOut[8][8] (pinned)
     void  * draw_scratch = nullptr;
     bool    step_capture_failed = false;                               // a failed capture is not retried
+    // the grammar on the device (wmi_set_grammar_device; device.cpp: grammar_device_begin / sample_rows_grammar_device), all made on
+    // first use: the vocabulary's texts and offsets (uploaded once), the rules of the call in progress {elements | rule offsets}, the
+    // row states of a step, the reject mask [8][n_vocab], the sampling scratch, a pinned block {ge::RowState[8] | overflow words [8]}
+    struct GrammarBufs {
+        uint8_t * vbytes = nullptr; uint32_t * voff = nullptr; char * rules = nullptr; size_t rules_cap = 0; int n_rules = 0, n_elems = 0;
+        ge::RowState * states = nullptr; uint8_t * reject = nullptr; void * scratch = nullptr; void * host = nullptr;
+    } gram;
     // the no-speech head (device.cpp: no_speech_*): block partials, the <sot> row's logits of a quantised prompt batch, the pinned {p, tag}
     // records of up to k::NSP_MAX_ROWS rows, the tag of the last launch; nsp_row >= 0 asks the next decode() for the head on that batch row
     void  * nsp_scratch = nullptr; float * nsp_logits = nullptr; void * nsp_host = nullptr; int32_t nsp_seq = 0; int nsp_row = -1;
@@ -289,6 +296,9 @@ struct State {
     // the last window aligned on this state (wmi_token_dtw_dims; the tensors stay in dev.dtw until the next one), the alignment's own timer
     struct DtwDims { int n = 0, n_sot = 0, R = 0, M = 0, n_pairs = 0; } dtw_last; std::vector<int32_t> dtw_jumps;
     int64_t t_dtw_us = 0; int32_t n_dtw = 0;
+    // wmi_grammar_status: sampling steps whose reject masks k_grammar_reject wrote / rows whose mask the host computed instead, since the
+    // start of the last transcription call
+    int32_t gram_steps_dev = 0, gram_rows_host = 0; float gram_reject_us = 0.0f;      // (the last wmi_selftest_grammar launch, by events)
     std::vector<int32_t> dtw_pairs_call;          // the pairs of the transcription call in progress (full() copies the context's at its start)
     std::vector<int32_t> prompt_past;
     int     lang_id = 0;
@@ -399,6 +409,7 @@ struct whisper_context {
     int            no_speech_mode = 0;  // wmi_set_no_speech: 0 off, 1 report, 2 drop, 3 gate; read at the start of every transcription call
     // wmi_set_token_dtw: 0 off, 1 on; the (layer, head) pairs in effect, ascending, flattened {l, h, l, h, ..}; read at the start of every transcription call
     int            token_dtw_mode = 0; std::vector<int32_t> dtw_pairs;
+    int            grammar_device_mode = 0;   // wmi_set_grammar_device: 0 off, 1 the reject masks and the penalised sampling on the device; read per window
     // streams with a hardware queue of their own, made together with the context's first stream and handed to replica contexts later
     // (init_state: it is the ORDER in which the queues are created that decides whether the replicas run beside each other)
     std::vector<hipStream_t> spare_streams;
@@ -467,6 +478,18 @@ void enqueue_rows_lang_step_q(whisper_context & ctx, int nb, float * out);      
 bool decode_layers_q(whisper_context & ctx, int n, int n_kv, int kv_head, int Tc, const std::vector<int> & rows, float * lang_out = nullptr,
                      const int32_t * nsp_row_dev = nullptr, float * nsp_logits = nullptr);
 void enqueue_greedy_step_q(whisper_context & ctx, int Tc);
+// The grammar on the device (wmi_set_grammar_device; grammar_eval.h, k_grammar.hip).  grammar_flatten: the rules as one element array
+// (ok = false: malformed or too long — the host's logic serves such a grammar); grammar_row_state: a decoder's stacks and partial
+// sequence in the evaluator's form (false, n_stacks = -1: over a capacity); grammar_vocab_flat: the texts of the ids below eot;
+// grammar_eval_host: grammar_eval.h over the vocabulary on the host (false: some token's working set overflowed);
+// grammar_reject_mask: the same byte mask [n_vocab] from grammar_penalise's own logic — the definition, and the fallback.
+struct GrammarFlat { std::vector<ge::Elem> elems; std::vector<uint32_t> rule_off; bool ok = false; };
+GrammarFlat grammar_flatten(const Grammar & g);
+bool grammar_row_state(const Grammar & g, const GrammarFlat & f, ge::RowState & out);
+void grammar_vocab_flat(const Vocab & v, std::vector<uint8_t> & bytes, std::vector<uint32_t> & off);
+bool grammar_eval_host(const GrammarFlat & f, const std::vector<uint8_t> & bytes, const std::vector<uint32_t> & off, const ge::RowState & st,
+                       uint8_t * mask, int n_vocab);
+void grammar_reject_mask(const whisper_context & ctx, const Grammar & g, uint8_t * mask);
 // greedy fast path: decode ONE token of sequence 0 at position `pos` and pick the next token on the device
 struct StepFilter { bool ban_blank, last_ts, penult_ts; int ts_floor_end, ts_initial_start; };
 // the filter state of the token a decoder samples next (W/whisper.cpp:4541-4657), from its history, has_ts and seek_delta: the one place
@@ -516,6 +539,15 @@ void dtw_path_host(int R, int M, const float * A, int32_t * jumps, int32_t * pat
 // u [n_rows][k] uniform numbers in [0, 1) from the decoders' generators.  out [n_rows][k].
 bool sample_rows_device(whisper_context & ctx, const StepFilter * f, const int * rows, int n_rows, float temperature, int k,
                         const double * u, int tid_default, whisper_token_data * out);
+// The grammar on the device (wmi_set_grammar_device).  grammar_device_begin: the buffers, the vocabulary's texts (first use) and the flat
+// rules gf of the call in progress (gf.ok = false: nothing is uploaded, every row takes the host's reject set).  sample_rows_grammar_device:
+// sample_rows_device for rows that carry a grammar each (gr[r]) — the reject masks by k_grammar_reject (a row over the state's or a
+// token's capacities: by grammar_reject_mask on the host, counted in State::gram_rows_host), then the penalised second pass; best: the
+// arg-max pick (k = 1, u unused) instead of draws.
+bool grammar_device_begin(whisper_context & ctx, const GrammarFlat & gf);
+bool sample_rows_grammar_device(whisper_context & ctx, const GrammarFlat & gf, const Grammar * const * gr, float penalty, const StepFilter * f,
+                                const int * rows, int n_rows, float temperature, int k, bool best, const double * u, int tid_default,
+                                whisper_token_data * out);
 bool wait_for_sample(const k::SampleOut * r, int32_t want, hipStream_t s, int32_t * status = nullptr);   // spin on a pinned, self-tagged result record (device.cpp)
 // host worker pool (pool.cpp): fn(0..n_tasks-1) on a few persistent threads + the caller; nested calls run inline
 void pool_run(int n_tasks, const std::function<void(int)> & fn);

@@ -37,8 +37,13 @@ def _fptr(a: np.ndarray):
 class SpeechToText:
     """One `whisper_context` per node (src/speech_to_text.h:135); not re-entrant."""
 
-    def __init__(self, lib: C.CDLL, settings: dict | None = None, no_speech: int = 0, token_dtw=False):
-        """token_dtw (product library only, include/wmi_device.h wmi_set_token_dtw): True — DTW token times over the default alignment
+    def __init__(self, lib: C.CDLL, settings: dict | None = None, no_speech: int = 0, token_dtw=False, grammar=None,
+                 grammar_penalty: float = 100.0, grammar_device: bool = False):
+        """grammar: rules in the format of abi.make_grammar (a list of rules, each a list of (type, value) without the closing END; rule 0
+        is the start rule) — every full_params() then carries them with grammar_penalty; None: no grammar.
+        grammar_device (product library only, include/wmi_device.h wmi_set_grammar_device): True — the grammar's reject masks and the
+        penalised sampling run on the device; False — the reference's host path.
+        token_dtw (product library only, include/wmi_device.h wmi_set_token_dtw): True — DTW token times over the default alignment
         heads — or a list of (layer, head) pairs; every token dictionary then gains "t_dtw" (10 ms units, -1 for a token that is no text).
         "t0" / "t1" stay the reference's.
         no_speech (product library only, include/wmi_device.h wmi_set_no_speech): 0 off — the reference's behaviour —, 1 report the
@@ -47,6 +52,10 @@ class SpeechToText:
         self.ctx = None
         self.no_speech = int(no_speech)
         self.token_dtw = token_dtw
+        self.grammar_device = bool(grammar_device)
+        self.grammar_penalty = float(grammar_penalty)
+        self._grammar = None
+        self.set_grammar(grammar, grammar_penalty)
         self.last_windows = []
         self.language = "en"  # Language enum -> code, src/speech_to_text.cpp:117-324
         self.settings = dict(SETTINGS)
@@ -66,6 +75,25 @@ class SpeechToText:
         del buf  # the loader only borrows the buffer during the call (W/whisper.cpp:3231-3240)
         self.set_no_speech(self.no_speech)
         self.set_token_dtw(self.token_dtw)
+        self.set_grammar_device(self.grammar_device)
+
+    def set_grammar(self, rules, penalty: float = 100.0):
+        """The grammar of every later full_params() (None: none).  The element arrays stay referenced by this node."""
+        self.grammar_penalty = float(penalty)
+        self._grammar = abi.make_grammar(rules) if rules else None
+
+    def set_grammar_device(self, on: bool) -> int:
+        """The context's grammar route from the next transcription call on; returns the previous mode (0 without a context)."""
+        self.grammar_device = bool(on)
+        if not self.ctx or not (self.grammar_device or hasattr(self.lib, "wmi_set_grammar_device")):
+            return 0
+        return self.lib.wmi_set_grammar_device(self.ctx, 1 if self.grammar_device else 0)
+
+    def grammar_status(self) -> dict:
+        """wmi_grammar_status of the last call: device steps, host fallback rows, the compiled capacities"""
+        st = abi.wmi_grammar_status()
+        assert self.lib.wmi_grammar_status(self.ctx, C.byref(st)) == 0
+        return {k: getattr(st, k) for k, _ in st._fields_}
 
     def set_token_dtw(self, token_dtw) -> int:
         """The context's alignment mode from the next transcription call on (False, True or (layer, head) pairs); returns the previous
@@ -110,6 +138,10 @@ class SpeechToText:
         p.max_tokens = int(self.settings["audio/input/transcribe/max_tokens"])
         p.entropy_thold = float(self.settings["audio/input/transcribe/entropy_treshold"])
         p.initial_prompt = prompt
+        if self._grammar is not None:
+            ptrs, n_rules, _ = self._grammar
+            p.grammar_rules = C.cast(ptrs, C.c_void_p); p.n_grammar_rules = n_rules; p.i_start_rule = 0
+            p.grammar_penalty = self.grammar_penalty
         if getattr(self, "n_threads", 0):            # tests: the CPU reference behind this mirror (results do not depend on the thread count)
             p.n_threads = int(self.n_threads)
         return p

@@ -30,6 +30,18 @@ void SpeechToText::set_language_model(const uint8_t * data, size_t size) {   // 
     context_instance = whisper_init_from_buffer_with_params((void *) data, size, context_params);
     if (context_instance && no_speech != 0) (void) wmi_set_no_speech(context_instance, no_speech);
     if (context_instance && token_dtw) (void) wmi_set_token_dtw(context_instance, 1, token_dtw_pairs.data(), (int) token_dtw_pairs.size() / 2);
+    if (context_instance && grammar_device) (void) wmi_set_grammar_device(context_instance, 1);
+}
+
+void SpeechToText::set_grammar(const std::vector<std::vector<whisper_grammar_element>> & rules, float penalty) {
+    grammar_rules = rules; grammar_penalty = penalty;
+    grammar_ptrs.clear();
+    for (auto & r : grammar_rules) { r.push_back(whisper_grammar_element{ WHISPER_GRETYPE_END, 0 }); grammar_ptrs.push_back(r.data()); }
+}
+
+int SpeechToText::set_grammar_device(bool on) {
+    grammar_device = on;
+    return context_instance ? wmi_set_grammar_device(context_instance, on ? 1 : 0) : 0;
 }
 
 int SpeechToText::set_token_dtw(bool on, const std::vector<int32_t> & layer_head) {
@@ -84,6 +96,10 @@ whisper_full_params SpeechToText::make_params(const std::string & initial_prompt
     p.max_tokens = settings.max_tokens;
     p.entropy_thold = settings.entropy_treshold;
     p.initial_prompt = initial_prompt.c_str();          // the caller's string outlives the call (the reference lets it dangle, :413)
+    if (!grammar_ptrs.empty()) {
+        p.grammar_rules = const_cast<const whisper_grammar_element **>(grammar_ptrs.data()); p.n_grammar_rules = grammar_ptrs.size();
+        p.i_start_rule = 0; p.grammar_penalty = grammar_penalty;
+    }
     return p;
 }
 

@@ -65,6 +65,13 @@ public:
     // given {layer, head, layer, head, ..} list; kept across set_language_model.  Returns what wmi_set_token_dtw does (0 without a context).
     int  set_token_dtw(bool on, const std::vector<int32_t> & layer_head = {});
     bool get_token_dtw() const { return token_dtw; }
+    // not in the reference: a grammar for every later transcription (whisper_full_params.grammar_rules: rule 0 is the start rule, each rule
+    // without its closing END element; an empty list: none), and where it is evaluated (include/wmi_device.h wmi_set_grammar_device:
+    // true — reject masks and penalised sampling on the device); both kept across set_language_model.  set_grammar_device returns the
+    // previous mode (0 without a context).
+    void set_grammar(const std::vector<std::vector<whisper_grammar_element>> & rules, float penalty = 100.0f);
+    int  set_grammar_device(bool on);
+    bool get_grammar_device() const { return grammar_device; }
 
     // src/speech_to_text.h:151-156, :162 — resample(PackedVector2Array buffer, InterpolatorType): stereo capture frames at the mix rate
     // -> mono 16 kHz.  The reference folds on the CPU and calls libsamplerate's src_simple; here both steps run on the device
@@ -99,6 +106,9 @@ protected:
     int language = English;
     int no_speech = 0;
     bool token_dtw = false; std::vector<int32_t> token_dtw_pairs;
+    bool grammar_device = false; float grammar_penalty = 100.0f;
+    std::vector<std::vector<whisper_grammar_element>> grammar_rules;     // each closed by an END element
+    std::vector<const whisper_grammar_element *> grammar_ptrs;
     whisper_context * context_instance = nullptr;
 };
 

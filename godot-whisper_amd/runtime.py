@@ -130,6 +130,11 @@ DEVICE_API = [
     ("wmi_get_token_dtw_timings", None, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     ("wmi_selftest_dtw_matrix", C.c_int, [C.c_int] * 8 + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     ("wmi_selftest_dtw_path", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
+    ("wmi_set_grammar_device", C.c_int, [C.c_void_p, C.c_int]),
+    ("wmi_grammar_status", C.c_int, [C.c_void_p, C.POINTER(abi.wmi_grammar_status)]),
+    ("wmi_selftest_grammar", C.c_int, [C.c_void_p, abi.whisper_full_params, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("wmi_selftest_grammar_sample", C.c_int, [C.c_void_p, abi.whisper_full_params, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     ("wmi_long_default_params", abi.wmi_long_params, []),
     ("wmi_full_long", C.c_int, [C.c_void_p, abi.whisper_full_params, C.c_void_p, C.c_int, C.c_int, C.POINTER(abi.wmi_long_params)]),
     ("wmi_long_n_pieces", C.c_int, [C.c_void_p]),

@@ -625,6 +625,54 @@ WHISPER_API int     wmi_selftest_dtw_matrix(int device, int L, int S, int H, int
                                             const int32_t * layer_head, int n_pairs, float * A_out);
 WHISPER_API int     wmi_selftest_dtw_path(int device, int R, int M, const float * A, int32_t * jumps, int32_t * path, int * n_path);
 
+/* Grammar-constrained decoding on the device (whisper_full_params.grammar_rules; csrc/grammar_eval.h, csrc/k_grammar.hip).
+ * By default a call with a grammar copies every step's logits to the host, filters them there and walks the grammar's pushdown stacks over
+ * the whole vocabulary (csrc/grammar.cpp).  In mode 1 the general driver keeps the logits in HBM: after the host has advanced a decoder's
+ * grammar by the one sampled token, its stacks and partial UTF-8 state go up (2 KB per decoder), k_grammar_reject evaluates every token id
+ * below <eot> against them — one thread per id, the same text the host library compiles — into a reject byte mask beside the static ban,
+ * and the penalised second pass of W/whisper.cpp:4657-4709 (unless the timestamp mass beats every text token: every rejected, allowed,
+ * finite text logit loses grammar_penalty behind the temperature division, the log-soft-max is taken again) feeds the greedy pick, the
+ * t > 0 draws and the beam draws there; 32 bytes per pick come back.
+ * CONTRACT: the reject set is EXACT — the set grammar_penalise computes.  A decoder state above the compiled capacities (cap_stacks stacks
+ * of cap_depth positions, 65535 grammar elements, a malformed grammar) or a token whose working set outgrows cap_words 16-bit words is never
+ * guessed: that row's set is computed by the host's own logic for that step and uploaded, and the event is counted (rows_host).
+ * Probabilities carry the device sums' ~1e-6 relative, as on every device sampling path (see above); a pick at a near-tie may differ.
+ * whisper_get_logits() is undefined in the mode, as for device draws.  WMI_HOST_DRAWS=1 and a logits_filter_callback keep the whole host
+ * path.  Lock-step calls send grammar chunks to the general driver as before; that driver takes this route.  The one-row greedy step of
+ * grammar-free calls is not involved.
+ *   wmi_set_grammar_device   mode 0 off (default: nothing is allocated or launched, every result is byte for byte what it was without this
+ *                            interface), 1 on; read per window.  Returns the previous mode, -2 for a NULL context.
+ *   wmi_grammar_status       counters since the start of the last whisper_full* call on the context's state, and the compiled capacities.
+ *                            Returns 0, -2 for a NULL argument.
+ * Not measured here: transcription quality under a grammar on real models — only synthetic weights exist in this repository. */
+struct wmi_grammar_status {
+    int32_t steps_device;    /* sampling steps whose reject masks the kernel wrote */
+    int32_t rows_host;       /* decoder rows whose reject set the host computed instead (capacity fallback) */
+    int32_t cap_stacks;      /* stacks of a decoder's uploaded state */
+    int32_t cap_depth;       /* positions of one stack */
+    int32_t cap_words;       /* 16-bit words of one of the two runs of a token's working set (a stack takes 1 + its depth) */
+    float   reject_us;       /* GPU time of the last wmi_selftest_grammar(where = 1) launch of k_grammar_reject, by events (0: none yet) */
+};
+WHISPER_API int wmi_set_grammar_device(struct whisper_context * ctx, int mode);
+WHISPER_API int wmi_grammar_status(struct whisper_context * ctx, struct wmi_grammar_status * out);
+/* Test hooks.  Row r's grammar state is built from `params` (grammar_rules, n_grammar_rules, i_start_rule) and its token history exactly
+ * as wmi_process_logits builds it (hist: the histories one after the other, n_hist[r] tokens each); 1 <= n_rows <= 8.
+ *   wmi_selftest_grammar          reject_out [n_rows][n_vocab]: 1 rejected, 0 not; overflow_out [n_rows]: 1 where the row's state or a token's
+ *                                 working set exceeded a capacity (the row's bytes are then 0).  where = 0: csrc/grammar_eval.h on the host —
+ *                                 needs no device and touches none (works on a host-only context); where = 1: k_grammar_reject, the rows
+ *                                 on grid.y of one launch.
+ *   wmi_selftest_grammar_sample   modelled on wmi_selftest_filters (the same step records): caller logits [n_rows][n_vocab] go where the
+ *                                 decoder leaves them, then the driver's own route runs — reject masks, penalised second pass, and
+ *                                 mode 0 the pick (out [n_rows]) / mode 2 k draws per row with the uniform numbers u [n_rows][k]
+ *                                 (out [n_rows][k]).  The counters of wmi_grammar_status advance as in a transcription call.
+ * Return 0; -1 bad arguments (before the device is touched), -2 the context cannot compute, -3 device error. */
+WHISPER_API int wmi_selftest_grammar(struct whisper_context * ctx, struct whisper_full_params params, int where, int n_rows,
+                                     const whisper_token * hist, const int * n_hist, uint8_t * reject_out, uint32_t * overflow_out);
+WHISPER_API int wmi_selftest_grammar_sample(struct whisper_context * ctx, struct whisper_full_params params, int mode, int n_rows,
+                                            const float * logits, const whisper_token * hist, const int * n_hist, const int * has_ts,
+                                            const int * seek_delta, float temperature, const double * u, int k, int tid_default,
+                                            whisper_token_data * out);
+
 /* Long recordings: cut at silences on the device, decode the pieces in lock-step.
  * whisper_full walks a long signal window by window (each seek comes from the previous window's timestamps); whisper_full_parallel cuts it
  * into equal pieces wherever the arithmetic lands.  wmi_full_long looks at the signal first:
