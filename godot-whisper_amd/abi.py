@@ -206,6 +206,16 @@ class wmi_grammar_status(C.Structure):  # include/wmi_device.h: the counters and
                 ("cap_words", C.c_int32), ("reject_us", C.c_float)]
 
 
+class wmi_score_params(C.Structure):  # include/wmi_device.h: the parameters of wmi_score_texts (wmi_score_default_params has the defaults)
+    _fields_ = [("lang_id", C.c_int32), ("translate", C.c_int32), ("prompt_tokens", C.POINTER(C.c_int32)), ("prompt_n_tokens", C.c_int32),
+                ("with_eot", C.c_int32), ("length_norm", C.c_int32)]
+
+
+class wmi_text_score(C.Structure):  # include/wmi_device.h: one text's result of wmi_score_texts
+    _fields_ = [("sum_logprob", C.c_double), ("avg_logprob", C.c_float), ("posterior", C.c_float), ("n_scored", C.c_int32),
+                ("first", C.c_int32)]
+
+
 NO_SPEECH_OFF, NO_SPEECH_REPORT, NO_SPEECH_DROP, NO_SPEECH_GATE = range(4)       # wmi_set_no_speech modes
 WINDOW_EMITTED, WINDOW_DROPPED, WINDOW_GATED = range(3)                          # wmi_window.outcome
 TOKEN_DTW_OFF, TOKEN_DTW_ON = range(2)                                           # wmi_set_token_dtw modes

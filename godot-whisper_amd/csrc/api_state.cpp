@@ -354,6 +354,104 @@ void wmi_get_token_dtw_timings(struct whisper_context * ctx, int64_t * us, int32
     if (us) *us = have ? ctx->state->t_dtw_us : 0;
     if (n_windows) *n_windows = have ? ctx->state->n_dtw : 0;
 }
+// candidate texts scored against the audio (wmi_device.h; score.cpp)
+struct wmi_score_params wmi_score_default_params(void) {
+    struct wmi_score_params p = { 0, 0, nullptr, 0, 1, 0 };
+    return p;
+}
+int wmi_score_texts_with_state(struct whisper_context * ctx, struct whisper_state * state, struct wmi_score_params params, const whisper_token * tokens,
+                               const int32_t * n_tokens, int n_texts, struct wmi_text_score * out, float * token_logprobs, float * logits_out) {
+    if (!ctx) return -1;
+    if (ctx->host_only) { WMI_ERR("%s: host-only context has no compute path (this backend has no CPU fallback)\n", __func__); return -2; }
+    if (!state) state = reinterpret_cast<struct whisper_state *>(ctx->state.get());      // (NULL: the context's own state)
+    if (!state) return -1;
+    StateScope sc(ctx, state);
+    return score_texts(*ctx, params, tokens, n_tokens, n_texts, out, token_logprobs, logits_out);
+}
+int wmi_score_texts(struct whisper_context * ctx, struct wmi_score_params params, const whisper_token * tokens, const int32_t * n_tokens, int n_texts,
+                    struct wmi_text_score * out, float * token_logprobs) {
+    return wmi_score_texts_with_state(ctx, ctx ? reinterpret_cast<struct whisper_state *>(ctx->state.get()) : nullptr, params, tokens, n_tokens, n_texts,
+                                      out, token_logprobs, nullptr);
+}
+int wmi_score_pcm(struct whisper_context * ctx, struct wmi_score_params params, const float * pcm, int n_samples, int pcm_on_device, int audio_ctx,
+                  const whisper_token * tokens, const int32_t * n_tokens, int n_texts, struct wmi_text_score * out, float * token_logprobs) {
+    if (!ctx) return -1;
+    if (ctx->host_only) { WMI_ERR("%s: host-only context has no compute path (this backend has no CPU fallback)\n", __func__); return -2; }
+    if (!ctx->state || !pcm || n_samples < 1 || !out) return -1;
+    if (audio_ctx < 0 || audio_ctx > ctx->model.hp.n_audio_ctx) return -1;
+    StateScope sc(ctx, reinterpret_cast<struct whisper_state *>(ctx->state.get()));
+    State & st = *ctx->state;
+    {   // the arguments are judged before the log-mel and the encoder run
+        ScorePlan pl;
+        if (score_plan(ctx->model.vocab, ctx->model.hp, st.kv_self.size, params, tokens, n_tokens, n_texts, pl) != 0) return -1;
+    }
+    const int saved = st.exp_n_audio_ctx;
+    st.exp_n_audio_ctx = audio_ctx;
+    const bool ok = pcm_to_mel(*ctx, pcm, n_samples, pcm_on_device != 0) && encode(*ctx, 0);
+    st.exp_n_audio_ctx = saved;
+    if (!ok) { WMI_ERR("%s: failed to encode\n", __func__); return -3; }
+    return score_texts(*ctx, params, tokens, n_tokens, n_texts, out, token_logprobs, nullptr);
+}
+void wmi_get_score_timings(struct whisper_context * ctx, int64_t * us, int32_t * n_calls, int32_t * n_launches) {
+    const bool have = ctx && ctx->state;
+    if (us) *us = have ? ctx->state->t_score_us : 0;
+    if (n_calls) *n_calls = have ? ctx->state->n_score : 0;
+    if (n_launches) *n_launches = have ? ctx->state->n_score_launches : 0;
+}
+int wmi_selftest_score_plan(struct whisper_context * ctx, struct wmi_score_params params, const whisper_token * tokens, const int32_t * n_tokens,
+                            int n_texts, int32_t * prefix, int cap_prefix, int * n_prefix, int32_t * first, int32_t * prefix_target, int32_t * rows,
+                            int cap_rows, int * n_rows, int32_t * pass_text0, int cap_passes) {
+    if (!ctx) return -1;
+    ScorePlan pl;
+    // (a host-only context has no self cache: the size init_state would give it)
+    const size_t kv_cells = ctx->state && ctx->state->kv_self.size > 0 ? ctx->state->kv_self.size : 3 * (size_t) ctx->model.hp.n_text_ctx;
+    if (score_plan(ctx->model.vocab, ctx->model.hp, kv_cells, params, tokens, n_tokens, n_texts, pl) != 0) return -1;
+    if (n_prefix) *n_prefix = (int) pl.prefix.size();
+    for (int i = 0; prefix && i < cap_prefix && i < (int) pl.prefix.size(); ++i) prefix[i] = pl.prefix[i];
+    for (int c = 0; first && c <= n_texts; ++c) first[c] = pl.first[c];
+    for (int c = 0; prefix_target && c < n_texts; ++c) prefix_target[c] = pl.prefix_target[c];
+    int nr = 0;
+    for (size_t ip = 0; ip < pl.passes.size(); ++ip) {
+        const ScorePass & ps = pl.passes[ip];
+        if (pass_text0 && (int) ip < cap_passes) pass_text0[ip] = ps.c0;
+        for (size_t i = 0; i < ps.token.size(); ++i, ++nr) {
+            if (!rows || nr >= cap_rows) continue;
+            int32_t * r = rows + (size_t) nr * 7;
+            r[0] = (int32_t) ip; r[1] = ps.token[i]; r[2] = ps.pos[i]; r[3] = ps.seq[i]; r[4] = ps.flag[i]; r[5] = ps.target[i]; r[6] = ps.place[i];
+        }
+    }
+    if (pass_text0 && (int) pl.passes.size() < cap_passes) pass_text0[pl.passes.size()] = n_texts;
+    if (n_rows) *n_rows = nr;
+    return (int) pl.passes.size();
+}
+int wmi_selftest_score_rows(int device, int rows, int n_vocab, const float * logits, const int32_t * targets, float * lp_out) {
+    if (rows < 1 || n_vocab < 1 || n_vocab > k::NSP_MAX_VOCAB || !logits || !targets || !lp_out) return -1;
+    for (int r = 0; r < rows; ++r) if (targets[r] < 0 || targets[r] >= n_vocab) return -1;
+    if (!HIP_OK(hipSetDevice(device))) return -2;
+    struct Bufs {
+        std::vector<void *> dev; hipStream_t st = nullptr;
+        ~Bufs() { if (st) (void) hipStreamDestroy(st); for (void * q : dev) (void) hipFree(q); }
+        void * get(size_t bytes) { void * q = nullptr; if (!HIP_OK(hipMalloc(&q, bytes))) return nullptr; dev.push_back(q); return q; }
+    } b;
+    // as decode() works: a logits buffer of 8 rows, filled and scored group by group on one stream
+    const int G = k::SCORE_MAX_ROWS;
+    void * scratch = b.get(k::score_scratch_bytes(n_vocab));
+    float * d_l = (float *) b.get((size_t) G * n_vocab * 4), * d_lp = (float *) b.get((size_t) rows * 4);
+    int32_t * d_i = (int32_t *) b.get((size_t) 2 * rows * 4);
+    if (!scratch || !d_l || !d_lp || !d_i || !HIP_OK(hipStreamCreate(&b.st))) return -3;
+    std::vector<int32_t> items((size_t) 2 * rows);
+    for (int r = 0; r < rows; ++r) { items[r] = targets[r]; items[(size_t) rows + r] = r; }
+    if (!HIP_OK(hipMemcpyAsync(d_i, items.data(), items.size() * 4, hipMemcpyHostToDevice, b.st)) || !HIP_OK(hipStreamSynchronize(b.st))) return -3;
+    for (int r0 = 0; r0 < rows; r0 += G) {
+        const int nr = std::min(G, rows - r0);
+        if (!HIP_OK(hipMemcpyAsync(d_l, logits + (size_t) r0 * n_vocab, (size_t) nr * n_vocab * 4, hipMemcpyHostToDevice, b.st))) return -3;
+        k::ScoreRows sr{}; sr.n = nr; for (int r = 0; r < nr; ++r) sr.row[r] = r;
+        if (!k::score_rows(d_l, n_vocab, sr, n_vocab, d_i + r0, d_i + rows + r0, scratch, d_lp, b.st)) return -3;
+    }
+    if (!HIP_OK(hipMemcpyAsync(lp_out, d_lp, (size_t) rows * 4, hipMemcpyDeviceToHost, b.st)) || !HIP_OK(hipStreamSynchronize(b.st)) ||
+        !HIP_OK(hipGetLastError())) return -3;
+    return 0;
+}
 int wmi_selftest_no_speech_rule(int mode, float p, float thold, int failed, double avg_logprob, float logprob_thold) {
     return no_speech_rule(mode, p, thold, failed != 0, avg_logprob, logprob_thold);
 }

@@ -226,6 +226,9 @@ void destroy_state(State * st) {
     for (void * q : { (void *) d.dtw.w, (void *) d.dtw.mu, (void *) d.dtw.sigma, (void *) d.dtw.A, (void *) d.dtw.cost, (void *) d.dtw.trace, (void *) d.dtw.q })
         if (q) (void) hipFree(q);
     if (d.dtw_host) (void) hipHostFree(d.dtw_host);
+    if (d.score_scratch) (void) hipFree(d.score_scratch);
+    dfree(d.score_items); dfree(d.score_lp);
+    if (d.score_host) (void) hipHostFree(d.score_host);
     if (d.pinned) (void) hipHostFree(d.pinned);
     if (d.stream && d.stream_own_queue) own_queue_stream_put(st->device, d.stream);
     else if (d.stream) (void) hipStreamDestroy(d.stream);
@@ -558,8 +561,15 @@ bool decode(whisper_context & ctx, const Batch & batch, float * lang_logits) {
     const int Tc = st.enc_n_ctx > 0 ? st.enc_n_ctx : (st.exp_n_audio_ctx > 0 ? st.exp_n_audio_ctx : hp.n_audio_ctx);
     hipStream_t s = d.stream;
 
+    // the scorer's request (score_texts), for this call only: the flagged rows' logits are scored in d.logits group by group, nothing goes
+    // to the host's logits image or into the reference's timers, no wait here; the staging block is the request's own (the call's batches
+    // follow each other without a wait, so none may rewrite a block an earlier copy has not read yet)
+    const DeviceState::ScoreReq * const score = d.score_req;
+    d.score_req = nullptr;
+    if (score && (lang_logits || d.nsp_row >= 0 || d.dtw_collect || !score->staging ||
+                  score->staging_bytes < ((size_t) 3 * n + (size_t) n * kv.n) * 4)) { d.nsp_row = -1; d.dtw_collect = false; return false; }
     // host -> pinned -> device: tokens, positions, mask (W/whisper.cpp:2186-2226), rows wanting logits
-    int32_t * p_tok = (int32_t *) d.pinned, * p_pos = p_tok + n, * p_rows = p_pos + n;
+    int32_t * p_tok = (int32_t *) (score ? score->staging : d.pinned), * p_pos = p_tok + n, * p_rows = p_pos + n;
     float * p_mask = (float *) (p_rows + n);
     std::vector<int> rows;
     for (int i = 0; i < n; ++i) { p_tok[i] = batch.token[i]; p_pos[i] = batch.pos[i]; if (batch.logits[i]) rows.push_back(i); }
@@ -597,7 +607,8 @@ bool decode(whisper_context & ctx, const Batch & batch, float * lang_logits) {
     float * const lang_pinned = lang_logits ? (float *) ((char *) d.pinned + d.pinned_bytes - LANG_PINNED_TAIL) : nullptr;
     if (ctx.model.quantised) {
         const bool nsp_own = nsp_row >= 0 && nsp_slot < 0;
-        if (!decode_layers_q(ctx, n, n_kv, kv_head, Tc, rows, lang_pinned, nsp_own ? d.d_rows + rows.size() : nullptr, nsp_own ? d.nsp_logits : nullptr)) return false;
+        if (!decode_layers_q(ctx, n, n_kv, kv_head, Tc, rows, lang_pinned, nsp_own ? d.d_rows + rows.size() : nullptr, nsp_own ? d.nsp_logits : nullptr, score)) return false;
+        if (score) return HIP_OK(hipGetLastError());         // (no wait here: score_texts waits once, behind its last launch)
         if (nsp_row >= 0 && !(nsp_own ? no_speech_from_logits(ctx, d.nsp_logits, 0) : no_speech_from_logits(ctx, d.logits, nsp_slot))) return false;
         if (dtw) return HIP_OK(hipGetLastError());           // (no wait here: dtw_window waits once, behind the path)
         HIP_TRY(hipStreamSynchronize(s));
@@ -655,6 +666,18 @@ bool decode(whisper_context & ctx, const Batch & batch, float * lang_logits) {
     // final LN + logits = d_te . x for the rows that asked for them (the reference computes all rows
     // and copies out the flagged ones, W/whisper.cpp:2498, 2566-2572)
     if (dtw) return HIP_OK(hipGetLastError());               // (no row asked for logits, the host's image is left alone; no wait here: dtw_window waits once, behind the path)
+    if (score) {                                             // the groups of 8 as below, each scored where it lies; stream order makes the reuse of d.logits safe
+        int item = 0;
+        for (size_t r0 = 0; r0 < rows.size(); r0 += 8) {
+            const int nr = (int) std::min<size_t>(8, rows.size() - r0);
+            k::GemvArgs g{};
+            g.x32 = d.dx; g.ln_g = w.d_ln_g; g.ln_b = w.d_ln_b; g.eps = hp.eps; g.n = nr; g.K = S; g.N = NV; g.W = w.d_te;
+            g.epi = k::EPI_LOGITS; g.C = d.logits; g.ldc = NV; g.rows = d.d_rows + r0;
+            k::gemv(g, s);
+            if (!score_group(ctx, *score, (int) r0, nr, item)) return false;
+        }
+        return item == score->n_items && HIP_OK(hipGetLastError());
+    }
     if (lang_logits) k::lang_head(d.dx, 1, S, w.d_ln_g, w.d_ln_b, hp.eps, w.d_te + (size_t) (ctx.model.vocab.sot + 1) * S, lang_pinned, s);
     else st.logits.resize((size_t) n * NV);
     for (size_t r0 = 0; r0 < rows.size() && !lang_logits; r0 += 8) {

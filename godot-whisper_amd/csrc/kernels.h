@@ -420,6 +420,28 @@ bool no_speech_logits(const float * logits, int ld, const NoSpeechRows & rows, i
 bool no_speech_head(const float * x, int rows, int S, const float * ln_g, const float * ln_b, float eps, const __half * te, int n_vocab, int nosp,
                     void * scratch, NoSpeechOut * out, int32_t tag, hipStream_t st);
 
+// The text scorer (k_score.hip): lp = log soft-max(l)[t] of a decoder row's RAW logits l for a given target t, with the
+// no-speech head's block pass (nsp_block.h: the same bits for m_b and s_b on the same logits), the blocks combined in ascending order:
+// M = max m_b, S = sum_b s_b exp(double(m_b - M)), lp = float(double(float(l[t] - M)) - log(S)) — one rounding to f32; l[t] = -inf gives -inf.
+//   score_rows:   rows.n <= SCORE_MAX_ROWS launch rows; launch row r reads logits + rows.row[r] * ld (several launch rows may read one
+//                 logits row with different targets), its target is targets[r], its result goes to lp[place[r]] (targets, place, lp: device).
+//                 Two launches: blocks (grid = blocks x rows, one wavefront each), combine (one wavefront per row).
+//   score_finish: one workgroup.  Text c owns lp[first[c] .. first[c + 1]): sum in double in ascending order, avg = sum / count,
+//                 v = length_norm ? avg : sum (double), posterior = float(exp(v_c - max v) / sum_c exp(v_c - max v)), the maximum and the sum
+//                 taken over the texts in ascending order in double; v = -inf gives 0, every v = -inf gives 0 everywhere.  rec [n_texts],
+//                 lp_out (optional copy of lp[0 .. first[n_texts])) and out = {n_texts, tag} are stored with plain vector stores, usually
+//                 into pinned host memory.
+// Workgroups are independent inside every launch; no atomics.
+constexpr int SCORE_MAX_ROWS = 8, SCORE_MAX_TEXTS = 4096, SCORE_FINISH_THREADS = 256;
+struct ScoreRows { int n; int row[SCORE_MAX_ROWS]; };
+struct ScoreRec { double sum; float avg, post; int32_t n_scored, first; };      // the layout of wmi_text_score (wmi_device.h)
+struct ScoreOut { int32_t n_texts; int32_t tag; };
+size_t score_scratch_bytes(int n_vocab);                        // the block partials of SCORE_MAX_ROWS rows
+bool score_rows(const float * logits, int ld, const ScoreRows & rows, int n_vocab, const int32_t * targets, const int32_t * place, void * scratch,
+                float * lp, hipStream_t st);
+bool score_finish(const float * lp, const int32_t * first, int n_texts, bool length_norm, ScoreRec * rec, float * lp_out, ScoreOut * out, int32_t tag,
+                  hipStream_t st);
+
 // Token alignment (k_align.hip): DTW over the cross-attention of chosen (layer, head) pairs.  For a pass of n rows over
 // M key frames and a pair (l, h): s[i][t] = sum_{c < 64} q_l[i][64 h + c] k_l[t][64 h + c] (f16 operands as stored — both carry
 // d^-1/4 —, f32 sum), w = soft-max over exactly the first M keys, z = (w - mean) / sigma per (pair, t) over all n rows (population

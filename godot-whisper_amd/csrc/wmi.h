@@ -276,6 +276,18 @@ struct DeviceState {
     k::AlignBufs dtw{}; size_t dtw_cap[7] = {}; void * dtw_host = nullptr; int32_t dtw_seq = 0;
     bool dtw_collect = false, dtw_active = false; int dtw_n_sot = 0, dtw_M = 0;
     int dec_n = 0;                                                     // rows of the last decode() batch (wmi_get_tensor "dec_cross_q")
+    // the text scorer (score.cpp; kernels.h: score_*), all made on first use and grow-only: the block partials, the call's items
+    // {targets | places | text starts} and per-token results on the device, a pinned block {ScoreOut | ScoreRec[texts] | lp[rows] | the items'
+    // staging | the staging blocks of the call's decode() batches}.  score_req asks the next decode() to score its flagged rows where the
+    // vocabulary projection leaves them instead of copying them out, a request for this call only: item i reads flagged row item_row[i]
+    // (ascending; several items may read one row) with target d_target[i] into score_lp[d_place[i]].  staging: pinned memory for that
+    // batch's tokens | positions | rows | mask (no wait separates the call's batches, so each has a block of its own).  logits_out (tests):
+    // the row item i saw goes to logits_out + place[i] * n_vocab
+    struct ScoreReq { const int32_t * item_row = nullptr; int n_items = 0; const int32_t * d_target = nullptr, * d_place = nullptr;
+                      void * staging = nullptr; size_t staging_bytes = 0; float * logits_out = nullptr; const int32_t * place = nullptr; };
+    void * score_scratch = nullptr; int32_t * score_items = nullptr; size_t score_items_cap = 0; float * score_lp = nullptr; size_t score_lp_cap = 0;
+    void * score_host = nullptr; size_t score_host_cap = 0; int32_t score_seq = 0;
+    const ScoreReq * score_req = nullptr;
 };
 
 struct State {
@@ -296,6 +308,7 @@ struct State {
     // the last window aligned on this state (wmi_token_dtw_dims; the tensors stay in dev.dtw until the next one), the alignment's own timer
     struct DtwDims { int n = 0, n_sot = 0, R = 0, M = 0, n_pairs = 0; } dtw_last; std::vector<int32_t> dtw_jumps;
     int64_t t_dtw_us = 0; int32_t n_dtw = 0;
+    int64_t t_score_us = 0; int32_t n_score = 0, n_score_launches = 0;     // the text scorer's own timer: calls, and launches of its kernels (wmi_get_score_timings)
     // wmi_grammar_status: sampling steps whose reject masks k_grammar_reject wrote / rows whose mask the host computed instead, since the
     // start of the last transcription call
     int32_t gram_steps_dev = 0, gram_rows_host = 0; float gram_reject_us = 0.0f;      // (the last wmi_selftest_grammar launch, by events)
@@ -476,7 +489,7 @@ void enqueue_rows_step_q(whisper_context & ctx, int nb);
 void enqueue_rows_lang_step_q(whisper_context & ctx, int nb, float * out);      // the same step ending in the language head (batch.cpp: detection)
 // nsp_row_dev (device, one batch row index): that row's raw logits also go to nsp_logits (the no-speech head reads them there)
 bool decode_layers_q(whisper_context & ctx, int n, int n_kv, int kv_head, int Tc, const std::vector<int> & rows, float * lang_out = nullptr,
-                     const int32_t * nsp_row_dev = nullptr, float * nsp_logits = nullptr);
+                     const int32_t * nsp_row_dev = nullptr, float * nsp_logits = nullptr, const DeviceState::ScoreReq * score = nullptr);
 void enqueue_greedy_step_q(whisper_context & ctx, int Tc);
 // The grammar on the device (wmi_set_grammar_device; grammar_eval.h, k_grammar.hip).  grammar_flatten: the rules as one element array
 // (ok = false: malformed or too long — the host's logic serves such a grammar); grammar_row_state: a decoder's stacks and partial
@@ -535,6 +548,18 @@ bool dtw_ensure(DeviceState & d, int nh, int n, int R, int M, int n_pairs);
 bool dtw_layer(whisper_context & ctx, int il, int n, int Tc);
 bool dtw_window(whisper_context & ctx, const std::vector<int32_t> & x, int n_sot, int M);
 void dtw_path_host(int R, int M, const float * A, int32_t * jumps, int32_t * path, int * n_path);
+// The text scorer (score.cpp; kernels.h: score_*).  score_plan is pure host arithmetic: the prefix, per text its first entry
+// in the per-token results (first [n_texts + 1]), the items on the prefix's last row (item c = text c: target y_0 or <eot>, place first[c]) and
+// the candidate passes — texts [c0, c1) whole, at most n_text_ctx rows, the prefix plus the rows within the self cache; per row the token,
+// the position P + i, the sequence id c + 1, and for a row that predicts something its target and place.  Returns 0, -1 for a bad argument.
+// score_group is decode()'s hook behind the vocabulary projection of the flagged rows [r0, r0 + nr): the launches of the items on them.
+// score_texts runs a call: one wait, behind score_finish.  Returns 0, -1 bad argument, -2 no encoder result / no compute path, -3 device error.
+struct ScorePass { int c0 = 0, c1 = 0; std::vector<int32_t> token, pos, seq, target, place; std::vector<int8_t> flag; };
+struct ScorePlan { std::vector<int32_t> prefix, first, prefix_target; std::vector<ScorePass> passes; };
+int  score_plan(const Vocab & v, const HParams & hp, size_t kv_cells, const wmi_score_params & p, const int32_t * tokens, const int32_t * n_tokens, int n_texts, ScorePlan & out);
+bool score_group(whisper_context & ctx, const DeviceState::ScoreReq & rq, int r0, int nr, int & item);
+int  score_texts(whisper_context & ctx, const wmi_score_params & p, const int32_t * tokens, const int32_t * n_tokens, int n_texts, wmi_text_score * out,
+                 float * token_logprobs, float * logits_out);
 // k draws per row from the filtered distribution of logits row `rows[r]` of the last decode() (keep_logits_on_device), r < n_rows <= 8;
 // u [n_rows][k] uniform numbers in [0, 1) from the decoders' generators.  out [n_rows][k].
 bool sample_rows_device(whisper_context & ctx, const StepFilter * f, const int * rows, int n_rows, float temperature, int k,

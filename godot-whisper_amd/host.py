@@ -157,6 +157,42 @@ class SpeechToText:
             return []  # ERR_PRINT("Failed to process audio, returned ...")
         return self.collect()
 
+    # -- not in the reference: candidate texts scored against the audio (include/wmi_device.h: wmi_score_pcm).  The reference's guided mode
+    # (examples/command/command.cpp:254-462) sums the probabilities of each command's FIRST token; this scores every token of every text.
+    def tokenize(self, text: str) -> list:
+        b = text.encode("utf-8")
+        buf = (C.c_int32 * (len(b) + 8))()
+        n = self.lib.whisper_tokenize(self.ctx, b, buf, len(buf))
+        return list(buf[:max(n, 0)])
+
+    def score(self, pcm: np.ndarray, texts: list, prompt=None, length_norm: bool = False, audio_ctx: int = 0) -> list:
+        """-> per text {text, tokens, token_logprobs, sum_logprob, avg_logprob, posterior}; every text is tokenized with a leading
+        space, as command.cpp:276 insists.  Leaves the list in last_scores and the return code in last_ret; [] on an error."""
+        self.last_scores = []
+        if not self.ctx:
+            return []
+        pcm = np.ascontiguousarray(pcm, dtype=np.float32)
+        toks = [self.tokenize(" " + t) for t in texts]
+        p = self.lib.wmi_score_default_params()
+        p.length_norm = int(bool(length_norm))
+        if self.lib.whisper_is_multilingual(self.ctx):
+            p.lang_id = max(0, self.lib.whisper_lang_id(self.language.encode()))          # ("auto": English, nothing is detected here)
+        pt = np.asarray(self.tokenize(prompt) if prompt else [], np.int32)
+        if pt.size:
+            p.prompt_tokens = pt.ctypes.data_as(C.POINTER(C.c_int32)); p.prompt_n_tokens = int(pt.size)
+        flat = np.asarray([t for y in toks for t in y], np.int32)
+        nt = np.asarray([len(y) for y in toks], np.int32)
+        out = (abi.wmi_text_score * max(1, len(texts)))()
+        lp = np.zeros(int(nt.sum()) + len(texts), np.float32)
+        self.last_ret = self.lib.wmi_score_pcm(self.ctx, p, pcm.ctypes.data_as(C.c_void_p), int(pcm.size), 0, int(audio_ctx),
+                                               flat.ctypes.data_as(C.c_void_p) if flat.size else None, nt.ctypes.data_as(C.c_void_p), len(texts), out,
+                                               lp.ctypes.data_as(C.c_void_p))
+        if self.last_ret != 0:
+            return []
+        self.last_scores = [{"text": t, "tokens": y, "token_logprobs": lp[o.first:o.first + o.n_scored].tolist(), "sum_logprob": o.sum_logprob,
+                             "avg_logprob": o.avg_logprob, "posterior": o.posterior} for t, y, o in zip(texts, toks, out)]
+        return self.last_scores
+
     def collect(self) -> list:
         out, full_text = [], b""
         lib, ctx = self.lib, self.ctx

@@ -5,6 +5,7 @@
 //       language = mix rate, prompt = interpolator type: prints the frame count, an FNV-1a hash of the frames' bits and the error string)
 //       | capture (pcm file = interleaved stereo frames; language = mix rate, prompt = "session" or "calls", audio_ctx = the largest number of
 //       transcribe calls: the node's own loop, CaptureStreamToText::stream_capture)
+//       | score (initial_prompt = the candidate texts with '|' between them: SpeechToText::score_texts)
 // Prints one JSON document on stdout.  pcm.f32: raw little-endian float32 mono 16 kHz; for `batch` the file starts with
 // int32 n, then n x int32 lengths, then the buffers back to back.
 #include "speech_to_text.h"
@@ -124,6 +125,22 @@ int main(int argc, char ** argv) {
         printf("{\"transcription\": "); json_transcription(node.transcribe_long(pcm, prompt, &lp));
         printf(", \"pieces\": [");
         for (size_t i = 0; i < node.last_pieces.size(); ++i) printf("%s[%d, %d]", i ? ", " : "", node.last_pieces[i].frame0, node.last_pieces[i].frame1);
+        printf("]}\n");
+        return 0;
+    }
+    if (mode == "score") {                                    // prompt = the candidate texts, '|' between them; audio_ctx as for transcribe
+        std::vector<std::string> texts(1);
+        for (char c : prompt) { if (c == '|') texts.emplace_back(); else texts.back().push_back(c); }
+        const auto res = node.score_texts(pcm, texts, "", false, audio_ctx);
+        printf("{\"ret\": %d, \"scores\": [", node.last_return);
+        for (size_t i = 0; i < res.size(); ++i) {
+            printf("%s{\"text\": ", i ? ", " : ""); json_string(res[i].text);
+            printf(", \"tokens\": [");
+            for (size_t j = 0; j < res[i].tokens.size(); ++j) printf("%s%d", j ? ", " : "", res[i].tokens[j]);
+            printf("], \"token_logprobs\": [");
+            for (size_t j = 0; j < res[i].token_logprobs.size(); ++j) printf("%s%.9g", j ? ", " : "", res[i].token_logprobs[j]);
+            printf("], \"sum_logprob\": %.17g, \"avg_logprob\": %.9g, \"posterior\": %.9g}", res[i].sum_logprob, res[i].avg_logprob, res[i].posterior);
+        }
         printf("]}\n");
         return 0;
     }

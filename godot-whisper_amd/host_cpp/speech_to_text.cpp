@@ -125,6 +125,52 @@ Transcription SpeechToText::collect() const {                            // src/
     return out;
 }
 
+std::vector<SpeechToText::TextScore> SpeechToText::score_texts(const std::vector<float> & buffer, const std::vector<std::string> & texts,
+                                                               const std::string & prompt, bool length_norm, int audio_ctx) {
+    std::vector<TextScore> res;
+    if (!context_instance) {
+        fprintf(stderr, "ERROR: Context instance is null\n");
+        return res;
+    }
+    auto tokenize = [&](const std::string & t) {
+        std::vector<whisper_token> ids(t.size() + 8);
+        const int n = whisper_tokenize(context_instance, t.c_str(), ids.data(), (int) ids.size());
+        ids.resize(n > 0 ? n : 0);
+        return ids;
+    };
+    std::vector<TextScore> all(texts.size());
+    std::vector<whisper_token> flat;
+    std::vector<int32_t> n_tokens;
+    for (size_t c = 0; c < texts.size(); ++c) {
+        all[c].text = texts[c];
+        const auto ids = tokenize(" " + texts[c]);
+        all[c].tokens.assign(ids.begin(), ids.end());
+        flat.insert(flat.end(), ids.begin(), ids.end());
+        n_tokens.push_back((int32_t) ids.size());
+    }
+    wmi_score_params p = wmi_score_default_params();
+    p.length_norm = length_norm ? 1 : 0;
+    if (whisper_is_multilingual(context_instance)) {
+        const int id = whisper_lang_id(language_to_code(language));
+        p.lang_id = id > 0 ? id : 0;                                      // ("auto": English, nothing is detected here)
+    }
+    const std::vector<whisper_token> pt = prompt.empty() ? std::vector<whisper_token>() : tokenize(prompt);
+    if (!pt.empty()) { p.prompt_tokens = pt.data(); p.prompt_n_tokens = (int32_t) pt.size(); }
+    std::vector<wmi_text_score> out(texts.size() ? texts.size() : 1);
+    std::vector<float> lp(flat.size() + texts.size() + 1);
+    last_return = wmi_score_pcm(context_instance, p, buffer.data(), (int) buffer.size(), 0, audio_ctx, flat.empty() ? nullptr : flat.data(),
+                                n_tokens.data(), (int) texts.size(), out.data(), lp.data());
+    if (last_return != 0) {
+        fprintf(stderr, "ERROR: Failed to score the texts, returned %d\n", last_return);
+        return res;
+    }
+    for (size_t c = 0; c < texts.size(); ++c) {
+        all[c].token_logprobs.assign(lp.begin() + out[c].first, lp.begin() + out[c].first + out[c].n_scored);
+        all[c].sum_logprob = out[c].sum_logprob; all[c].avg_logprob = out[c].avg_logprob; all[c].posterior = out[c].posterior;
+    }
+    return all;
+}
+
 Transcription SpeechToText::transcribe(const std::vector<float> & buffer, const std::string & initial_prompt, int audio_ctx) {
     const whisper_full_params whisper_params = make_params(initial_prompt, audio_ctx);
     if (!context_instance) {

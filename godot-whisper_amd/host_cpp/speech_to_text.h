@@ -93,6 +93,13 @@ public:
                                   const wmi_long_params * long_params = nullptr);
     std::vector<wmi_long_piece> last_pieces;
 
+    // not in the reference: candidate texts scored against the audio in one teacher-forced pass (include/wmi_device.h: wmi_score_pcm) — per
+    // text the log-probability of every token and of the whole text, and the posterior over the texts.  Every text is tokenized with a
+    // leading space (examples/command/command.cpp:276).  An empty result: an error, its code in last_return.
+    struct TextScore { std::string text; std::vector<int32_t> tokens; std::vector<float> token_logprobs; double sum_logprob = 0.0; float avg_logprob = 0.0f, posterior = 0.0f; };
+    std::vector<TextScore> score_texts(const std::vector<float> & buffer, const std::vector<std::string> & texts, const std::string & prompt = "",
+                                       bool length_norm = false, int audio_ctx = 0);
+
     whisper_context * context() { return context_instance; }
     int last_return = 0;          // whisper_full's code of the last transcribe()
     std::vector<int> last_langs;  // transcribe_batch: per chunk the language id whisper_full would report (the detected one with Language "auto")

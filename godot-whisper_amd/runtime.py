@@ -135,6 +135,16 @@ DEVICE_API = [
     ("wmi_selftest_grammar", C.c_int, [C.c_void_p, abi.whisper_full_params, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("wmi_selftest_grammar_sample", C.c_int, [C.c_void_p, abi.whisper_full_params, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    ("wmi_score_default_params", abi.wmi_score_params, []),
+    ("wmi_score_texts", C.c_int, [C.c_void_p, abi.wmi_score_params, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(abi.wmi_text_score), C.c_void_p]),
+    ("wmi_score_texts_with_state", C.c_int, [C.c_void_p, C.c_void_p, abi.wmi_score_params, C.c_void_p, C.c_void_p, C.c_int,
+                                             C.POINTER(abi.wmi_text_score), C.c_void_p, C.c_void_p]),
+    ("wmi_score_pcm", C.c_int, [C.c_void_p, abi.wmi_score_params, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                C.POINTER(abi.wmi_text_score), C.c_void_p]),
+    ("wmi_get_score_timings", None, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    ("wmi_selftest_score_rows", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("wmi_selftest_score_plan", C.c_int, [C.c_void_p, abi.wmi_score_params, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                          C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_int]),
     ("wmi_long_default_params", abi.wmi_long_params, []),
     ("wmi_full_long", C.c_int, [C.c_void_p, abi.whisper_full_params, C.c_void_p, C.c_int, C.c_int, C.POINTER(abi.wmi_long_params)]),
     ("wmi_long_n_pieces", C.c_int, [C.c_void_p]),

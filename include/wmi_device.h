@@ -744,6 +744,76 @@ WHISPER_API int  wmi_selftest_long_window(int n_samples, int offset_ms, int dura
 WHISPER_API int  wmi_selftest_long_plan(const float * e, int F, int n_samples, const struct wmi_long_params * long_params, int n_audio_ctx,
                                         struct wmi_long_piece * out, int cap);
 
+/* Score candidate texts against the audio in one teacher-forced pass: "which of my N commands was said?", N-best rescoring, or a
+ * confidence for a transcript the caller already has.  Given the encoder result in the state and n_texts token sequences, per text the
+ * log-probability of every token and of the whole text, and the posterior over the call's texts — two decoder batches (the prefix, then all
+ * texts side by side as sequences of the unified self cache) and ONE host wait, whatever the texts' lengths.
+ * Prefix, as whisper_full builds a window's prompt: [<|startofprev|>, the last n_text_ctx / 2 - 1 prompt tokens] only when prompt tokens are
+ * passed, <sot>, on multilingual models the language and the task token, <|notimestamps|>: P rows at positions 0 .. P - 1.
+ * A text y_0 .. y_{n-1} (every id < eot, n >= 0) has n + 1 scored rows with with_eot (the default), n without: the prefix's last row predicts
+ * y_0, input y_i at position P + i predicts y_{i+1}, input y_{n-1} predicts <eot>; n = 0 is legal only with with_eot and scores <eot> at the
+ * prefix row.  Per scored row, on the RAW f32 logits l of the vocabulary projection (no temperature, no filter, no ban) with target t: the
+ * no-speech head's block pass (blocks of 128 entries: m_b = max l, s_b = sum exp(l - m_b), the difference in f32, exp and sums in double,
+ * an entry of -inf adds 0), the blocks combined in ascending order, M = max m_b, S = sum_b s_b exp(m_b - M), and
+ * lp = f32(double(f32(l[t] - M)) - log(S)), rounded to f32 once; l[t] = -inf gives -inf.  Per text: sum_logprob = the sum of its lp in double
+ * in ascending row order, avg_logprob = sum / count, posterior = exp(v_c - max v) / sum_c exp(v_c - max v) in double, the texts in ascending
+ * order, rounded to f32, v = sum_logprob or (length_norm) sum / count; a text with v = -inf has posterior 0, and so has every text when all are -inf.
+ * The same call twice gives the same bits (csrc/k_score.hip).
+ *   wmi_score_texts    tokens: the texts' ids one text after the other, n_tokens [n_texts].  out [n_texts]; token_logprobs (may be NULL) holds
+ *                      the sum of the texts' n_scored values, text c's from out[c].first on.  Needs an encoder result in the state: from
+ *                      whisper_encode, any whisper_full*, or wmi_score_pcm.  Texts are split over several candidate passes, each text whole,
+ *                      when their rows exceed n_text_ctx.  Afterwards the self cache holds the scoring rows, not a decoding step's (as after an
+ *                      alignment pass), and whisper_get_logits() is what it was.
+ *   wmi_score_pcm      log-mel and encoder of the window at seek 0 of pcm (audio_ctx = 0: the model's), then wmi_score_texts.
+ *   wmi_get_score_timings   the scorer's own timer: us (plan, batches, kernels and the one wait), calls, launches of its kernels — not part
+ *                      of wmi_get_timings, to which a scoring call adds nothing beyond wmi_score_pcm's log-mel and encoder pass.
+ * Off unless called: a context that never scores allocates and launches nothing for it.
+ * Returns 0; -1 no context / state, or a bad argument, nothing launched: NULL lists, n_texts < 1 or > 4096, an id < 0 or >= eot, a negative
+ * length, an empty text without with_eot, a text longer than n_text_ctx - P, a language id out of range, a prompt id outside the vocabulary;
+ * -2 no compute path (host-only context) or no encoder result in the state; -3 device error.
+ * Not measured here: ranking quality on real models — only synthetic weights exist in this repository. */
+struct wmi_score_params {
+    int32_t lang_id;                       /* multilingual models: the language token's index (whisper_lang_id) */
+    int32_t translate;                     /* multilingual models: the task token */
+    const whisper_token * prompt_tokens;   /* NULL: no [<|startofprev|> ...] context */
+    int32_t prompt_n_tokens;
+    int32_t with_eot;                      /* score <eot> behind the last token (default 1) */
+    int32_t length_norm;                   /* the posterior over avg_logprob instead of sum_logprob (default 0) */
+};
+struct wmi_text_score {
+    double  sum_logprob;
+    float   avg_logprob;
+    float   posterior;
+    int32_t n_scored;                      /* entries of token_logprobs that belong to the text */
+    int32_t first;                         /* index of the first of them */
+};
+WHISPER_API struct wmi_score_params wmi_score_default_params(void);
+WHISPER_API int  wmi_score_texts(struct whisper_context * ctx, struct wmi_score_params params, const whisper_token * tokens, const int32_t * n_tokens,
+                                 int n_texts, struct wmi_text_score * out, float * token_logprobs);
+/* the same on a caller-owned state (NULL: the context's own), under that state's lock; logits_out (tests, may be NULL): [sum of n_scored][n_vocab], the logits row
+ * every entry of token_logprobs was taken from */
+WHISPER_API int  wmi_score_texts_with_state(struct whisper_context * ctx, struct whisper_state * state, struct wmi_score_params params,
+                                            const whisper_token * tokens, const int32_t * n_tokens, int n_texts, struct wmi_text_score * out,
+                                            float * token_logprobs, float * logits_out);
+WHISPER_API int  wmi_score_pcm(struct whisper_context * ctx, struct wmi_score_params params, const float * pcm, int n_samples, int pcm_on_device,
+                               int audio_ctx, const whisper_token * tokens, const int32_t * n_tokens, int n_texts, struct wmi_text_score * out,
+                               float * token_logprobs);
+WHISPER_API void wmi_get_score_timings(struct whisper_context * ctx, int64_t * us, int32_t * n_calls, int32_t * n_launches);
+/* Test hooks.
+ *   wmi_selftest_score_rows   the scoring kernels on caller data (no context; host pointers): logits [rows][n_vocab] f32, targets [rows] in
+ *                             [0, n_vocab), lp_out [rows]; rows >= 1 in groups of 8 as decode() groups its flagged rows, 1 <= n_vocab <= 65536.
+ *                             Returns 0; -1 bad argument, before the device is touched; -2 / -3 device errors.
+ *   wmi_selftest_score_plan   the plan of a call (host only: works on a wmi_init_host_only context).  prefix: up to cap_prefix ids, *n_prefix
+ *                             their count; first [n_texts + 1]; prefix_target [n_texts]: the targets on the prefix's last row (text c's at
+ *                             place first[c]); rows [cap_rows][7]: {pass, token, position, sequence id, flag, target, place} of every batch
+ *                             row of every pass in order (target = place = -1 for a row that predicts nothing), *n_rows their count (which
+ *                             may exceed cap_rows); pass_text0 [n_passes + 1 <= cap_passes]: the first text of every pass.  Returns the
+ *                             number of passes, -1 for a bad argument (wmi_score_texts' list). */
+WHISPER_API int  wmi_selftest_score_rows(int device, int rows, int n_vocab, const float * logits, const int32_t * targets, float * lp_out);
+WHISPER_API int  wmi_selftest_score_plan(struct whisper_context * ctx, struct wmi_score_params params, const whisper_token * tokens,
+                                         const int32_t * n_tokens, int n_texts, int32_t * prefix, int cap_prefix, int * n_prefix, int32_t * first,
+                                         int32_t * prefix_target, int32_t * rows, int cap_rows, int * n_rows, int32_t * pass_text0, int cap_passes);
+
 /* Host worker pool self-test (no device needed): `reps` jobs of `n_tasks` tasks; returns reps * n_tasks * (n_tasks + 1) / 2
  * when every task of every job ran exactly once. */
 WHISPER_API int64_t wmi_selftest_pool(int n_tasks, int reps);
