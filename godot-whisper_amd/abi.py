@@ -201,6 +201,14 @@ class wmi_long_piece(C.Structure):  # include/wmi_device.h: one piece of the las
                 ("i_segment", C.c_int32), ("n_segments", C.c_int32)]
 
 
+WMI_WAV_S8, WMI_WAV_S16, WMI_WAV_F32 = 0, 1, 32  # include/wmi_device.h; 0 / 1 = AudioStreamWAV.FORMAT_8_BITS / FORMAT_16_BITS
+
+
+class wmi_wav(C.Structure):  # include/wmi_device.h: the data bytes of an AudioStreamWAV and what they hold (wmi_wav_to_pcm, wmi_full_*_wav)
+    _fields_ = [("data", C.c_void_p), ("n_bytes", C.c_longlong), ("format", C.c_int), ("stereo", C.c_int), ("mix_rate", C.c_int),
+                ("on_device", C.c_int)]
+
+
 class wmi_grammar_status(C.Structure):  # include/wmi_device.h: the counters and capacities of the grammar's device route (wmi_set_grammar_device)
     _fields_ = [("steps_device", C.c_int32), ("rows_host", C.c_int32), ("cap_stacks", C.c_int32), ("cap_depth", C.c_int32),
                 ("cap_words", C.c_int32), ("reject_us", C.c_float)]

@@ -119,6 +119,7 @@ void whisper_free(struct whisper_context * ctx) {
     for (float * t : ctx->d_sinc) if (t) (void) hipFree(t);
     if (ctx->vad_res) (void) hipHostFree(ctx->vad_res);
     if (ctx->dsp_scratch) (void) hipFree(ctx->dsp_scratch);
+    free_wav(*ctx);
     delete ctx;
 }
 

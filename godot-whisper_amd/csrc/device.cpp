@@ -274,7 +274,10 @@ bool pcm_to_mel(whisper_context & ctx, const float * samples, int n_samples, boo
     const float * src = samples;
     if (!samples_on_device) {                      // stage the borrowed host PCM behind the padded image
         float * stage = d.pcm + n_pad;
-        HIP_TRY(hipMemcpyAsync(stage, samples, (size_t) n_samples * 4, hipMemcpyHostToDevice, ms));
+        if (WavJob * job = d.pcm_job) {            // wmi_full_wav: the samples are decoded / resampled straight into the staging area
+            d.pcm_job = nullptr;
+            if (!wav_job_run(ctx, *job, stage, ms)) return false;
+        } else HIP_TRY(hipMemcpyAsync(stage, samples, (size_t) n_samples * 4, hipMemcpyHostToDevice, ms));
         src = stage;
     }
     d.last_pcm = src; d.last_pcm_n = n_samples;

@@ -23,8 +23,13 @@
 // is in[pos_n - 1] held, or in[pos_n - 1] + frac_n * (in[pos_n] - in[pos_n - 1]) with an f32 difference and a separate f64 multiply
 // and add; while pos_n is still 0 both give in[0] (their last_value).  They stop at the capacity or when the position runs off the
 // input (plan_simple), which is also what keeps every read inside the array.
+//
+// What an input frame is read from is a template parameter (kernels.h SrcKind, in_frame<KIND>): a mono f32 buffer, the capture session's
+// f32 stereo frames, or the packed s16 / s8 frames of an AudioStreamWAV, mono or stereo (wav_frame.h: decode and fold per tap).  Plan,
+// positions, tap order and accumulators do not depend on it: the output equals that of a mono f32 buffer decoded first, bit for bit.
 
 #include "kernels.h"
+#include "wav_frame.h"
 #include <cmath>
 #include <cstring>
 #include <algorithm>
@@ -46,16 +51,23 @@ struct ResampleArgs {
     int increment;
     unsigned long long m; int sh; double frac_scale;          // closed form: position n = (n * m) >> sh, fraction = low bits * 2^-sh
     const int * pos_tab; const double * frac_tab;             // or the host's recurrence
-    const float2 * in2;                                       // STEREO forms: the capture frames themselves (in is unused)
+    const float2 * in2;                                       // SRC_F32_STEREO: the capture frames themselves (in is unused)
     long long n0;                                             // the launch computes outputs [n0, n_out)
+    const void * raw;                                         // the packed-frame kinds: the frames as an AudioStreamWAV holds them
 };
 
+// f32 stereo frames that start on a 4-byte boundary only (a device source one sample off its frame grid): two loads instead of a float2
+constexpr int SRC_F32_STEREO_U = 6;
+
 // input frame i: the mono sample, or the capture frame folded exactly as k_downmix folds it (a float add, then an exact halving) —
-// the same bits as a mono buffer written first, without writing one
-template <bool STEREO>
+// the same bits as a mono buffer written first, without writing one.  The packed integer kinds (SrcKind) decode the frame first
+// (wav_frame.h): no f32 image of the input exists anywhere.
+template <int KIND>
 __device__ __forceinline__ float in_frame(const ResampleArgs & a, long long i) {
-    if (STEREO) { const float2 f = a.in2[i]; return (float) ((double) (f.x + f.y) / 2.0); }
-    return a.in[i];
+    if (KIND == SRC_F32_STEREO) { const float2 f = a.in2[i]; return (float) ((double) (f.x + f.y) / 2.0); }
+    if (KIND == SRC_F32_MONO) return a.in[i];
+    if (KIND == SRC_F32_STEREO_U) return wav_frame<SRC_F32_STEREO>(a.raw, i);
+    return wav_frame<KIND>(a.raw, i);
 }
 
 // where output n sits on the input: the host's table, or integer and fractional part of n * m * 2^-sh
@@ -73,7 +85,7 @@ __device__ __forceinline__ void out_position(const ResampleArgs & a, long long n
     *pos_out = pos; *frac_out = frac;
 }
 
-template <bool STEREO>
+template <int KIND>
 __global__ __launch_bounds__(256) void k_resample(const ResampleArgs a) {
     const long long n = a.n0 + (long long) blockIdx.x * 256 + threadIdx.x;
     if (n >= a.n_out) return;
@@ -97,7 +109,7 @@ __global__ __launch_bounds__(256) void k_resample(const ResampleArgs a) {
         const float c0 = c[ix], c1 = c[ix + 1];
         const double ic = (double) c0 + fraction * (double) (c1 - c0);
         const long long dc = di < 0 ? 0 : (di > last ? last : di);
-        float v = in_frame<STEREO>(a, dc);
+        float v = in_frame<KIND>(a, dc);
         v = (di < 0 || di > last) ? 0.0f : v;                 // zero history before the first sample, zero tail after the last
         left += ic * (double) v;
         fi -= increment;
@@ -116,7 +128,7 @@ __global__ __launch_bounds__(256) void k_resample(const ResampleArgs a) {
         const float c0 = c[ix], c1 = c[ix + 1];
         const double ic = (double) c0 + fraction * (double) (c1 - c0);
         const long long dc = di > last ? last : di;
-        float v = in_frame<STEREO>(a, dc);
+        float v = in_frame<KIND>(a, dc);
         v = di > last ? 0.0f : v;
         right += ic * (double) v;
         fi -= increment;
@@ -128,7 +140,7 @@ __global__ __launch_bounds__(256) void k_resample(const ResampleArgs a) {
 
 // SRC_ZERO_ORDER_HOLD (LINEAR = false, src_zoh.c:80, :99) and SRC_LINEAR (src_linear.c:82-83, :107-108).  The plan emits output n only
 // while pos_n - 1 (and pos_n for LINEAR) are frames of the input; the clamp keeps a wrong plan from reading outside it.
-template <bool LINEAR, bool STEREO>
+template <bool LINEAR, int KIND>
 __global__ __launch_bounds__(256) void k_resample_simple(const ResampleArgs a) {
     const long long n = a.n0 + (long long) blockIdx.x * 256 + threadIdx.x;
     if (n >= a.n_out) return;
@@ -136,10 +148,10 @@ __global__ __launch_bounds__(256) void k_resample_simple(const ResampleArgs a) {
     out_position(a, n, &pos, &frac);
     const long long last = a.n_in - 1;
     const long long i0 = pos <= 0 ? 0 : (pos - 1 > last ? last : pos - 1);     // pos 0: last_value = in[0]
-    const float v0 = in_frame<STEREO>(a, i0);
+    const float v0 = in_frame<KIND>(a, i0);
     if (!LINEAR) { a.out[n] = v0; return; }
     const long long i1 = pos <= 0 ? 0 : (pos > last ? last : pos);
-    const float d = in_frame<STEREO>(a, i1) - v0;                                               // float difference, then double multiply and add
+    const float d = in_frame<KIND>(a, i1) - v0;                                               // float difference, then double multiply and add
     a.out[n] = (float) ((double) v0 + frac * (double) d);
 }
 
@@ -335,38 +347,53 @@ void resample_positions(const ResamplePlan & pl, long long n, long long * pos, d
     for (long long i = 0; i < n; ++i) pl.stepper->at(i, pos + i, frac + i);
 }
 
-static void launch(const ResamplePlan & pl, const float * d_in, const float * d_frames_xy, long long n_in, float * d_out, const float * d_coeffs,
+template <int KIND>
+static void launch_as(const ResamplePlan & pl, const dim3 grid, const ResampleArgs & a, hipStream_t st) {
+    if (pl.converter == 3) hipLaunchKernelGGL((k_resample_simple<false, KIND>), grid, dim3(256), 0, st, a);
+    else if (pl.converter == 4) hipLaunchKernelGGL((k_resample_simple<true, KIND>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((k_resample<KIND>), grid, dim3(256), 0, st, a);
+}
+
+static void launch(const ResamplePlan & pl, int kind, const void * d_src, long long n_in, float * d_out, const float * d_coeffs,
                    const int * d_pos, const double * d_frac, long long first, hipStream_t st) {
     if (first < 0) first = 0;
     if (pl.n_out <= first) return;
+    if (kind == SRC_F32_STEREO && ((uintptr_t) d_src & 7)) kind = SRC_F32_STEREO_U;
     ResampleArgs a;
-    a.in = d_in; a.in2 = (const float2 *) d_frames_xy; a.n_in = n_in; a.out = d_out; a.n_out = pl.n_out; a.n0 = first;
+    a.in = kind == SRC_F32_MONO ? (const float *) d_src : nullptr; a.in2 = kind == SRC_F32_STEREO ? (const float2 *) d_src : nullptr;
+    a.raw = kind >= SRC_S16_MONO ? d_src : nullptr;
+    a.n_in = n_in; a.out = d_out; a.n_out = pl.n_out; a.n0 = first;
     a.coeffs = d_coeffs; a.half_len = pl.half_len;
     a.float_inc = pl.float_inc; a.out_scale = pl.out_scale; a.increment = pl.increment;
     a.m = pl.stepper->m; a.sh = pl.stepper->sh; a.frac_scale = ldexp(1.0, -pl.stepper->sh);
     a.pos_tab = pl.need_table ? d_pos : nullptr; a.frac_tab = pl.need_table ? d_frac : nullptr;
     const dim3 grid((unsigned) ((pl.n_out - first + 255) / 256));
-    const bool stereo = d_frames_xy != nullptr;
-    if (pl.converter == 3) {
-        if (stereo) hipLaunchKernelGGL((k_resample_simple<false, true>), grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((k_resample_simple<false, false>), grid, dim3(256), 0, st, a);
-    } else if (pl.converter == 4) {
-        if (stereo) hipLaunchKernelGGL((k_resample_simple<true, true>), grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((k_resample_simple<true, false>), grid, dim3(256), 0, st, a);
-    } else {
-        if (stereo) hipLaunchKernelGGL((k_resample<true>), grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((k_resample<false>), grid, dim3(256), 0, st, a);
+    switch (kind) {
+        case SRC_F32_MONO:     launch_as<SRC_F32_MONO>(pl, grid, a, st); break;
+        case SRC_F32_STEREO:   launch_as<SRC_F32_STEREO>(pl, grid, a, st); break;
+        case SRC_S16_MONO:     launch_as<SRC_S16_MONO>(pl, grid, a, st); break;
+        case SRC_S16_STEREO:   launch_as<SRC_S16_STEREO>(pl, grid, a, st); break;
+        case SRC_S8_MONO:      launch_as<SRC_S8_MONO>(pl, grid, a, st); break;
+        case SRC_S8_STEREO:    launch_as<SRC_S8_STEREO>(pl, grid, a, st); break;
+        case SRC_F32_STEREO_U: launch_as<SRC_F32_STEREO_U>(pl, grid, a, st); break;
+        default: break;
     }
 }
 
 void resample_launch(const ResamplePlan & pl, const float * d_in, long long n_in, float * d_out, const float * d_coeffs,
                      const int * d_pos, const double * d_frac, hipStream_t st) {
-    launch(pl, d_in, nullptr, n_in, d_out, d_coeffs, d_pos, d_frac, 0, st);
+    launch(pl, SRC_F32_MONO, d_in, n_in, d_out, d_coeffs, d_pos, d_frac, 0, st);
 }
 
 void resample_launch_stereo(const ResamplePlan & pl, const float * d_frames_xy, long long n_in, float * d_out, const float * d_coeffs,
                             const int * d_pos, const double * d_frac, long long first, hipStream_t st) {
-    launch(pl, nullptr, d_frames_xy, n_in, d_out, d_coeffs, d_pos, d_frac, first, st);
+    launch(pl, SRC_F32_STEREO, d_frames_xy, n_in, d_out, d_coeffs, d_pos, d_frac, first, st);
+}
+
+void resample_launch_kind(const ResamplePlan & pl, int kind, const void * d_src, long long n_in, float * d_out, const float * d_coeffs,
+                          const int * d_pos, const double * d_frac, long long first, hipStream_t st) {
+    if (kind < SRC_F32_MONO || kind > SRC_S8_STEREO) return;
+    launch(pl, kind, d_src, n_in, d_out, d_coeffs, d_pos, d_frac, first, st);
 }
 
 // Output k of a plan does not depend on the input length as long as every frame it reads exists: its position comes from k alone and the

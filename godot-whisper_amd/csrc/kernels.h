@@ -176,6 +176,20 @@ void resample_launch(const ResamplePlan & pl, const float * d_in, long long n_in
 void resample_launch_stereo(const ResamplePlan & pl, const float * d_frames_xy, long long n_in, float * d_out, const float * d_coeffs,
                             const int * d_pos, const double * d_frac, long long first, hipStream_t st);
 long long resample_first_dirty(const ResamplePlan & old_pl, long long n_old, const ResamplePlan & new_pl);
+// What a resampler input frame is read from (in_frame<KIND>, k_resample.hip): the two f32 forms above, and the packed integer frames of an
+// AudioStreamWAV (k_wav.hip has the decode: s16 / 32768, s8 / 128, little-endian, a stereo frame folded as downmix_stereo folds it).
+// The integer kinds need only sample alignment (2 bytes for s16, none for s8).
+enum SrcKind : int { SRC_F32_MONO = 0, SRC_F32_STEREO = 1, SRC_S16_MONO = 2, SRC_S16_STEREO = 3, SRC_S8_MONO = 4, SRC_S8_STEREO = 5 };
+// resample_launch / resample_launch_stereo for any kind: d_src holds n_in frames of `kind`; SRC_F32_MONO and SRC_F32_STEREO launch exactly
+// what those two launch.  No f32 image of the input is written.
+void resample_launch_kind(const ResamplePlan & pl, int kind, const void * d_src, long long n_in, float * d_out, const float * d_coeffs,
+                          const int * d_pos, const double * d_frac, long long first, hipStream_t st);
+
+// AudioStreamWAV frames -> mono f32 at the rate they have (k_wav.hip): out[i] = frame i of `kind` decoded (and folded).  One launch; eight
+// frames per thread with 16-byte loads from the first frame that starts on a 16-byte boundary, the frames before it and behind the last full
+// group of eight one per thread — or every frame so when no frame starts on such a boundary (a stereo source one sample off its frame grid).
+// d_src: sample-aligned; out: any f32 pointer.  false: bad kind / launch error.  n_frames = 0 launches nothing.
+bool wav_decode(int kind, const void * d_src, long long n_frames, float * out, hipStream_t st);
 
 // ---------------------------------------------------------------- GEMM (k_gemm.hip)
 enum Epi : int {

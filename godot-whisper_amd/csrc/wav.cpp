@@ -1,0 +1,322 @@
+// AudioStreamWAV ingest (include/wmi_device.h wmi_wav_* / wmi_full_*_wav): the asset's bytes go to the device as bytes and become the
+// mono 16 kHz f32 samples of the transcription in ONE launch per clip.
+//
+// replaces: AudioStreamToText.get_text (bin/addons/godot_whisper/audio_stream_to_text.gd:31-48) — a GDScript loop over every sample and a
+// 4-byte float per 2-byte sample over PCIe, with the three misreadings INTEGRATION.md lists (stereo, other rates, every second 8-bit byte).
+//
+// A clip is planned on the host (format, frame count, the resampler's plan: nothing touches the device, every argument error is decided
+// here), then queued: the upload of its bytes into the context's grow-only byte buffer, the position table of a rate without a closed
+// form, and one launch — k_wav_decode at 16 kHz, else the resampler reading the packed frames (k_resample.hip in_frame<KIND>).  For
+// wmi_full_wav the launch writes into the staging area behind pcm_to_mel's padded image, on the log-mel's stream (DeviceState::pcm_job);
+// the long and the batch form convert into a buffer of the context and hand wmi_full_long / wmi_full_batch device pointers.
+
+#include <algorithm>
+#include <climits>
+#include <cstring>
+#include <mutex>
+#include <vector>
+#include "wmi.h"
+#include "kernels.h"
+
+namespace wmi {
+
+struct WavPlan {
+    int err = 0;                          // a conversion error of wmi_device.h, or 0
+    int kind = 0, sample_bytes = 0;       // k::SrcKind
+    long long frames = 0, n_out = 0;
+    bool resample = false; k::ResamplePlan pl;
+};
+
+struct WavJob {
+    const wmi_wav * wav = nullptr; int converter = 0;
+    WavPlan plan;
+    size_t bytes_off = 0, tab_off = 0;    // the clip's place in the byte buffer / the position tables (batch: one after the other)
+    bool mark_begin = true, mark_end = true;   // record the events of wmi_wav_stats' timer around this job
+    bool used = false;
+};
+
+struct WavWork {
+    unsigned char * d_bytes = nullptr; size_t bytes_cap = 0;       // the clips' bytes as uploaded (grow-only)
+    int * d_pos = nullptr; double * d_frac = nullptr; size_t tab_cap = 0;
+    float * d_out = nullptr; size_t out_cap = 0;                   // wmi_wav_to_pcm with a host dst
+    float * d_pcm = nullptr; size_t pcm_cap = 0;                   // the samples of the long and the batch form
+    hipEvent_t ev[2] = {nullptr, nullptr}; bool ev_pending = false;
+    int64_t stats[5] = {0, 0, 0, 0, 0};
+};
+
+namespace {
+
+constexpr int RATE_16K = WHISPER_SAMPLE_RATE;
+
+struct Scope {                                                         // the context's lock, then its own state's (api.cpp CtxScope)
+    std::unique_lock<std::recursive_mutex> lk, lks;
+    explicit Scope(whisper_context * c) : lk(c->mu) { if (State * st = c->state.own) lks = std::unique_lock<std::recursive_mutex>(st->mu); }
+};
+
+// everything that can be said about a clip without a device
+WavPlan wav_plan(const wmi_wav * w, int converter, const char * who) {
+    WavPlan p;
+    if (!w || !w->data) { p.err = -1; return p; }
+    bool stereo = w->stereo == 1;
+    switch (w->format) {
+        case WMI_WAV_S8:  p.kind = stereo ? k::SRC_S8_STEREO : k::SRC_S8_MONO; p.sample_bytes = 1; break;
+        case WMI_WAV_S16: p.kind = stereo ? k::SRC_S16_STEREO : k::SRC_S16_MONO; p.sample_bytes = 2; break;
+        case WMI_WAV_F32: p.kind = stereo ? k::SRC_F32_STEREO : k::SRC_F32_MONO; p.sample_bytes = 4; break;
+        case 2: case 3:
+            WMI_ERR("%s: format %d (%s) is not decoded here: its decoder is sequential and stays on the host\n", who, w->format,
+                    w->format == 2 ? "IMA-ADPCM" : "QOA");
+            p.err = -11; return p;
+        default: p.err = -1; return p;
+    }
+    if (w->stereo < 0 || w->stereo > 1 || w->mix_rate <= 0 || w->n_bytes < 0) { p.err = -1; return p; }
+    p.frames = w->n_bytes / p.sample_bytes / (stereo ? 2 : 1);         // a trailing incomplete sample or frame is ignored
+    if (p.frames > INT_MAX) { p.err = -1; return p; }
+    if (w->on_device && ((uintptr_t) w->data % (uintptr_t) p.sample_bytes)) { p.err = -1; return p; }
+    if (w->mix_rate == RATE_16K) { p.n_out = p.frames; return p; }
+    if (converter < 0 || converter > 4) { p.err = -1; return p; }
+    p.resample = true;
+    const double ratio = (double) (uint32_t) RATE_16K / (double) (uint32_t) w->mix_rate;         // src/speech_to_text.cpp:25-26, as wmi_resample
+    const long long out_frames = (int) ((uint32_t) p.frames * ratio);
+    p.pl = k::resample_plan(p.frames, out_frames, ratio, converter);
+    if (p.pl.error == -10) { p.err = -10; return p; }
+    if (p.pl.error == -31) WMI_ERR("%s: SRC_LINEAR cannot upsample a single frame, 0 frames\n", who);
+    else if (p.pl.error) WMI_ERR("%s: converter error %d (src_simple would report it through src_strerror)\n", who, -p.pl.error);
+    p.n_out = p.pl.error ? 0 : p.pl.n_out;                             // the host gets 0 frames on a converter error (:33-36)
+    return p;
+}
+
+WavWork * work(whisper_context & ctx) {
+    if (!ctx.wav) {
+        WavWork * w = new WavWork();
+        if (!HIP_OK(hipEventCreate(&w->ev[0])) || !HIP_OK(hipEventCreate(&w->ev[1]))) {
+            for (hipEvent_t e : w->ev) if (e) (void) hipEventDestroy(e);
+            delete w;
+            return nullptr;
+        }
+        ctx.wav = w;
+    }
+    return ctx.wav;
+}
+
+// grow-only; the caller knows the buffer is idle (every call of this file waits for its launches before it returns)
+template <typename T> bool reserve(T *& p, size_t & cap, size_t want, size_t slack) {
+    if (want <= cap) return true;
+    if (p) (void) hipFree(p);
+    p = nullptr; cap = 0;
+    if (!HIP_OK(hipMalloc((void **) &p, (want + slack) * sizeof(T)))) return false;
+    cap = want + slack;
+    return true;
+}
+bool reserve_tables(WavWork & w, size_t want) {
+    if (want <= w.tab_cap) return true;
+    if (w.d_pos) (void) hipFree(w.d_pos);
+    if (w.d_frac) (void) hipFree(w.d_frac);
+    w.d_pos = nullptr; w.d_frac = nullptr; w.tab_cap = 0;
+    if (!HIP_OK(hipMalloc((void **) &w.d_pos, want * 4)) || !HIP_OK(hipMalloc((void **) &w.d_frac, want * 8))) return false;
+    w.tab_cap = want;
+    return true;
+}
+
+size_t up16(size_t n) { return (n + 15) & ~(size_t) 15; }
+
+// room for the jobs' bytes and position tables, each job's place written into it; resets the counters of wmi_wav_stats
+bool reserve_jobs(WavWork & w, WavJob * jobs, int n) {
+    size_t bytes = 0, tab = 0;
+    for (int i = 0; i < n; ++i) {
+        WavJob & j = jobs[i];
+        if (j.plan.frames <= 0 || j.plan.n_out <= 0) continue;
+        if (!j.wav->on_device) { j.bytes_off = bytes; bytes += up16((size_t) j.wav->n_bytes); }
+        if (j.plan.resample && j.plan.pl.need_table) { j.tab_off = tab; tab += (size_t) j.plan.n_out; }
+    }
+    memset(w.stats, 0, sizeof(w.stats)); w.ev_pending = false;
+    return reserve(w.d_bytes, w.bytes_cap, bytes, 4096) && reserve_tables(w, tab);
+}
+
+hipStream_t mel_stream_of(State & st) { return st.dev.mel_stream ? st.dev.mel_stream : st.dev.stream; }   // pcm_to_mel's choice
+
+}  // namespace
+
+bool wav_job_run(whisper_context & ctx, WavJob & job, float * d_dst, hipStream_t s) {
+    WavWork * w = ctx.wav;
+    if (!w) return false;
+    const WavPlan & p = job.plan;
+    job.used = true;
+    if (job.mark_begin) HIP_TRY(hipEventRecord(w->ev[0], s));
+    if (p.frames > 0 && p.n_out > 0) {
+        const void * src = job.wav->data;
+        if (!job.wav->on_device) {                                         // the bytes as they are: 1 or 2 per sample, not 4
+            unsigned char * d = w->d_bytes + job.bytes_off;
+            HIP_TRY(hipMemcpyAsync(d, job.wav->data, (size_t) job.wav->n_bytes, hipMemcpyHostToDevice, s));
+            w->stats[0] += job.wav->n_bytes;
+            src = d;
+        }
+        if (!p.resample) {
+            if (!k::wav_decode(p.kind, src, p.frames, d_dst, s)) return false;
+        } else {
+            const float * d_tab = nullptr;
+            if (job.converter <= 2) {                                      // the converter's table, shared with wmi_resample
+                float *& d_sinc = ctx.d_sinc[job.converter];
+                if (!d_sinc) {
+                    const float * coeffs; int count, inc;
+                    (void) k::sinc_table(job.converter, &coeffs, &count, &inc);
+                    const bool ok = HIP_OK(hipMalloc((void **) &d_sinc, (size_t) count * 4)) &&
+                                    HIP_OK(hipMemcpyAsync(d_sinc, coeffs, (size_t) count * 4, hipMemcpyHostToDevice, s));
+                    if (!ok) { if (d_sinc) { (void) hipFree(d_sinc); d_sinc = nullptr; } return false; }
+                }
+                d_tab = d_sinc;
+            }
+            const int * d_pos = nullptr; const double * d_frac = nullptr;
+            if (p.pl.need_table) {                                         // positions from the host's recurrence (index bookkeeping)
+                const int * hp; const double * hf;
+                k::resample_table(p.pl, &hp, &hf);
+                HIP_TRY(hipMemcpyAsync(w->d_pos + job.tab_off, hp, (size_t) p.n_out * 4, hipMemcpyHostToDevice, s));
+                HIP_TRY(hipMemcpyAsync(w->d_frac + job.tab_off, hf, (size_t) p.n_out * 8, hipMemcpyHostToDevice, s));
+                w->stats[0] += p.n_out * 12;
+                d_pos = w->d_pos + job.tab_off; d_frac = w->d_frac + job.tab_off;
+            }
+            k::resample_launch_kind(p.pl, p.kind, src, p.frames, d_dst, d_tab, d_pos, d_frac, 0, s);
+            HIP_TRY(hipGetLastError());
+        }
+        w->stats[3] += 1;
+    }
+    w->stats[1] += p.frames; w->stats[2] += p.n_out;
+    if (job.mark_end) { HIP_TRY(hipEventRecord(w->ev[1], s)); w->ev_pending = true; }
+    return true;
+}
+
+void free_wav(whisper_context & ctx) {
+    WavWork * w = ctx.wav;
+    if (!w) return;
+    for (void * p : { (void *) w->d_bytes, (void *) w->d_pos, (void *) w->d_frac, (void *) w->d_out, (void *) w->d_pcm }) if (p) (void) hipFree(p);
+    for (hipEvent_t e : w->ev) if (e) (void) hipEventDestroy(e);
+    delete w;
+    ctx.wav = nullptr;
+}
+
+}  // namespace wmi
+
+using namespace wmi;
+
+extern "C" {
+
+int wmi_selftest_wav_plan(const struct wmi_wav * wav, int converter, long long * frames, long long * n_out) {
+    try {
+        const WavPlan p = wav_plan(wav, converter, __func__);
+        if (p.err) return p.err;
+        if (frames) *frames = p.frames;
+        if (n_out) *n_out = p.n_out;
+        return 0;
+    } catch (...) { return -3; }
+}
+
+int wmi_wav_to_pcm(struct whisper_context * ctx, const struct wmi_wav * wav, int converter, float * dst, int dst_capacity, int dst_on_device) {
+    if (!ctx || !ctx->state) return -1;
+    try {
+        WavJob job; job.wav = wav; job.converter = converter;
+        job.plan = wav_plan(wav, converter, __func__);
+        if (job.plan.err) return job.plan.err;
+        if (!dst || dst_capacity < 0) return -1;
+        if (job.plan.n_out > dst_capacity) return -4;
+        Scope lk(ctx);
+        if (!compute_ready(*ctx, __func__)) return -2;
+        if (!HIP_OK(hipSetDevice(ctx->device))) return -2;
+        WavWork * w = work(*ctx);
+        if (!w) return -3;
+        hipStream_t s = mel_stream_of(*ctx->state);
+        const size_t n = (size_t) job.plan.n_out;
+        if (!reserve_jobs(*w, &job, 1) || (!dst_on_device && !reserve(w->d_out, w->out_cap, n, 1024))) return -3;
+        float * d_dst = dst_on_device ? dst : w->d_out;
+        bool ok = wav_job_run(*ctx, job, d_dst, s);
+        if (ok && !dst_on_device && n > 0) ok = HIP_OK(hipMemcpyAsync(dst, d_dst, n * 4, hipMemcpyDeviceToHost, s));
+        ok = HIP_OK(hipStreamSynchronize(s)) && ok;                        // (the caller's bytes and the plan's tables are free again)
+        return ok ? (int) n : -3;
+    } catch (...) { WMI_ERR("%s: out of memory\n", __func__); return -3; }
+}
+
+int wmi_full_wav(struct whisper_context * ctx, struct whisper_full_params params, const struct wmi_wav * wav, int converter) {
+    if (!ctx || !ctx->state) return -101;
+    try {
+        WavJob job; job.wav = wav; job.converter = converter;
+        job.plan = wav_plan(wav, converter, __func__);
+        if (job.plan.err) return -100 + job.plan.err;
+        Scope lk(ctx);                                                     // wmi_full_device_pcm's locks
+        if (!compute_ready(*ctx, __func__)) return -102;
+        if (!HIP_OK(hipSetDevice(ctx->device))) return -102;
+        WavWork * w = work(*ctx);
+        if (!w || !reserve_jobs(*w, &job, 1)) return -103;
+        DeviceState & d = ctx->state->dev;
+        struct Hook { DeviceState & d; ~Hook() { d.pcm_job = nullptr; } } hook{d};
+        d.pcm_job = &job;                                                  // the one pcm_to_mel of full() runs the job instead of copying host samples
+        const int r = full(*ctx, params, nullptr, nullptr, (int) job.plan.n_out);
+        if (job.used) (void) hipStreamSynchronize(mel_stream_of(*ctx->state));   // full() has waited for its results; an early error return may not have
+        return r;
+    } catch (...) { WMI_ERR("%s: out of memory\n", __func__); return -103; }
+}
+
+int wmi_full_long_wav(struct whisper_context * ctx, struct whisper_full_params params, const struct wmi_wav * wav, int converter,
+                      const struct wmi_long_params * long_params) {
+    if (!ctx || !ctx->state) return -101;
+    try {
+        WavJob job; job.wav = wav; job.converter = converter;
+        job.plan = wav_plan(wav, converter, __func__);
+        if (job.plan.err) return -100 + job.plan.err;
+        Scope lk(ctx);                                                     // wmi_full_long's locks
+        if (!compute_ready(*ctx, __func__)) return -102;
+        if (!HIP_OK(hipSetDevice(ctx->device))) return -102;
+        WavWork * w = work(*ctx);
+        const size_t n = (size_t) job.plan.n_out;
+        if (!w || !reserve_jobs(*w, &job, 1) || !reserve(w->d_pcm, w->pcm_cap, std::max<size_t>(n, 1), 4096)) return -103;
+        hipStream_t s = mel_stream_of(*ctx->state);
+        bool ok = wav_job_run(*ctx, job, w->d_pcm, s);
+        ok = HIP_OK(hipStreamSynchronize(s)) && ok;                        // wmi_full_long takes device samples as ready, on whichever stream it reads them
+        if (!ok) return -103;
+        return wmi_full_long(ctx, params, w->d_pcm, (int) n, 1, long_params);
+    } catch (...) { WMI_ERR("%s: out of memory\n", __func__); return -103; }
+}
+
+int wmi_full_batch_wav(struct whisper_context * ctx, struct whisper_full_params params, const struct wmi_wav * wavs, int n, int converter) {
+    if (!ctx || !ctx->state || !wavs || n < 0) return -101;
+    try {
+        std::vector<WavJob> jobs((size_t) n);
+        std::vector<size_t> off((size_t) n);
+        size_t total = 0;
+        for (int i = 0; i < n; ++i) {
+            jobs[i].wav = wavs + i; jobs[i].converter = converter;
+            jobs[i].plan = wav_plan(wavs + i, converter, __func__);
+            if (jobs[i].plan.err) return -100 + jobs[i].plan.err;
+            jobs[i].mark_begin = i == 0; jobs[i].mark_end = i == n - 1;
+            off[i] = total; total += ((size_t) jobs[i].plan.n_out + 63) & ~(size_t) 63;
+        }
+        Scope lk(ctx);                                                     // wmi_full_batch's locks
+        if (!compute_ready(*ctx, __func__)) return -102;
+        if (!HIP_OK(hipSetDevice(ctx->device))) return -102;
+        WavWork * w = work(*ctx);
+        if (!w || !reserve_jobs(*w, jobs.data(), n) || !reserve(w->d_pcm, w->pcm_cap, std::max<size_t>(total, 1), 4096)) return -103;
+        hipStream_t s = mel_stream_of(*ctx->state);
+        bool ok = true;
+        for (int i = 0; i < n && ok; ++i) ok = wav_job_run(*ctx, jobs[i], w->d_pcm + off[i], s);      // every conversion is queued ...
+        ok = HIP_OK(hipStreamSynchronize(s)) && ok;                                                  // ... before the one wait
+        if (!ok) return -103;
+        std::vector<const float *> pcm((size_t) n); std::vector<int> ns((size_t) n);
+        for (int i = 0; i < n; ++i) { pcm[i] = w->d_pcm + off[i]; ns[i] = (int) jobs[i].plan.n_out; }
+        return wmi_full_batch(ctx, params, pcm.data(), ns.data(), n, 1);
+    } catch (...) { WMI_ERR("%s: out of memory\n", __func__); return -103; }
+}
+
+int wmi_wav_stats(struct whisper_context * ctx, int64_t * out5) {
+    if (!ctx || !out5) return -1;
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    memset(out5, 0, 5 * sizeof(int64_t));
+    WavWork * w = ctx->wav;
+    if (!w) return 0;
+    if (w->ev_pending) {
+        w->ev_pending = false;
+        float ms = 0.0f;
+        if (HIP_OK(hipSetDevice(ctx->device)) && hipEventSynchronize(w->ev[1]) == hipSuccess && hipEventElapsedTime(&ms, w->ev[0], w->ev[1]) == hipSuccess)
+            w->stats[4] = (int64_t) (ms * 1e3);
+    }
+    memcpy(out5, w->stats, sizeof(w->stats));
+    return 0;
+}
+
+}  // extern "C"

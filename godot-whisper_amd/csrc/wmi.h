@@ -195,6 +195,9 @@ struct DeviceState {
     float * mel = nullptr;      size_t mel_cap = 0;          // [n_mel][n_len] f32 (reference layout)
     float * mel_max = nullptr;                                // 1 float (ordered-int encoded)
     const float * last_pcm = nullptr; int last_pcm_n = 0;     // device copy of the samples of the last pcm_to_mel
+    // wmi_full_wav (wav.cpp): the next pcm_to_mel of HOST samples takes no samples from the host — this job writes them into the staging
+    // area behind the padded image, on the log-mel's stream (null: nothing changes).  Taken once: pcm_to_mel clears it.
+    struct WavJob * pcm_job = nullptr;
     float * energy = nullptr;   size_t energy_cap = 0;        // |x| envelope (device)
     float * energy_host = nullptr;                            // pinned mirror
     size_t  energy_dev_cap = 0;                               // floats allocated at `energy` (envelope + block extrema; the copy-engine form)
@@ -405,6 +408,12 @@ struct StateInstall {                            // RAII: `st` is what `slot` re
 // ctx.state as their caller does; the chain lives on the caller's stack, which outlives the job)
 StateInstall * state_installs_top();
 void state_installs_set(StateInstall * top);
+// AudioStreamWAV ingest (wav.cpp): the context's work set, and one planned conversion (DeviceState::pcm_job)
+struct WavWork;
+struct WavJob;
+// queue the job's upload, position table and its one conversion launch on `s`; the mono 16 kHz samples land at d_dst (room for the job's count)
+bool wav_job_run(whisper_context & ctx, WavJob & job, float * d_dst, hipStream_t s);
+void free_wav(whisper_context & ctx);
 }
 
 struct whisper_context {
@@ -429,6 +438,7 @@ struct whisper_context {
     float * d_sinc[3] = {nullptr, nullptr, nullptr};   // resampler coefficient tables on the device, by converter (wmi_resample)
     float * vad_res = nullptr;          // pinned host memory the VAD kernel writes {decision, energy_all, energy_last} into (wmi_vad)
     float * dsp_scratch = nullptr; size_t dsp_scratch_bytes = 0;   // grow-only device staging of the host-pointer forms of wmi_vad / wmi_downmix_stereo / wmi_resample
+    wmi::WavWork * wav = nullptr;       // wmi_wav_* / wmi_full_*_wav (wav.cpp): made by the first such call, null in a context that never makes one
     // guards what belongs to the CONTEXT: the lock-step work set (wmi_full_batch), the DSP scratch, state creation, the probes.  Compute
     // on a state takes the state's own lock (wmi::State::mu), not this one.
     std::recursive_mutex mu;

@@ -294,6 +294,60 @@ class SpeechToText:
         self.last_segments = self.segments()
         return out
 
+    # -- an AudioStreamWAV as it is (product library only: include/wmi_device.h wmi_full_wav & co.): `data` are the asset's bytes, 8 or
+    #    16 bit (AudioStreamWAV.FORMAT_8_BITS = 0 / FORMAT_16_BITS = 1; abi.WMI_WAV_F32 for f32), mono or stereo, at its own mix rate.
+    #    The reference node decodes them in a GDScript loop as if they were 16 kHz mono (audio_stream_to_text.gd:40-46).
+    @staticmethod
+    def _wav(data, format: int, stereo, mix_rate: int):
+        """-> (abi.wmi_wav, keepalive) for host bytes; an empty clip still gets a non-NULL pointer."""
+        raw = bytes(data)
+        buf = C.create_string_buffer(raw, max(len(raw), 1))
+        return abi.wmi_wav(C.cast(buf, C.c_void_p), len(raw), int(format), int(stereo), int(mix_rate), 0), buf
+
+    def transcribe_wav(self, data: bytes, format: int, stereo, mix_rate: int, initial_prompt: str = "", audio_ctx: int = 0,
+                       interpolator_type: int = 2, params=None) -> list:
+        if not self.ctx:
+            return []
+        wav, _keep = self._wav(data, format, stereo, mix_rate)
+        p = params if params is not None else self.full_params(initial_prompt, audio_ctx)
+        self.last_ret = self.lib.wmi_full_wav(self.ctx, p, C.byref(wav), int(interpolator_type))
+        if self.last_ret != 0:
+            return []
+        return self.collect()
+
+    def transcribe_wav_long(self, data: bytes, format: int, stereo, mix_rate: int, interpolator_type: int = 2, params=None,
+                            long_params=None) -> list:
+        """transcribe_long on the asset's bytes; leaves what transcribe_long leaves."""
+        self.last_pieces, self.last_modes, self.last_segments = [], [], []
+        if not self.ctx:
+            return []
+        wav, _keep = self._wav(data, format, stereo, mix_rate)
+        p = params if params is not None else self.full_params()
+        lp = C.byref(long_params) if long_params is not None else None
+        self.last_ret = self.lib.wmi_full_long_wav(self.ctx, p, C.byref(wav), int(interpolator_type), lp)
+        if self.last_ret != 0:
+            return []
+        for i in range(self.lib.wmi_long_n_pieces(self.ctx)):
+            pc = abi.wmi_long_piece()
+            assert self.lib.wmi_long_get_piece(self.ctx, i, C.byref(pc)) == 0
+            self.last_pieces.append({name: getattr(pc, name) for name, _ in abi.wmi_long_piece._fields_})
+            self.last_modes.append(pc.mode)
+        out = self.collect()
+        self.last_segments = self.segments()
+        return out
+
+    def transcribe_wav_batch(self, clips: list, initial_prompt: str = "", audio_ctx: int = 0, interpolator_type: int = 2, params=None) -> list:
+        """clips: (data, format, stereo, mix_rate) each — a folder of voice lines in one lock-step call (wmi_full_batch_wav)."""
+        if not self.ctx:
+            return []
+        made = [self._wav(*c) for c in clips]
+        wavs = (abi.wmi_wav * max(len(made), 1))(*[w for w, _ in made])
+        p = params if params is not None else self.full_params(initial_prompt, audio_ctx)
+        self.last_ret = self.lib.wmi_full_batch_wav(self.ctx, p, wavs, len(made), int(interpolator_type))
+        if self.last_ret != 0:
+            return []
+        return self.collect_batch(len(made))
+
     def segments(self) -> list:
         """(t0, t1, text) of the segments the accessors show now (10 ms units)."""
         lib, ctx = self.lib, self.ctx
@@ -451,6 +505,18 @@ class AudioStreamToText(SpeechToText):
             return ""
         text = tokens.pop(0).decode("utf-8", errors="replace")
         return remove_special_characters(text)
+
+    def get_text_wav(self, data: bytes, format: int, stereo, mix_rate: int, initial_prompt: str = "", interpolator_type: int = 2,
+                     long_form: bool = False) -> str:
+        """get_text on audio_stream.data / .format / .stereo / .mix_rate themselves: every sample is decoded, a stereo asset is folded
+        and another rate resampled on the device — what the node's own loop (audio_stream_to_text.gd:40-46) gets wrong."""
+        if long_form:
+            tokens = self.transcribe_wav_long(data, format, stereo, mix_rate, interpolator_type, self.full_params(initial_prompt, 0))
+        else:
+            tokens = self.transcribe_wav(data, format, stereo, mix_rate, initial_prompt, 0, interpolator_type)
+        if not tokens:
+            return ""
+        return remove_special_characters(tokens.pop(0).decode("utf-8", errors="replace"))
 
 
 def remove_special_characters(message: str) -> str:

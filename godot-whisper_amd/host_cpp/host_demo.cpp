@@ -118,6 +118,15 @@ int main(int argc, char ** argv) {
         printf("]\n");
         return 0;
     }
+    if (mode == "--wav-bytes") {                              // the file is audio_stream.data; language = format, prompt = "<stereo>,<mix_rate>,<interpolator>"
+        int stereo = 0, mix_rate = 16000, interp = SpeechToText::SRC_SINC_FASTEST;
+        sscanf(prompt.c_str(), "%d,%d,%d", &stereo, &mix_rate, &interp);
+        node.set_language(SpeechToText::English);
+        printf("{\"transcription\": ");
+        json_transcription(node.transcribe_wav(raw, language, stereo != 0, mix_rate, "", audio_ctx, (SpeechToText::InterpolatorType) interp));
+        printf(", \"ret\": %d}\n", node.last_return);
+        return 0;
+    }
     std::vector<float> pcm((const float *) raw.data(), (const float *) raw.data() + raw.size() / 4);
     if (mode == "long") {
         wmi_long_params lp = wmi_long_default_params();

@@ -186,6 +186,24 @@ Transcription SpeechToText::transcribe(const std::vector<float> & buffer, const 
     return collect();
 }
 
+Transcription SpeechToText::transcribe_wav(const std::vector<uint8_t> & data, int format, bool stereo, int mix_rate,
+                                           const std::string & initial_prompt, int audio_ctx, InterpolatorType interpolator_type) {
+    const whisper_full_params whisper_params = make_params(initial_prompt, audio_ctx);
+    if (!context_instance) {
+        fprintf(stderr, "ERROR: Context instance is null\n");
+        return Transcription();
+    }
+    static const uint8_t none = 0;                                   // an empty PackedByteArray still hands over a pointer
+    const wmi_wav wav = { data.empty() ? &none : data.data(), (long long) data.size(), format, stereo ? 1 : 0, mix_rate, 0 };
+    const int ret = wmi_full_wav(context_instance, whisper_params, &wav, (int) interpolator_type);
+    last_return = ret;
+    if (ret != 0) {
+        fprintf(stderr, "ERROR: Failed to process audio, returned %d\n", ret);
+        return Transcription();
+    }
+    return collect();
+}
+
 std::vector<Transcription> SpeechToText::transcribe_batch(const std::vector<std::vector<float>> & buffers,
                                                           const std::string & initial_prompt, int audio_ctx) {
     std::vector<Transcription> out;

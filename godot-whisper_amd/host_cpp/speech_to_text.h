@@ -82,6 +82,11 @@ public:
 
     bool voice_activity_detection(const std::vector<float> & buffer) const;
     Transcription transcribe(const std::vector<float> & buffer, const std::string & initial_prompt, int audio_ctx);
+    // not in the reference: an AudioStreamWAV as it is (include/wmi_device.h: wmi_full_wav) — `data` = audio_stream.data, format =
+    // audio_stream.format (0 = FORMAT_8_BITS, 1 = FORMAT_16_BITS), stereo, mix_rate.  Every sample is decoded, a stereo asset folded
+    // and another rate resampled to 16 kHz on the device; the node's own GDScript loop (addon/audio_stream_to_text.gd:40-46) does none of it.
+    Transcription transcribe_wav(const std::vector<uint8_t> & data, int format, bool stereo, int mix_rate, const std::string & initial_prompt = "",
+                                 int audio_ctx = 0, InterpolatorType interpolator_type = SRC_SINC_FASTEST);
     // not in the reference: several buffers in lock-step on one GPU (include/wmi_device.h: wmi_full_batch); element c is
     // what transcribe(buffers[c], initial_prompt, audio_ctx) returns on a fresh context
     std::vector<Transcription> transcribe_batch(const std::vector<std::vector<float>> & buffers, const std::string & initial_prompt,

@@ -156,6 +156,12 @@ DEVICE_API = [
     ("wmi_selftest_long_window", C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("wmi_selftest_long_plan", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(abi.wmi_long_params), C.c_int,
                                          C.POINTER(abi.wmi_long_piece), C.c_int]),
+    ("wmi_wav_to_pcm", C.c_int, [C.c_void_p, C.POINTER(abi.wmi_wav), C.c_int, C.c_void_p, C.c_int, C.c_int]),
+    ("wmi_full_wav", C.c_int, [C.c_void_p, abi.whisper_full_params, C.POINTER(abi.wmi_wav), C.c_int]),
+    ("wmi_full_long_wav", C.c_int, [C.c_void_p, abi.whisper_full_params, C.POINTER(abi.wmi_wav), C.c_int, C.POINTER(abi.wmi_long_params)]),
+    ("wmi_full_batch_wav", C.c_int, [C.c_void_p, abi.whisper_full_params, C.POINTER(abi.wmi_wav), C.c_int, C.c_int]),
+    ("wmi_selftest_wav_plan", C.c_int, [C.POINTER(abi.wmi_wav), C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
+    ("wmi_wav_stats", C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
 ]
 
 _lib = None

@@ -814,6 +814,63 @@ WHISPER_API int  wmi_selftest_score_plan(struct whisper_context * ctx, struct wm
                                          const int32_t * n_tokens, int n_texts, int32_t * prefix, int cap_prefix, int * n_prefix, int32_t * first,
                                          int32_t * prefix_target, int32_t * rows, int cap_rows, int * n_rows, int32_t * pass_text0, int cap_passes);
 
+/* Transcribe what an AudioStreamWAV holds: its `data` bytes as they are — 8 or 16 bit, mono or stereo, at the asset's own mix rate.
+ *   replaces: the per-sample loop of AudioStreamToText.get_text (bin/addons/godot_whisper/audio_stream_to_text.gd:31-48), which turns
+ *             the bytes into floats one `append` at a time and transcribes them as 16 kHz mono whatever the asset is (INTEGRATION.md,
+ *             host quirks: a stereo asset is read as interleaved mono, another rate at the wrong speed, an 8-bit asset every second byte).
+ * The definition, held bit for bit (tests/wav_ref.py):
+ *   sample   WMI_WAV_S16: float(v) / 32768, little-endian; WMI_WAV_S8: float(v) / 128, v signed; WMI_WAV_F32: as is — exact in f32
+ *   frame    mono: the sample; stereo: (float(l + r) as f32, then / 2 through double), wmi_downmix_stereo's fold
+ *   tails    a trailing incomplete sample (an odd byte at 16 bit) or frame (an odd sample in stereo) is ignored
+ *   rate     mix_rate == 16000: the frames are the result.  Else wmi_resample(frames, mix_rate -> 16000, converter) on them, bit for bit:
+ *            the result count is its plan's, within int(uint32(frames) * 16000.0 / mix_rate).  converter 1 - 4 as there (0: -10); it is
+ *            not looked at when mix_rate == 16000
+ * On the device this is ONE launch per clip: at 16 kHz k_wav_decode writes the f32 samples where the log-mel reads them; at any other rate
+ * the resampler reads the packed frames itself (csrc/k_resample.hip in_frame) — no f32 image of the input is written, no separate decode
+ * runs.  Host bytes are uploaded once, as bytes (2 or 1 per sample instead of 4), into a grow-only buffer of the context; upload, conversion
+ * and log-mel are queued on one stream without a host wait between them.  `on_device` != 0: data is a device pointer on the context's
+ * device, aligned to its sample size (any sample offset into an allocation will do).
+ *   wmi_wav_to_pcm      the mono 16 kHz f32 samples into dst (a host pointer, or a device pointer with dst_on_device != 0); returns the
+ *                       samples written.  Waits for them.
+ *   wmi_full_wav        wmi_full_device_pcm on those samples (token timestamps take their envelope from the staged samples); waits where
+ *                       whisper_full waits.  Results through the whisper_full_* accessors.
+ *   wmi_full_long_wav   the whole recording into a device buffer of the context, then wmi_full_long on it (pcm_on_device)
+ *   wmi_full_batch_wav  n clips, each with a format, channel count and rate of its own: every conversion is queued before the one wait,
+ *                       then wmi_full_batch on the device samples.  Results through wmi_batch_select & co.
+ *   wmi_selftest_wav_plan   host only, no context: the frame count and the result count of a clip.  Returns 0 or a conversion error.
+ *   wmi_wav_stats       of the last of these calls on the context: out5 = { bytes copied host -> device (the clip's bytes, and the position
+ *                       table at rates without a closed form, e.g. 22.05 kHz), frames read, samples written, kernel launches of the
+ *                       conversion (one per non-empty clip), microseconds on the device from the first upload to the last conversion
+ *                       launch (by stream events; this call waits for them) }.  All zero on a context that never made such a call.
+ * Conversion errors, every one decided before the device is touched: -1 a NULL pointer, an unknown format, stereo outside 0 / 1, a
+ * non-positive rate, negative bytes, more frames than an int holds, a device pointer that is not sample-aligned, a converter outside
+ * 0 - 4; -11 formats 2 and 3 (IMA-ADPCM, QOA: sequential decoders that stay on the host; logged); -10 converter 0; -2 the context cannot
+ * compute; -3 a device error; -4 dst_capacity below the result count.  A converter error of the plan (ratio outside [1/256, 256],
+ * SRC_LINEAR upsampling one frame) gives 0 samples, as wmi_resample.  The wmi_full_*_wav calls return a conversion error e as -100 + e,
+ * and otherwise exactly what whisper_full / wmi_full_long / wmi_full_batch return for the converted samples (an empty clip included).
+ * The no-speech, token-DTW and grammar-device modes apply as in those calls; each call takes the locks the call it ends in takes;
+ * wmi_get_timings gains nothing (the conversion's time is in wmi_wav_stats, and, being queued in front of the log-mel, inside the wall
+ * time of the transcription).  Off unless called: a context that never makes one of these calls allocates and launches nothing for them.
+ * Not served: IMA-ADPCM and QOA, RIFF headers (Godot hands over the data chunk), more than two channels, SRC_SINC_BEST_QUALITY. */
+enum { WMI_WAV_S8 = 0, WMI_WAV_S16 = 1, WMI_WAV_F32 = 32 };   /* 0 / 1 = AudioStreamWAV.FORMAT_8_BITS / FORMAT_16_BITS */
+struct wmi_wav {
+    const void * data;
+    long long    n_bytes;
+    int          format;
+    int          stereo;
+    int          mix_rate;
+    int          on_device;
+};
+WHISPER_API int wmi_wav_to_pcm(struct whisper_context * ctx, const struct wmi_wav * wav, int converter, float * dst, int dst_capacity,
+                               int dst_on_device);
+WHISPER_API int wmi_full_wav(struct whisper_context * ctx, struct whisper_full_params params, const struct wmi_wav * wav, int converter);
+WHISPER_API int wmi_full_long_wav(struct whisper_context * ctx, struct whisper_full_params params, const struct wmi_wav * wav, int converter,
+                                  const struct wmi_long_params * long_params);
+WHISPER_API int wmi_full_batch_wav(struct whisper_context * ctx, struct whisper_full_params params, const struct wmi_wav * wavs, int n,
+                                   int converter);
+WHISPER_API int wmi_selftest_wav_plan(const struct wmi_wav * wav, int converter, long long * frames, long long * n_out);
+WHISPER_API int wmi_wav_stats(struct whisper_context * ctx, int64_t * out5);
+
 /* Host worker pool self-test (no device needed): `reps` jobs of `n_tasks` tasks; returns reps * n_tasks * (n_tasks + 1) / 2
  * when every task of every job ran exactly once. */
 WHISPER_API int64_t wmi_selftest_pool(int n_tasks, int reps);
