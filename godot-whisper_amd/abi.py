@@ -224,6 +224,12 @@ class wmi_text_score(C.Structure):  # include/wmi_device.h: one text's result of
                 ("first", C.c_int32)]
 
 
+class wmi_draft_status(C.Structure):  # include/wmi_device.h: what became of the last transcription call's draft (wmi_set_draft)
+    _fields_ = [("n_offered", C.c_int32), ("n_rows", C.c_int32), ("n_accepted", C.c_int32), ("n_emitted_from_draft", C.c_int32),
+                ("reason", C.c_int32)]
+
+
+DRAFT_USED, DRAFT_NONE, DRAFT_NOT_ELIGIBLE, DRAFT_CLIPPED = range(4)             # wmi_draft_status.reason
 NO_SPEECH_OFF, NO_SPEECH_REPORT, NO_SPEECH_DROP, NO_SPEECH_GATE = range(4)       # wmi_set_no_speech modes
 WINDOW_EMITTED, WINDOW_DROPPED, WINDOW_GATED = range(3)                          # wmi_window.outcome
 TOKEN_DTW_OFF, TOKEN_DTW_ON = range(2)                                           # wmi_set_token_dtw modes

@@ -765,8 +765,10 @@ void wmi_get_timings(struct whisper_context * ctx, int64_t * t6, int32_t * n5) {
 
 int wmi_full_batch(struct whisper_context * ctx, struct whisper_full_params params, const float * const * pcm, const int * n_samples,
                    int n_chunks, int pcm_on_device) {
-    if (!ctx || !ctx->state || !pcm || !n_samples || n_chunks < 0) return -1;
+    if (!ctx || !ctx->state) return -1;
     CtxScope lk(ctx);
+    DraftRefuse no_draft(ctx->state.get());   // (dropped whatever the call returns, an argument error included)
+    if (!pcm || !n_samples || n_chunks < 0) return -1;
     (void) hipSetDevice(ctx->device);
     params.no_context = true;                 // chunks are independent transcriptions
     return full_batch(*ctx, params, pcm, n_samples, n_chunks, pcm_on_device != 0);
@@ -775,8 +777,10 @@ int wmi_full_batch(struct whisper_context * ctx, struct whisper_full_params para
 int wmi_full_batch_ctx(struct whisper_context * ctx, struct whisper_full_params params, const float * const * pcm, const int * n_samples,
                        const int * audio_ctx, int n_chunks, int pcm_on_device) {
     if (!audio_ctx) return wmi_full_batch(ctx, params, pcm, n_samples, n_chunks, pcm_on_device);
-    if (!ctx || !ctx->state || !pcm || !n_samples || n_chunks < 0) return -1;
+    if (!ctx || !ctx->state) return -1;
     CtxScope lk(ctx);
+    DraftRefuse no_draft(ctx->state.get());
+    if (!pcm || !n_samples || n_chunks < 0) return -1;
     // the lengths are checked before anything touches the device (and before the question whether there is one)
     if (const int bad = check_audio_ctxs(*ctx, audio_ctx, n_chunks, __func__)) return bad;
     (void) hipSetDevice(ctx->device);

@@ -170,9 +170,10 @@ int whisper_full_with_state(struct whisper_context * ctx, struct whisper_state *
 // replay, the timing bookkeeping AND the threads are the reference's: pieces 1.. run on host threads of their own, each on
 // its own state (own stream), piece 0 on the caller's thread.
 int whisper_full_parallel(struct whisper_context * ctx, struct whisper_full_params params, const float * samples, int n_samples, int n_processors) {
-    if (n_processors == 1) return whisper_full(ctx, params, samples, n_samples);
     if (!ctx || !ctx->state || n_processors < 1) return -1;
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    DraftRefuse no_draft(ctx->state.get());     // (pieces on states of their own: a draft of the whole does not fit one of them)
+    if (n_processors == 1) return whisper_full(ctx, params, samples, n_samples);
     const int offset_samples = (WHISPER_SAMPLE_RATE * params.offset_ms) / 1000;
     const int per = (n_samples - offset_samples) / n_processors;
     // nothing to split (the reference would hand negative sample counts to its workers here): one plain call
@@ -450,6 +451,101 @@ int wmi_selftest_score_rows(int device, int rows, int n_vocab, const float * log
     }
     if (!HIP_OK(hipMemcpyAsync(lp_out, d_lp, (size_t) rows * 4, hipMemcpyDeviceToHost, b.st)) || !HIP_OK(hipStreamSynchronize(b.st)) ||
         !HIP_OK(hipGetLastError())) return -3;
+    return 0;
+}
+// a draft transcript verified in one decoder pass (wmi_device.h; full.cpp, device.cpp: draft_*)
+int wmi_set_draft_with_state(struct whisper_context * ctx, struct whisper_state * state, const whisper_token * tokens, int n) {
+    if (!ctx || n < 0 || (n > 0 && !tokens)) return -1;
+    if (!state) state = reinterpret_cast<struct whisper_state *>(ctx->state.get());      // (NULL: the context's own state)
+    if (!state) return -1;
+    const int NV = ctx->model.vocab.n_vocab;
+    for (int i = 0; i < n; ++i) if (tokens[i] < 0 || tokens[i] >= NV) return -1;
+    std::lock_guard<std::recursive_mutex> lk(S(state)->mu);
+    S(state)->draft.assign(tokens, tokens + n);
+    return 0;
+}
+int wmi_set_draft(struct whisper_context * ctx, const whisper_token * tokens, int n) { return wmi_set_draft_with_state(ctx, nullptr, tokens, n); }
+int wmi_draft_status_from_state(struct whisper_state * state, struct wmi_draft_status * out) {
+    if (!state || !out) return -1;
+    std::lock_guard<std::recursive_mutex> lk(S(state)->mu);
+    *out = S(state)->draft_status;
+    return 0;
+}
+int wmi_draft_status(struct whisper_context * ctx, struct wmi_draft_status * out) {
+    return ctx && ctx->state ? wmi_draft_status_from_state(reinterpret_cast<struct whisper_state *>(ctx->state.get()), out) : -1;
+}
+int wmi_selftest_draft_logits(struct whisper_context * ctx, float * buf, int cap_rows) {
+    if (!ctx || !ctx->state || cap_rows < 0) return -1;
+    std::lock_guard<std::recursive_mutex> lk(ctx->state->mu);
+    ctx->state->draft_logits_out = cap_rows > 0 ? buf : nullptr; ctx->state->draft_logits_cap = buf ? cap_rows : 0;
+    return 0;
+}
+int wmi_selftest_draft_plan(struct whisper_context * ctx, struct whisper_full_params params, const whisper_token * prompt, int n_prompt,
+                            const whisper_token * draft, int n_draft, int32_t * n_rows, int32_t * logit_rows, int32_t * steps) {
+    if (!ctx || !prompt || n_prompt < 1 || n_draft < 0 || (n_draft > 0 && !draft) || !n_rows || !logit_rows || !steps) return -1;
+    const Vocab & v = ctx->model.vocab; const HParams & hp = ctx->model.hp;
+    if (n_prompt > hp.n_text_ctx) return -1;
+    for (int i = 0; i < n_prompt; ++i) if (prompt[i] < 0 || prompt[i] >= v.n_vocab) return -1;
+    for (int i = 0; i < n_draft; ++i) if (draft[i] < 0 || draft[i] >= v.n_vocab) return -1;
+    static_assert(sizeof(k::DecStep) == 16 * sizeof(int32_t), "a step record is 16 words");
+    const int seek = params.offset_ms / 10, seek_end = seek + (params.duration_ms > 0 ? params.duration_ms / 10 : 100 * WHISPER_CHUNK_SIZE);
+    const DraftPlan pl = draft_plan(*ctx, params, n_prompt, draft, n_draft, seek, seek_end);
+    int space_id = -1; { auto sp = v.token_to_id.find(" "); if (sp != v.token_to_id.end()) space_id = sp->second; }
+    *n_rows = pl.n + 1;
+    for (int j = 0; j <= pl.n; ++j) {
+        const StepFilter & f = pl.filters[j];
+        k::DecStep st; memset(&st, 0, sizeof(st));
+        st.flags = (f.ban_blank ? 1 : 0) | (f.last_ts ? 2 : 0) | (f.penult_ts ? 4 : 0);
+        st.space_id = space_id; st.eot = v.eot; st.beg = v.beg; st.n_vocab = v.n_vocab;
+        st.ts_floor_end = f.ts_floor_end; st.ts_initial_start = f.ts_initial_start;
+        memcpy(steps + (size_t) j * 16, &st, sizeof(st));
+        logit_rows[j] = n_prompt - 1 + j;
+    }
+    return 0;
+}
+int wmi_selftest_draft_rows(int device, int n_rows, int n_vocab, const float * logits, const uint8_t * ban, const int32_t * steps, const int32_t * targets,
+                            int32_t * out, int32_t * accepted) {
+    static_assert(sizeof(k::SampleOut) == 8 * sizeof(int32_t), "a record is 8 words");
+    if (n_rows < 1 || n_rows > 4096 || n_vocab < 1 || n_vocab > 65536 || !logits || !ban || !steps || !out || !accepted || (n_rows > 1 && !targets)) return -1;
+    std::vector<k::DecStep> hs((size_t) n_rows);
+    memcpy(hs.data(), steps, (size_t) n_rows * sizeof(k::DecStep));
+    for (int r = 0; r < n_rows; ++r) if (hs[r].n_vocab != n_vocab) return -1;      // (k_filter_stats takes the row length from the record)
+    for (int r = 0; r + 1 < n_rows; ++r) if (targets[r] < 0 || targets[r] >= n_vocab) return -1;
+    if (!HIP_OK(hipSetDevice(device))) return -2;
+    struct Bufs {
+        std::vector<void *> dev; void * host = nullptr; hipStream_t st = nullptr;
+        ~Bufs() { if (st) (void) hipStreamDestroy(st); for (void * q : dev) (void) hipFree(q); if (host) (void) hipHostFree(host); }
+        void * get(size_t bytes) { void * q = nullptr; if (!HIP_OK(hipMalloc(&q, bytes))) return nullptr; dev.push_back(q); return q; }
+    } b;
+    // as decode() works: a logits buffer of 8 rows, filled and picked group by group on one stream; one wait behind the finish
+    const int G = 8, n_targets = n_rows - 1;
+    const int32_t tag = hs[0].seq & k::SAMPLE_SEQ_MASK;
+    float * d_l = (float *) b.get((size_t) G * n_vocab * 4);
+    uint8_t * d_ban = (uint8_t *) b.get((size_t) n_vocab);
+    k::DecStep * d_steps = (k::DecStep *) b.get((size_t) n_rows * sizeof(k::DecStep));
+    int32_t * d_tm = (int32_t *) b.get((size_t) 2 * n_rows * 4);       // targets | match
+    k::FsPartial * part = (k::FsPartial *) b.get(k::filter_scratch_bytes(G));
+    const size_t host_bytes = 16 + (size_t) n_rows * sizeof(k::SampleOut);
+    if (!d_l || !d_ban || !d_steps || !d_tm || !part || !HIP_OK(hipHostMalloc(&b.host, host_bytes, hipHostMallocDefault)) || !HIP_OK(hipStreamCreate(&b.st))) return -3;
+    memset(b.host, 0, host_bytes);
+    k::DraftOut * h_out = (k::DraftOut *) b.host; k::SampleOut * h_rec = (k::SampleOut *) ((char *) b.host + 16);
+    std::vector<int32_t> tg((size_t) n_rows, 0);
+    for (int r = 0; r < n_targets; ++r) tg[r] = targets[r];
+    if (!HIP_OK(hipMemcpyAsync(d_ban, ban, (size_t) n_vocab, hipMemcpyHostToDevice, b.st)) ||
+        !HIP_OK(hipMemcpyAsync(d_steps, hs.data(), (size_t) n_rows * sizeof(k::DecStep), hipMemcpyHostToDevice, b.st)) ||
+        !HIP_OK(hipMemcpyAsync(d_tm, tg.data(), (size_t) n_rows * 4, hipMemcpyHostToDevice, b.st)) ||
+        !HIP_OK(hipMemsetAsync(d_tm + n_rows, 0xff, (size_t) n_rows * 4, b.st)) || !HIP_OK(hipStreamSynchronize(b.st))) return -3;
+    for (int r0 = 0; r0 < n_rows; r0 += G) {
+        const int nr = std::min(G, n_rows - r0);
+        if (!HIP_OK(hipMemcpyAsync(d_l, logits + (size_t) r0 * n_vocab, (size_t) nr * n_vocab * 4, hipMemcpyHostToDevice, b.st))) return -3;
+        k::filter_stats(d_l, d_ban, d_steps + r0, part, b.st, nr);
+        k::draft_pick(part, d_steps + r0, d_tm, r0, nr, n_targets, h_rec, d_tm + n_rows, b.st);
+    }
+    k::draft_finish(d_tm + n_rows, n_rows, tag, h_out, b.st);
+    if (!HIP_OK(hipGetLastError()) || !HIP_OK(hipStreamSynchronize(b.st))) return -3;
+    if (h_out->tag != tag || h_out->accepted < 0 || h_out->accepted > n_targets) return -3;
+    memcpy(out, h_rec, (size_t) n_rows * sizeof(k::SampleOut));
+    *accepted = h_out->accepted;
     return 0;
 }
 int wmi_selftest_no_speech_rule(int mode, float p, float thold, int failed, double avg_logprob, float logprob_thold) {

@@ -34,6 +34,8 @@ struct wmi_capture {
     bool dirty = false;                                               // frames changed since the last resample
     long long n_pcm = 0; int expected = 0;
     int64_t pending_h2d = 0, stats[4] = {0, 0, 0, 0};
+    // wmi_capture_set_draft: mode 1 arms the previous successful result's token ids (draft_last) in front of every wmi_capture_full
+    int draft_mode = 0; std::vector<int32_t> draft_last;
 };
 
 namespace {
@@ -213,6 +215,7 @@ int wmi_capture_push(struct wmi_capture * c, const float * frames_xy, int n_fram
 int wmi_capture_keep_last(struct wmi_capture * c, int n_frames) {
     if (!c || n_frames < 0) return -1;
     Scope lk(c->ctx);
+    c->draft_last.clear();                                              // the sentence ended: the next text will be another
     if (n_frames < c->count) {
         c->off += c->count - n_frames; c->count = n_frames;
         c->valid = false; c->dirty = true;                              // other frames at every position: everything is recomputed
@@ -277,9 +280,24 @@ int wmi_capture_full(struct wmi_capture * c, struct whisper_full_params params) 
         Scope lk(c->ctx);
         if (!HIP_OK(hipSetDevice(c->ctx->device))) return -2;
         const int n = refresh(c);
-        if (n < 0) return n;
-        return wmi_full_device_pcm(c->ctx, params, c->d_pcm, n, nullptr);
-    } catch (...) { return -3; }
+        if (n < 0) { c->draft_last.clear(); return n; }
+        State * st = c->ctx->state.get();
+        if (c->draft_mode == 1 && st && !c->draft_last.empty()) st->draft = c->draft_last;
+        const int ret = wmi_full_device_pcm(c->ctx, params, c->d_pcm, n, nullptr);
+        c->draft_last.clear();                                          // (a failed call forgets them)
+        if (c->draft_mode == 1 && ret == 0 && st)
+            for (const Segment & seg : st->result_all) for (const whisper_token_data & t : seg.tokens) c->draft_last.push_back(t.id);
+        return ret;
+    } catch (...) { c->draft_last.clear(); return -3; }
+}
+
+int wmi_capture_set_draft(struct wmi_capture * c, int mode) {
+    if (!c) return -1;
+    Scope lk(c->ctx);
+    const int prev = c->draft_mode;
+    c->draft_mode = mode != 0 ? 1 : 0;
+    if (c->draft_mode == 0) c->draft_last.clear();
+    return prev;
 }
 
 int wmi_capture_full_batch(struct wmi_capture * const * caps, int n, struct whisper_full_params params, const int * audio_ctx) {
@@ -288,7 +306,9 @@ int wmi_capture_full_batch(struct wmi_capture * const * caps, int n, struct whis
     whisper_context * ctx = caps[0]->ctx;
     try {
         Scope lk(ctx);                                                  // once, for the refreshes and the transcription alike
+        DraftRefuse no_draft(ctx->state.get());                         // (dropped whatever the call returns)
         if (const int bad = check_audio_ctxs(*ctx, audio_ctx, n, __func__)) return bad;      // wmi_full_batch_ctx's checks, before any device work here too
+        for (int i = 0; i < n; ++i) caps[i]->draft_last.clear();       // (a lock-step call carries no draft and leaves none)
         for (int i = 0; i < n; ++i) if (caps[i]->count <= 0) return -3; // an empty session: wmi_full_batch's empty chunk
         if (!HIP_OK(hipSetDevice(ctx->device))) return -2;
         std::vector<const float *> pcm(n); std::vector<int> ns(n);

@@ -229,6 +229,9 @@ void destroy_state(State * st) {
     if (d.score_scratch) (void) hipFree(d.score_scratch);
     dfree(d.score_items); dfree(d.score_lp);
     if (d.score_host) (void) hipHostFree(d.score_host);
+    if (d.draft_part) (void) hipFree(d.draft_part);
+    if (d.draft_dev) (void) hipFree(d.draft_dev);
+    if (d.draft_host) (void) hipHostFree(d.draft_host);
     if (d.pinned) (void) hipHostFree(d.pinned);
     if (d.stream && d.stream_own_queue) own_queue_stream_put(st->device, d.stream);
     else if (d.stream) (void) hipStreamDestroy(d.stream);
@@ -571,6 +574,11 @@ bool decode(whisper_context & ctx, const Batch & batch, float * lang_logits) {
     d.score_req = nullptr;
     if (score && (lang_logits || d.nsp_row >= 0 || d.dtw_collect || !score->staging ||
                   score->staging_bytes < ((size_t) 3 * n + (size_t) n * kv.n) * 4)) { d.nsp_row = -1; d.dtw_collect = false; return false; }
+    // the draft verifier's request (draft_verify), for this call only: the flagged rows are picked in d.logits group by group, nothing goes to
+    // the host's logits image or into the reference's timers, no wait here (its caller waits once, behind draft_finish)
+    const DeviceState::DraftReq * const draft = d.draft_req;
+    d.draft_req = nullptr;
+    if (draft && (lang_logits || score || d.dtw_collect)) { d.nsp_row = -1; d.dtw_collect = false; return false; }
     // host -> pinned -> device: tokens, positions, mask (W/whisper.cpp:2186-2226), rows wanting logits
     int32_t * p_tok = (int32_t *) (score ? score->staging : d.pinned), * p_pos = p_tok + n, * p_rows = p_pos + n;
     float * p_mask = (float *) (p_rows + n);
@@ -591,7 +599,8 @@ bool decode(whisper_context & ctx, const Batch & batch, float * lang_logits) {
     int nsp_slot = -1;
     if (nsp_row >= 0) {
         if (lang_logits || !no_speech_ensure(ctx, d)) return false;
-        if (rows.size() <= 8) for (size_t i = 0; i < rows.size(); ++i) if (rows[i] == nsp_row) nsp_slot = (int) i;
+        if (rows.size() <= 8 || draft) for (size_t i = 0; i < rows.size(); ++i) if (rows[i] == nsp_row) nsp_slot = (int) i;
+        if (draft) draft->nsp_flag = nsp_slot;              // (a flagged row of a drafted batch: the head runs behind that row's group, draft_group)
         if (nsp_slot < 0 && (int) rows.size() >= n) return false;      // (every row asked for logits, more than 8 of them: no caller does)
         if (nsp_slot < 0) p_rows[rows.size()] = nsp_row;
     }
@@ -610,8 +619,9 @@ bool decode(whisper_context & ctx, const Batch & batch, float * lang_logits) {
     float * const lang_pinned = lang_logits ? (float *) ((char *) d.pinned + d.pinned_bytes - LANG_PINNED_TAIL) : nullptr;
     if (ctx.model.quantised) {
         const bool nsp_own = nsp_row >= 0 && nsp_slot < 0;
-        if (!decode_layers_q(ctx, n, n_kv, kv_head, Tc, rows, lang_pinned, nsp_own ? d.d_rows + rows.size() : nullptr, nsp_own ? d.nsp_logits : nullptr, score)) return false;
+        if (!decode_layers_q(ctx, n, n_kv, kv_head, Tc, rows, lang_pinned, nsp_own ? d.d_rows + rows.size() : nullptr, nsp_own ? d.nsp_logits : nullptr, score, draft)) return false;
         if (score) return HIP_OK(hipGetLastError());         // (no wait here: score_texts waits once, behind its last launch)
+        if (draft) return (!nsp_own || no_speech_from_logits(ctx, d.nsp_logits, 0)) && HIP_OK(hipGetLastError());      // (nor here: draft_verify does)
         if (nsp_row >= 0 && !(nsp_own ? no_speech_from_logits(ctx, d.nsp_logits, 0) : no_speech_from_logits(ctx, d.logits, nsp_slot))) return false;
         if (dtw) return HIP_OK(hipGetLastError());           // (no wait here: dtw_window waits once, behind the path)
         HIP_TRY(hipStreamSynchronize(s));
@@ -681,6 +691,18 @@ bool decode(whisper_context & ctx, const Batch & batch, float * lang_logits) {
         }
         return item == score->n_items && HIP_OK(hipGetLastError());
     }
+    if (draft) {                                             // the same groups, each picked where it lies
+        for (size_t r0 = 0; r0 < rows.size(); r0 += 8) {
+            const int nr = (int) std::min<size_t>(8, rows.size() - r0);
+            k::GemvArgs g{};
+            g.x32 = d.dx; g.ln_g = w.d_ln_g; g.ln_b = w.d_ln_b; g.eps = hp.eps; g.n = nr; g.K = S; g.N = NV; g.W = w.d_te;
+            g.epi = k::EPI_LOGITS; g.C = d.logits; g.ldc = NV; g.rows = d.d_rows + r0;
+            k::gemv(g, s);
+            if (!draft_group(ctx, *draft, (int) r0, nr)) return false;
+        }
+        if (nsp_row >= 0 && nsp_slot < 0 && !no_speech_from_row(ctx, d.dx + (size_t) nsp_row * S)) return false;
+        return HIP_OK(hipGetLastError());
+    }
     if (lang_logits) k::lang_head(d.dx, 1, S, w.d_ln_g, w.d_ln_b, hp.eps, w.d_te + (size_t) (ctx.model.vocab.sot + 1) * S, lang_pinned, s);
     else st.logits.resize((size_t) n * NV);
     for (size_t r0 = 0; r0 < rows.size() && !lang_logits; r0 += 8) {
@@ -706,6 +728,103 @@ bool decode(whisper_context & ctx, const Batch & batch, float * lang_logits) {
     if (n == 1)      { st.t_decode_us += dt; st.n_decode++; }
     else if (n < 16) { st.t_batchd_us += dt; st.n_batchd += n; }
     else             { st.t_prompt_us += dt; st.n_prompt += n; }
+    return true;
+}
+
+// ------------------------------------------------------------------------------------------------ draft verifier
+namespace {
+// grow-only, made on first use; rows = logits rows of a call
+struct DraftView { k::DecStep * d_steps; int32_t * d_targets, * d_match; k::DraftOut * h_out; k::SampleOut * h_rec; k::DecStep * h_steps; int32_t * h_targets; };
+bool draft_ensure(DeviceState & d, int rows, DraftView & v) {
+    if (d.draft_cap < rows) {
+        if (d.draft_dev) { (void) hipFree(d.draft_dev); d.draft_dev = nullptr; }
+        if (d.draft_host) { (void) hipHostFree(d.draft_host); d.draft_host = nullptr; }
+        d.draft_cap = 0;
+        HIP_TRY(hipMalloc(&d.draft_dev, (size_t) rows * (sizeof(k::DecStep) + 8)));
+        HIP_TRY(hipHostMalloc(&d.draft_host, 16 + (size_t) rows * (sizeof(k::SampleOut) + sizeof(k::DecStep) + 4), hipHostMallocDefault));
+        d.draft_cap = rows;
+    }
+    if (!d.draft_part) HIP_TRY(hipMalloc(&d.draft_part, k::filter_scratch_bytes(8)));
+    const size_t cap = (size_t) d.draft_cap;
+    v.d_steps = (k::DecStep *) d.draft_dev; v.d_targets = (int32_t *) (v.d_steps + cap); v.d_match = v.d_targets + cap;
+    char * h = (char *) d.draft_host;
+    v.h_out = (k::DraftOut *) h; v.h_rec = (k::SampleOut *) (h + 16); v.h_steps = (k::DecStep *) (v.h_rec + cap); v.h_targets = (int32_t *) (v.h_steps + cap);
+    memset(h, 0, 16 + (size_t) rows * sizeof(k::SampleOut));
+    return true;
+}
+int32_t draft_next_tag(int32_t & seq) { seq = seq >= k::SAMPLE_SEQ_MASK ? 1 : seq + 1; return seq; }      // (never 0: the records start zeroed)
+// the call's results behind its one wait: the finish record and the records of rows 0 .. accepted carry the call's tag
+bool draft_collect(const DraftView & v, int rows, int32_t tag, k::SampleOut * out, int n_out_all, int32_t * accepted) {
+    k::DraftOut fin; { const uint64_t b = *(const volatile uint64_t *) v.h_out; memcpy(&fin, &b, sizeof(fin)); }      // (one 8-byte store: read it as one)
+    if (fin.tag != tag || fin.accepted < 0 || fin.accepted >= rows + (n_out_all ? 1 : 0)) { WMI_ERR("%s: the verifier's record did not arrive\n", __func__); return false; }
+    const int n_out = n_out_all ? rows : fin.accepted + 1;
+    for (int r = 0; r < n_out && r < rows; ++r) {
+        out[r] = v.h_rec[r];
+        if (out[r].seq0 != tag || out[r].seq != tag) { WMI_ERR("%s: the record of row %d did not arrive\n", __func__, r); return false; }
+    }
+    *accepted = fin.accepted;
+    return true;
+}
+} // namespace
+
+bool draft_group(whisper_context & ctx, const DeviceState::DraftReq & rq, int r0, int nr) {
+    DeviceState & d = ctx.state->dev;
+    const int NV = ctx.model.hp.n_vocab;
+    k::filter_stats(d.logits, d.ban_dev, rq.d_steps + r0, rq.part, d.stream, nr);
+    k::draft_pick(rq.part, rq.d_steps + r0, rq.d_targets, r0, nr, rq.n_targets, rq.out_host, rq.d_match, d.stream);
+    if (rq.nsp_flag >= r0 && rq.nsp_flag < r0 + nr && !no_speech_from_logits(ctx, d.logits, rq.nsp_flag - r0)) return false;
+    if (rq.logits_out) HIP_TRY(hipMemcpyAsync(rq.logits_out + (size_t) r0 * NV, d.logits, (size_t) nr * NV * 4, hipMemcpyDeviceToHost, d.stream));
+    return true;
+}
+
+bool draft_verify(whisper_context & ctx, const std::vector<int32_t> & prompt, const int32_t * draft, const DraftPlan & plan, int nsp_row,
+                  float * logits_out, std::vector<whisper_token_data> & picks, int & accepted) {
+    if (!compute_ready(ctx, __func__)) return false;
+    State & st = *ctx.state; DeviceState & d = st.dev; const Vocab & v = ctx.model.vocab; const HParams & hp = ctx.model.hp;
+    const int64_t t0 = time_us();
+    const int P = (int) prompt.size(), n = plan.n, rows = n + 1;
+    if (P < 1 || n < 1 || P + n > hp.n_text_ctx || (int) plan.filters.size() != rows || !d.ban_dev) return false;
+    DraftView dv{};
+    if (!draft_ensure(d, rows, dv)) return false;
+    const int32_t tag = draft_next_tag(d.draft_seq);
+    int space_id = -1; { auto sp = v.token_to_id.find(" "); if (sp != v.token_to_id.end()) space_id = sp->second; }
+    for (int j = 0; j < rows; ++j) {
+        const StepFilter & f = plan.filters[j];
+        k::DecStep & hs = dv.h_steps[j];
+        memset(&hs, 0, sizeof(hs));
+        hs.token = j == 0 ? prompt.back() : draft[j - 1]; hs.pos = P - 1 + j;
+        hs.flags = (f.ban_blank ? 1 : 0) | (f.last_ts ? 2 : 0) | (f.penult_ts ? 4 : 0);
+        hs.space_id = space_id; hs.eot = v.eot; hs.beg = v.beg; hs.n_vocab = v.n_vocab;
+        hs.ts_floor_end = f.ts_floor_end; hs.ts_initial_start = f.ts_initial_start; hs.seq = tag;
+        if (j < n) dv.h_targets[j] = draft[j];
+    }
+    hipStream_t s = d.stream;
+    HIP_TRY(hipMemcpyAsync(dv.d_steps, dv.h_steps, (size_t) rows * sizeof(k::DecStep), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(dv.d_targets, dv.h_targets, (size_t) n * 4, hipMemcpyHostToDevice, s));
+    // prompt + draft[0 .. n) as one batch of sequence 0; logits of row P - 1 and of the n draft rows
+    Batch & b = st.batch;
+    std::vector<int32_t> x(prompt);
+    x.insert(x.end(), draft, draft + n);
+    b.prep_legacy(x.data(), P + n, 0, 0);
+    for (int i = 0; i < P + n; ++i) b.logits[i] = i >= P - 1 ? 1 : 0;
+    DeviceState::DraftReq rq{};
+    rq.d_steps = dv.d_steps; rq.d_targets = dv.d_targets; rq.n_targets = n; rq.part = (k::FsPartial *) d.draft_part; rq.out_host = dv.h_rec;
+    rq.d_match = dv.d_match; rq.logits_out = logits_out;
+    d.draft_req = &rq; d.nsp_row = nsp_row;
+    const bool ok = decode(ctx, b);
+    d.draft_req = nullptr; d.nsp_row = -1;
+    if (!ok) { (void) hipStreamSynchronize(s); return false; }
+    k::draft_finish(dv.d_match, rows, tag, dv.h_out, s);
+    if (!HIP_OK(hipGetLastError()) || !HIP_OK(hipStreamSynchronize(s))) return false;      // the call's one wait
+    std::vector<k::SampleOut> rec((size_t) rows);
+    if (!draft_collect(dv, rows, tag, rec.data(), 0, &accepted)) return false;
+    picks.resize((size_t) accepted + 1);
+    for (int j = 0; j <= accepted; ++j) picks[j] = whisper_token_data{ rec[j].id, rec[j].tid, rec[j].p, rec[j].plog, rec[j].pt, rec[j].ptsum, -1, -1, 0.0f };
+    d.chain_valid = false;
+    int64_t dt = time_us() - t0;                              // the batch's rows go where decode() would have put them
+    { const int64_t done = phase_settle(st, false); if (done > t0) dt = std::max<int64_t>(0, dt - (done - t0)); }
+    if (P + n < 16) { st.t_batchd_us += dt; st.n_batchd += P + n; } else { st.t_prompt_us += dt; st.n_prompt += P + n; }
+    st.n_sample += accepted + 1;
     return true;
 }
 

@@ -141,7 +141,7 @@ bool encode_layers_q_on(whisper_context & ctx, const EncBufsQ & e, hipStream_t s
 }
 
 bool decode_layers_q(whisper_context & ctx, int n, int n_kv, int kv_head, int Tc, const std::vector<int> & rows, float * lang_out,
-                     const int32_t * nsp_row_dev, float * nsp_logits, const DeviceState::ScoreReq * score) {
+                     const int32_t * nsp_row_dev, float * nsp_logits, const DeviceState::ScoreReq * score, const DeviceState::DraftReq * draft) {
     State & st = *ctx.state; DeviceState & d = st.dev; const Weights & w = ctx.w; const HParams & hp = ctx.model.hp;
     KVCache & kv = st.kv_self;
     const int S = hp.n_text_state, H = hp.n_text_head, Lt = hp.n_text_layer, NV = hp.n_vocab, n_ctx = (int) kv.size;
@@ -247,13 +247,14 @@ bool decode_layers_q(whisper_context & ctx, int n, int n_kv, int kv_head, int Tc
         }
         return item == score->n_items;
     }
-    st.logits.resize((size_t) n * NV);
+    if (!draft) st.logits.resize((size_t) n * NV);
     for (size_t r0 = 0; r0 < rows.size(); r0 += 8) {
         const int nr = (int) std::min<size_t>(8, rows.size() - r0);
         k::GemvArgs g{};
         g.x32 = d.dx; g.ln_g = w.d_ln_g; g.ln_b = w.d_ln_b; g.eps = hp.eps; g.n = nr; g.K = S; g.N = NV;
         g.epi = k::EPI_LOGITS; g.C = d.logits; g.ldc = NV; g.rows = d.d_rows + r0; g.pend = pend;
         k::qrows(g, nullptr, w.q_te, s);
+        if (draft) { if (!draft_group(ctx, *draft, (int) r0, nr)) return false; continue; }      // (the verifier's request: picked where it lies, nothing copied out)
         if (d.keep_logits_on_device && rows.size() <= 8) continue;
         HIP_TRY(hipMemcpyAsync(d.pinned, d.logits, (size_t) nr * NV * 4, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));

@@ -59,6 +59,51 @@ void emit_segment(whisper_context & ctx, State & st, const whisper_full_params &
 
 bool align_window(whisper_context & ctx, State & st, int seek, int seek_end, const std::vector<int32_t> & prompt_init, const Decoder & best, int32_t seg0);
 
+void decoder_advance(const whisper_context & ctx, const whisper_full_params & params, Decoder & d, int i, int seek, int seek_end, int n_max) {
+    const Vocab & v = ctx.model.vocab;
+    int & result_len = d.sequence.result_len;
+    const whisper_token_data & tok = d.sequence.tokens.back();
+    if (tok.id > v.beg) {
+        const int sd_new = 2 * (tok.id - v.beg);
+        if (d.has_ts && d.seek_delta > sd_new && result_len < i) { d.failed = true; return; }   // going back in time
+        d.seek_delta = sd_new; result_len = i + 1; d.has_ts = true;
+    }
+    grammar_accept_token(ctx, d.grammar, tok.id);
+    if (tok.id == v.eot || (params.max_tokens > 0 && i >= params.max_tokens) ||
+        (d.has_ts && seek + d.seek_delta + 100 >= seek_end)) {
+        if (result_len == 0) {
+            if (seek + d.seek_delta + 100 >= seek_end) result_len = i + 1;
+            else { d.failed = true; return; }
+        }
+        if (params.single_segment) { result_len = i + 1; d.seek_delta = 100 * WHISPER_CHUNK_SIZE; }
+        d.completed = true;
+        return;
+    }
+    if (ctx.model.n_loaded == 0) { d.seek_delta = 100 * WHISPER_CHUNK_SIZE; d.completed = true; return; }   // empty test model
+    if (i == n_max - 1 && (result_len == 0 || d.seek_delta < 100 * WHISPER_CHUNK_SIZE / 2)) { d.failed = true; return; }
+}
+
+DraftPlan draft_plan(const whisper_context & ctx, const whisper_full_params & params, int P, const int32_t * draft, int n_offered, int seek, int seek_end) {
+    const Vocab & v = ctx.model.vocab; const HParams & hp = ctx.model.hp;
+    const int n_max = hp.n_text_ctx / 2 - 4;
+    DraftPlan pl;
+    int n = std::min(n_offered, n_max - 1);
+    if (params.max_tokens > 0) n = std::min(n, params.max_tokens + 1);
+    n = std::min(n, hp.n_text_ctx - P - 1);
+    pl.n = std::max(0, n);
+    // the dry run: a decoder as the window's attempt starts it, fed the draft token by token
+    Decoder dd;
+    dd.seek_delta = 100 * WHISPER_CHUNK_SIZE;
+    pl.filters.reserve((size_t) pl.n + 1);
+    for (int j = 0; j <= pl.n; ++j) {
+        pl.filters.push_back(make_step_filter(v, hp, params, dd));
+        if (j == pl.n) break;
+        dd.sequence.tokens.push_back(whisper_token_data{ draft[j], 0, 0.f, 0.f, 0.f, 0.f, -1, -1, 0.f });
+        if (!dd.completed && !dd.failed) decoder_advance(ctx, params, dd, j, seek, seek_end, n_max);
+    }
+    return pl;
+}
+
 int full(whisper_context & ctx, whisper_full_params params, const float * samples, const float * d_samples, int n_samples) {
     BusyScope busy(ctx.device);                                      // (see wmi.h: kernels that wait inside a launch are used by a lone transcription only)
     State & st = *ctx.state;
@@ -67,6 +112,12 @@ int full(whisper_context & ctx, whisper_full_params params, const float * sample
     st.result_all.clear();
     st.ts_failed = false;
     st.lang_probs.clear();
+    // the draft armed for this call (wmi_set_draft): taken here whatever becomes of it; honoured in the first window's first attempt only
+    std::vector<int32_t> draft_tokens; draft_tokens.swap(st.draft);
+    float * const draft_logits_out = st.draft_logits_out; const int draft_logits_cap = st.draft_logits_cap;
+    st.draft_logits_out = nullptr; st.draft_logits_cap = 0;
+    st.draft_status = { (int32_t) draft_tokens.size(), 0, 0, 0, draft_tokens.empty() ? 1 : 2 };
+    bool first_window = true;
     // the no-speech mode of this call (wmi_set_no_speech; 0: nothing below launches or stores anything)
     const int nsm = ctx.no_speech_mode;
     st.windows.clear();
@@ -261,7 +312,27 @@ int full(whisper_context & ctx, whisper_full_params params, const float * sample
                 return nsm == 3 && it == 0 && p_known &&
                        no_speech_rule(nsm, p_win, params.no_speech_thold, false, 0.0, params.logprob_thold) == NSP_GATE;
             };
-            if (fast) {
+            // a draft: prompt + draft as ONE batch, every row's filtered greedy pick taken on the device (device.cpp: draft_verify); tokens
+            // 0 .. draft_acc of the window are draft_picks, the loop below replays them through the state machine
+            bool drafted = false; std::vector<whisper_token_data> draft_picks; int draft_acc = 0;
+            if (fast && first_window && it == 0 && !draft_tokens.empty()) {
+                const DraftPlan plan = draft_plan(ctx, params, (int) prompt.size(), draft_tokens.data(), (int) draft_tokens.size(), seek, seek_end);
+                if (plan.n <= 0) st.draft_status.reason = 3;
+                else {
+                    const bool nsp_here = want_p;
+                    if (nsp_here) p_asked = true;
+                    const bool ok = draft_verify(ctx, prompt, draft_tokens.data(), plan, nsp_here ? sot_idx : -1,
+                                                 draft_logits_cap >= plan.n + 1 ? draft_logits_out : nullptr, draft_picks, draft_acc);
+                    if (!ok || (params.abort_callback && params.abort_callback(params.abort_callback_user_data))) {
+                        WMI_ERR("%s: failed to decode\n", __func__);
+                        return -7;
+                    }
+                    drafted = true;
+                    st.draft_status.n_rows = plan.n; st.draft_status.n_accepted = draft_acc; st.draft_status.reason = 0;
+                }
+            }
+            first_window = false;
+            if (fast && !drafted) {
                 bool ok = true;
                 if (prompt.size() > 1) {            // all but the last prompt token: plain batch decode, no logits wanted
                     st.batch.prep_legacy(prompt.data(), (int) prompt.size() - 1, 0, 0);
@@ -280,7 +351,7 @@ int full(whisper_context & ctx, whisper_full_params params, const float * sample
                     WMI_ERR("%s: failed to decode\n", __func__);
                     return -7;
                 }
-            } else {
+            } else if (!fast) {
             st.batch.prep_legacy(prompt.data(), (int) prompt.size(), 0, 0);
             if (want_p) { st.dev.nsp_row = sot_idx; p_asked = true; }
             const bool ok_prompt = decode(ctx, st.batch);
@@ -356,6 +427,7 @@ int full(whisper_context & ctx, whisper_full_params params, const float * sample
                     Decoder & d = st.decoders[j];
                     if (d.completed || d.failed) continue;
                     if (fast) {
+                        if (drafted && i <= draft_acc) { fast_next = draft_picks[i]; st.draft_status.n_emitted_from_draft++; }
                         d.sequence.tokens.push_back(fast_next);
                         d.sequence.sum_logprobs_all += fast_next.plog;
                     } else if (!beam) {
@@ -399,26 +471,7 @@ int full(whisper_context & ctx, whisper_full_params params, const float * sample
                 for (int j = 0; j < n_cur; ++j) {
                     Decoder & d = st.decoders[j];
                     if (d.completed || d.failed) continue;
-                    int & result_len = d.sequence.result_len;
-                    const whisper_token_data & tok = d.sequence.tokens.back();
-                    if (tok.id > v.beg) {
-                        const int sd_new = 2 * (tok.id - v.beg);
-                        if (d.has_ts && d.seek_delta > sd_new && result_len < i) { d.failed = true; continue; }   // going back in time
-                        d.seek_delta = sd_new; result_len = i + 1; d.has_ts = true;
-                    }
-                    grammar_accept_token(ctx, d.grammar, tok.id);
-                    if (tok.id == v.eot || (params.max_tokens > 0 && i >= params.max_tokens) ||
-                        (d.has_ts && seek + d.seek_delta + 100 >= seek_end)) {
-                        if (result_len == 0) {
-                            if (seek + d.seek_delta + 100 >= seek_end) result_len = i + 1;
-                            else { d.failed = true; continue; }
-                        }
-                        if (params.single_segment) { result_len = i + 1; d.seek_delta = 100 * WHISPER_CHUNK_SIZE; }
-                        d.completed = true;
-                        continue;
-                    }
-                    if (ctx.model.n_loaded == 0) { d.seek_delta = 100 * WHISPER_CHUNK_SIZE; d.completed = true; continue; }   // empty test model
-                    if (i == n_max - 1 && (result_len == 0 || d.seek_delta < 100 * WHISPER_CHUNK_SIZE / 2)) { d.failed = true; continue; }
+                    decoder_advance(ctx, params, d, i, seek, seek_end, n_max);
                 }
 
                 bool all_done = true;
@@ -428,6 +481,9 @@ int full(whisper_context & ctx, whisper_full_params params, const float * sample
 
                 if (fast) {
                     Decoder & d0 = st.decoders[0];
+                    if (drafted && i < draft_acc) continue;                  // the next token is the pass's too
+                    // behind the last token of the pass: the cells of the refused draft rows go, the one-row step goes on from pick_a
+                    if (drafted && i == draft_acc) kv_seq_rm(st.kv_self, 0, (int) prompt.size() + draft_acc, -1);
                     if (!decode_greedy_step(ctx, d0.sequence.tokens.back().id, (int) prompt.size() + i, step_filter(d0), fast_next) ||
                         (params.abort_callback && params.abort_callback(params.abort_callback_user_data))) {
                         WMI_ERR("%s: failed to decode\n", __func__);

@@ -16,6 +16,7 @@
 #include "kernels.h"
 #include <algorithm>
 #include "wave_ops.h"
+#include "filter_combine.h"
 
 namespace wmi { namespace k {
 
@@ -23,16 +24,6 @@ namespace {
 
 constexpr int NB = 64;          // workgroups of the statistics pass
 constexpr int NT = 256;
-
-using MaxIdx = FsMaxIdx;
-__device__ __forceinline__ MaxIdx better(MaxIdx a, MaxIdx b) {      // larger value, then smaller index (first occurrence)
-    return (b.v > a.v || (b.v == a.v && b.i < a.i)) ? b : a;
-}
-__device__ __forceinline__ MaxIdx wave_max(MaxIdx m) {
-    _Pragma("unroll") for (int o = 32; o > 0; o >>= 1) { MaxIdx t; t.v = WMI_SHX(m.v, o); t.i = WMI_SHX(m.i, o); m = better(m, t); }
-    return m;
-}
-__device__ __forceinline__ float wave_sum(float v) { for (int o = 32; o > 0; o >>= 1) v += WMI_SHX(v, o); return v; }
 
 // per-workgroup partial statistics of the filtered logits: maxima with first-index tie-break (all / text /
 // timestamps) and sums of exp(l - local max) — combined exactly (online soft-max identity) by the second kernel
@@ -134,29 +125,7 @@ __global__ __launch_bounds__(64) void k_filter_pick(const Partial * __restrict__
     Partial pq[PPL];                                     // partials lane, lane + 64, ... (all requested before the first use)
 #pragma unroll
     for (int q = 0; q < PPL; ++q) { const int idx = lane + 64 * q; pq[q] = part[idx < nparts ? idx : 0]; }
-    MaxIdx la = {-INFINITY, 0x7fffffff}, lt = la, lz = la;
-#pragma unroll
-    for (int q = 0; q < PPL; ++q) {
-        if (lane + 64 * q >= nparts) { pq[q].all = MaxIdx{-INFINITY, 0x7fffffff}; pq[q].txt = pq[q].all; pq[q].ts = pq[q].all; pq[q].sum = 0.0f; pq[q].sum_ts = 0.0f; }
-        la = better(la, pq[q].all); lt = better(lt, pq[q].txt); lz = better(lz, pq[q].ts);
-    }
-    const MaxIdx a = wave_max(la), t = wave_max(lt), z = wave_max(lz);
-    const float M = a.v;
-    float lsum = 0.0f, lsum_ts = 0.0f;
-#pragma unroll
-    for (int q = 0; q < PPL; ++q) {
-        const float w = pq[q].all.v > -INFINITY ? expf(pq[q].all.v - M) : 0.0f;      // rescale the local sums to the global max
-        if (q == 0) { lsum = pq[q].sum * w; lsum_ts = pq[q].sum_ts * w; } else { lsum += pq[q].sum * w; lsum_ts += pq[q].sum_ts * w; }
-    }
-    const float sum = wave_sum(lsum), sum_ts = wave_sum(lsum_ts);
-    // every lane evaluates the pick (uniform values): no broadcast between the decision and the next step's gathers
-    const float lse = logf(sum) + M;
-    // timestamp log-mass vs best text token (W/whisper.cpp:4659-4683)
-    const float ts_logprob = sum_ts > 0.0f ? logf(sum_ts) + M - lse : -INFINITY;
-    const float max_text = t.v > -INFINITY ? t.v - lse : -INFINITY;
-    const bool force_ts = ts_logprob > max_text;
-    const MaxIdx pick = force_ts ? z : a;
-    const int id = pick.i;
+    WMI_FS_COMBINE(PPL)                                  // (filter_combine.h: the text k_draft_pick compiles too) -> a, t, z, M, sum_ts, lse, pick, id
     // the next greedy step feeds this pick at the next position (the host checks that before it replays the chained step):
     // its embedding + positional rows are requested now, the result goes to the host while they are in flight
     const int pos1 = st0.y + 1;
@@ -173,15 +142,7 @@ __global__ __launch_bounds__(64) void k_filter_pick(const Partial * __restrict__
         }
     }
     if (lane == 0) {
-        SampleOut r;
-        r.id = id; r.plog = pick.v - lse; r.p = expf(r.plog); r.seq0 = seqv; r.seq = seqv;
-        // timestamp statistics over the post-filter probabilities (W/whisper.cpp:4793-4809)
-        const float p_ts_max = z.v > -INFINITY ? expf(z.v - lse) : 0.0f;
-        const double sum_ts_p = (double) sum_ts * (double) expf(M - lse);
-        r.tid = p_ts_max > 0.0f ? z.i : 0;
-        r.pt = (float) ((double) p_ts_max / (sum_ts_p + 1e-10));
-        r.ptsum = (float) sum_ts_p;
-        if (r.id >= beg) { r.tid = r.id; r.pt = r.p; }
+        WMI_FS_RECORD()                                  // -> SampleOut r
         *out = r;
         if (out_host) {                                      // two 16-byte stores, each carrying the step's sequence number
             const int4 * h = (const int4 *) &r;

@@ -596,6 +596,19 @@ void filter_draw(const float * logits, const uint8_t * static_ban, const DecStep
                  void * scratch, hipStream_t st, int n_rows, int tid_default);
 size_t filter_draw_scratch_bytes(int n_rows);
 void filter_stats(const float * logits, const uint8_t * static_ban, const DecStep * step, FsPartial * part, hipStream_t st, int n_rows);
+// The draft verifier (k_draft.hip): the filtered greedy picks of teacher-forced rows, checked against the draft on the device.
+//   draft_pick:   behind filter_stats(logits, ban, steps, part, st, n_group) on a group of n_group <= 8 rows: group row g is row row0 + g of
+//                 the call.  Its 64 partials are combined with k_filter_pick<.., 1>'s arithmetic (filter_combine.h) — the record equals
+//                 filter_argmax's bit for bit — and stored to out_host[row0 + g] (pinned; two 16-byte stores tagged steps[g].seq);
+//                 match[row0 + g] = 1 where row0 + g < n_targets and the pick is targets[row0 + g], else 0.  steps, part: the group's;
+//                 targets, out_host, match: the call's.  targets holds at least one entry.
+//   draft_finish: one wavefront behind the last group: accepted = the number of leading 1s of match[0 .. n_rows), {accepted, tag} as ONE
+//                 8-byte store (pinned).
+// Workgroups are independent inside every launch; no atomics.
+struct DraftOut { int32_t accepted, tag; };
+void draft_pick(const FsPartial * part, const DecStep * steps, const int32_t * targets, int row0, int n_group, int n_targets,
+                SampleOut * out_host, int32_t * match, hipStream_t st);
+void draft_finish(const int32_t * match, int n_rows, int32_t tag, DraftOut * out, hipStream_t st);
 // Grammar-constrained decoding on the device (k_grammar.hip; the evaluator is grammar_eval.h).  grammar_reject: grid (ceil(eot / 256), rows),
 // one thread per token id — reject [n_rows][n_vocab] gets ge::REJECTED / ge::ACCEPTED for ids below eot (the bytes from eot on are never
 // written: the caller keeps them 0), overflow[row] = 1 (a plain store; the caller zeroes the words) when a token's working set exceeded its

@@ -140,7 +140,10 @@ struct wmi_long_params wmi_long_default_params(void) { return long_default_param
 
 int wmi_full_long(struct whisper_context * ctx, struct whisper_full_params params, const float * pcm, int n_samples, int pcm_on_device,
                   const struct wmi_long_params * long_params) {
-    if (!ctx || !ctx->state || !pcm || n_samples < 0) return -1;
+    if (!ctx || !ctx->state) return -1;
+    CtxLock lk(ctx);
+    DraftRefuse no_draft(ctx->state.get());                 // (pieces in lock-step: no draft is carried; dropped whatever the call returns)
+    if (!pcm || n_samples < 0) return -1;
     const wmi_long_params lp = long_params ? *long_params : long_default_params();
     if (!long_params_ok(lp) || params.offset_ms < 0 || params.duration_ms < 0) return -1;
     if (params.new_segment_callback || params.progress_callback || params.encoder_begin_callback || params.logits_filter_callback) {
@@ -148,7 +151,6 @@ int wmi_full_long(struct whisper_context * ctx, struct whisper_full_params param
         return -1;
     }
     if (n_samples == 0) { WMI_ERR("%s: no signal data available\n", __func__); return -3; }
-    CtxLock lk(ctx);
     if (!compute_ready(*ctx, __func__)) return -2;
     try {
         (void) hipSetDevice(ctx->device);

@@ -66,7 +66,11 @@ int wmi_pool_size(struct wmi_pool * p) { return p ? (int) p->ctx.size() : 0; }
 struct whisper_context * wmi_pool_context(struct wmi_pool * p, int i) { return (p && i >= 0 && i < (int) p->ctx.size()) ? p->ctx[i] : nullptr; }
 
 int wmi_pool_full(struct wmi_pool * p, struct whisper_full_params params, const float * const * pcm, const int * n_samples, int n_chunks) {
-    if (!p || !pcm || !n_samples || n_chunks < 0) return -1;
+    if (!p) return -1;
+    if (!pcm || !n_samples || n_chunks < 0) {                // (no draft is carried: dropped on an argument error as well)
+        for (whisper_context * c : p->ctx) { std::lock_guard<std::recursive_mutex> lk(c->mu); DraftRefuse no_draft(c->state.own); }
+        return -1;
+    }
     const int N = (int) p->ctx.size();
     try {
     p->owner.assign(n_chunks, 0); p->index.assign(n_chunks, 0);
@@ -85,6 +89,7 @@ int wmi_pool_full(struct wmi_pool * p, struct whisper_full_params params, const 
         const int64_t t0 = time_us();
         try {
             std::lock_guard<std::recursive_mutex> lk(p->ctx[d]->mu);
+            DraftRefuse no_draft(p->ctx[d]->state.own);         // (chunks in lock-step: no draft is carried)
             if (!ptrs[d].empty()) {
                 (void) hipSetDevice(p->ctx[d]->device);
                 rets[d] = full_batch(*p->ctx[d], params, ptrs[d].data(), lens[d].data(), (int) ptrs[d].size(), false);

@@ -257,6 +257,7 @@ int wmi_full_long_wav(struct whisper_context * ctx, struct whisper_full_params p
                       const struct wmi_long_params * long_params) {
     if (!ctx || !ctx->state) return -101;
     try {
+        { Scope lk(ctx); DraftRefuse no_draft(ctx->state.get()); }         // (no draft is carried: dropped whatever the call returns)
         WavJob job; job.wav = wav; job.converter = converter;
         job.plan = wav_plan(wav, converter, __func__);
         if (job.plan.err) return -100 + job.plan.err;
@@ -275,8 +276,10 @@ int wmi_full_long_wav(struct whisper_context * ctx, struct whisper_full_params p
 }
 
 int wmi_full_batch_wav(struct whisper_context * ctx, struct whisper_full_params params, const struct wmi_wav * wavs, int n, int converter) {
-    if (!ctx || !ctx->state || !wavs || n < 0) return -101;
+    if (!ctx || !ctx->state) return -101;
     try {
+        { Scope lk(ctx); DraftRefuse no_draft(ctx->state.get()); }         // (no draft is carried: dropped whatever the call returns)
+        if (!wavs || n < 0) return -101;
         std::vector<WavJob> jobs((size_t) n);
         std::vector<size_t> off((size_t) n);
         size_t total = 0;

@@ -291,6 +291,16 @@ struct DeviceState {
     void * score_scratch = nullptr; int32_t * score_items = nullptr; size_t score_items_cap = 0; float * score_lp = nullptr; size_t score_lp_cap = 0;
     void * score_host = nullptr; size_t score_host_cap = 0; int32_t score_seq = 0;
     const ScoreReq * score_req = nullptr;
+    // the draft verifier (device.cpp: draft_*; kernels.h: draft_*), all made on first use and grow-only: the rows' statistics
+    // partials, a device block {DecStep[rows] | targets[rows] | match[rows]}, a pinned block {DraftOut (16 bytes) | SampleOut[rows] |
+    // DecStep[rows] | targets[rows]}.  draft_req asks the next decode() to pick every flagged row where the vocabulary projection leaves it
+    // (draft_group behind every group of <= 8) instead of copying it out, a request for this call only: no wait, no host image, no
+    // reference timers.  nsp_flag: decode() notes here which flagged row carries the no-speech head (-1: none, or an unflagged row);
+    // logits_out (tests): flagged row i goes to logits_out + i * n_vocab
+    struct DraftReq { const k::DecStep * d_steps = nullptr; const int32_t * d_targets = nullptr; int n_targets = 0; k::FsPartial * part = nullptr;
+                      k::SampleOut * out_host = nullptr; int32_t * d_match = nullptr; float * logits_out = nullptr; mutable int nsp_flag = -1; };
+    void * draft_part = nullptr, * draft_dev = nullptr, * draft_host = nullptr; int draft_cap = 0; int32_t draft_seq = 0;
+    const DraftReq * draft_req = nullptr;
 };
 
 struct State {
@@ -312,6 +322,9 @@ struct State {
     struct DtwDims { int n = 0, n_sot = 0, R = 0, M = 0, n_pairs = 0; } dtw_last; std::vector<int32_t> dtw_jumps;
     int64_t t_dtw_us = 0; int32_t n_dtw = 0;
     int64_t t_score_us = 0; int32_t n_score = 0, n_score_launches = 0;     // the text scorer's own timer: calls, and launches of its kernels (wmi_get_score_timings)
+    // wmi_set_draft: the tokens armed for this state's NEXT transcription call (full() takes them at its start, whatever becomes of them),
+    // what became of the last call's (wmi_draft_status), and the tests' buffer for the logits rows the verifier saw (taken with the draft)
+    std::vector<int32_t> draft; struct wmi_draft_status draft_status{0, 0, 0, 0, 1}; float * draft_logits_out = nullptr; int draft_logits_cap = 0;
     // wmi_grammar_status: sampling steps whose reject masks k_grammar_reject wrote / rows whose mask the host computed instead, since the
     // start of the last transcription call
     int32_t gram_steps_dev = 0, gram_rows_host = 0; float gram_reject_us = 0.0f;      // (the last wmi_selftest_grammar launch, by events)
@@ -329,6 +342,15 @@ struct State {
     int32_t exp_n_audio_ctx = 0;
     int     enc_n_ctx = 0;                        // n_ctx of the last encode (cross cache extent)
     DeviceState dev;
+};
+
+// a call that cannot carry a draft (lock-step, long, pool and parallel calls: DESIGN.md §11): whatever is armed on the state is dropped
+// when the call starts, and the call leaves "not eligible" (or "nothing armed") as its status, whatever its inner calls wrote there
+struct DraftRefuse {
+    State * st; int32_t n = 0;
+    explicit DraftRefuse(State * s) : st(s) { if (st) { n = (int32_t) st->draft.size(); st->draft.clear(); st->draft_logits_out = nullptr; st->draft_logits_cap = 0; } }
+    ~DraftRefuse() { if (st) st->draft_status = { n, 0, 0, 0, n > 0 ? 2 : 1 }; }
+    DraftRefuse(const DraftRefuse &) = delete; DraftRefuse & operator=(const DraftRefuse &) = delete;
 };
 
 // Lock-step transcription of several independent chunks on one GPU (8 chunks per GPU; same ownership
@@ -499,7 +521,8 @@ void enqueue_rows_step_q(whisper_context & ctx, int nb);
 void enqueue_rows_lang_step_q(whisper_context & ctx, int nb, float * out);      // the same step ending in the language head (batch.cpp: detection)
 // nsp_row_dev (device, one batch row index): that row's raw logits also go to nsp_logits (the no-speech head reads them there)
 bool decode_layers_q(whisper_context & ctx, int n, int n_kv, int kv_head, int Tc, const std::vector<int> & rows, float * lang_out = nullptr,
-                     const int32_t * nsp_row_dev = nullptr, float * nsp_logits = nullptr, const DeviceState::ScoreReq * score = nullptr);
+                     const int32_t * nsp_row_dev = nullptr, float * nsp_logits = nullptr, const DeviceState::ScoreReq * score = nullptr,
+                     const DeviceState::DraftReq * draft = nullptr);
 void enqueue_greedy_step_q(whisper_context & ctx, int Tc);
 // The grammar on the device (wmi_set_grammar_device; grammar_eval.h, k_grammar.hip).  grammar_flatten: the rules as one element array
 // (ok = false: malformed or too long — the host's logic serves such a grammar); grammar_row_state: a decoder's stacks and partial
@@ -532,6 +555,21 @@ inline StepFilter make_step_filter(const Vocab & v, const HParams & hp, const wh
     }
     return f;
 }
+// The per-token state machine of a decoder (W/whisper.cpp:5474-5533): d.sequence.tokens.back() has just been sampled at iteration i of the
+// window at seek — timestamps move seek_delta, <eot> / max_tokens / the end of the audio complete the decoder, the failure rules fail it.
+// The one statement of it: full()'s loop over the live decoders, the draft's dry run and the drafted tokens' replay all call this.
+void decoder_advance(const whisper_context & ctx, const whisper_full_params & params, Decoder & d, int i, int seek, int seek_end, int n_max);
+// The draft verifier (DESIGN.md §5 has the rule).  draft_plan is pure host arithmetic: n = the draft tokens fed behind a prompt of P tokens
+// (0: clipped to nothing) and filters [n + 1], the step filter of logits row j = make_step_filter of a fresh decoder that has sampled
+// draft[0 .. j) (decoder_advance over a copy; once it has completed or failed only the history grows).  draft_verify feeds prompt + draft[0 .. n)
+// as one batch (sequence 0, positions 0 .. P + n), picks rows P - 1 .. P + n - 1 on the device and waits once: picks [n + 1] and the accepted
+// length a <= n.  nsp_row >= 0: the no-speech head on that batch row rides along.  draft_group is decode()'s hook behind the vocabulary
+// projection of the flagged rows [r0, r0 + nr).
+struct DraftPlan { int n = 0; std::vector<StepFilter> filters; };
+DraftPlan draft_plan(const whisper_context & ctx, const whisper_full_params & params, int P, const int32_t * draft, int n_offered, int seek, int seek_end);
+bool draft_group(whisper_context & ctx, const DeviceState::DraftReq & rq, int r0, int nr);
+bool draft_verify(whisper_context & ctx, const std::vector<int32_t> & prompt, const int32_t * draft, const DraftPlan & plan, int nsp_row,
+                  float * logits_out, std::vector<whisper_token_data> & picks, int & accepted);
 // forms: when given, the launch form the step took (STEP_FORM_* bits; the test hook wmi_selftest_greedy_step reports them)
 enum : unsigned { STEP_FORM_LONG_KV = 1, STEP_FORM_CHAINED = 2, STEP_FORM_GRAPH = 4, STEP_FORM_PAIRED = 8, STEP_FORM_FRONTED = 16,
                   STEP_FORM_BACKED = 32, STEP_FORM_RERUN = 64, STEP_FORM_SLOW = 128, STEP_FORM_QUANTISED = 256 };

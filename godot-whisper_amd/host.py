@@ -57,6 +57,7 @@ class SpeechToText:
         self._grammar = None
         self.set_grammar(grammar, grammar_penalty)
         self.last_windows = []
+        self.last_draft_status = {}
         self.language = "en"  # Language enum -> code, src/speech_to_text.cpp:117-324
         self.settings = dict(SETTINGS)
         if settings:
@@ -146,13 +147,28 @@ class SpeechToText:
             p.n_threads = int(self.n_threads)
         return p
 
-    def transcribe(self, buffer: np.ndarray, initial_prompt: str = "", audio_ctx: int = 0, params=None) -> list:
+    def draft_status(self) -> dict:
+        """include/wmi_device.h wmi_draft_status: what became of the last transcription call's draft"""
+        s = abi.wmi_draft_status()
+        if not self.ctx or self.lib.wmi_draft_status(self.ctx, C.byref(s)) != 0:
+            return {}
+        return {k: int(getattr(s, k)) for k, _ in abi.wmi_draft_status._fields_}
+
+    def transcribe(self, buffer: np.ndarray, initial_prompt: str = "", audio_ctx: int = 0, params=None, draft=None) -> list:
+        """draft (product library only, include/wmi_device.h wmi_set_draft): token ids the call verifies in one decoder pass and decodes
+        on from where they stop being the greedy decode; the result is the undrafted call's.  last_draft_status says what became of it."""
         if not self.ctx:
             return []  # ERR_PRINT("Context instance is null")
         buffer = np.ascontiguousarray(buffer, dtype=np.float32)
         p = params if params is not None else self.full_params(initial_prompt, audio_ctx)
+        if draft is not None:
+            d = np.ascontiguousarray(draft, dtype=np.int32)
+            if self.lib.wmi_set_draft(self.ctx, d.ctypes.data_as(C.c_void_p) if d.size else None, int(d.size)) != 0:
+                raise ValueError("wmi_set_draft refused the draft (an id outside the vocabulary)")
         ret = self.lib.whisper_full(self.ctx, p, _fptr(buffer), int(buffer.size))
         self.last_ret = ret
+        if draft is not None or hasattr(self.lib, "wmi_draft_status"):
+            self.last_draft_status = self.draft_status()
         if ret != 0:
             return []  # ERR_PRINT("Failed to process audio, returned ...")
         return self.collect()
@@ -540,11 +556,16 @@ class CaptureStreamToText(SpeechToText):
     16 kHz PCM stay on the device) or, for comparison, over resample() / voice_activity_detection() / transcribe() on host arrays."""
 
     def __init__(self, lib, settings=None, transcribe_interval: float = 0.3, minimum_sentence_ms: int = 3000,
-                 maximum_sentence_ms: int = 15000, punctuation_characters: str = ".!?;。；？！", no_speech_gate: bool = False):
+                 maximum_sentence_ms: int = 15000, punctuation_characters: str = ".!?;。；？！", no_speech_gate: bool = False,
+                 draft_reuse: bool = False):
         """no_speech_gate: transcribe in the no-speech mode "gate" (wmi_set_no_speech 3).  A step whose window was gated is treated like
-        "no activity": nothing is emitted for it and the loop goes on."""
+        "no activity": nothing is emitted for it and the loop goes on.
+        draft_reuse (stream_capture on a session; wmi_capture_set_draft 1): every step offers the previous step's tokens as a draft —
+        the messages are the same, the steps shorter; draft_statuses collects every step's wmi_draft_status."""
         super().__init__(lib, settings, no_speech=abi.NO_SPEECH_GATE if no_speech_gate else 0)
         self.no_speech_gate = bool(no_speech_gate)
+        self.draft_reuse = bool(draft_reuse)
+        self.draft_statuses = []
         self.interval = transcribe_interval
         self.min_ms = minimum_sentence_ms
         self.max_ms = maximum_sentence_ms
@@ -612,6 +633,9 @@ class CaptureStreamToText(SpeechToText):
         vad_thold = float(self.settings["audio/input/transcribe/vad_treshold"])
         freq_thold = float(self.settings["audio/input/transcribe/freq_treshold"])
         sess = CaptureSession(self, mix_rate, interpolator_type, frames_hint=int(maximum_sentence_time * mix_rate)) if use_session else None
+        if sess and self.draft_reuse:
+            self.lib.wmi_capture_set_draft(sess.cap, 1)
+        self.draft_statuses = []
         try:
             start, pos, calls, last_token_count = 0, 0, 0, 0
             while pos < xy.shape[0]:
@@ -636,6 +660,7 @@ class CaptureStreamToText(SpeechToText):
                     p.temperature_inc = float(temperature_inc)
                 if sess:
                     self.last_ret = sess.full(p)
+                    self.draft_statuses.append(self.draft_status())
                     tokens = self.collect() if self.last_ret == 0 else []
                 else:
                     tokens = self.transcribe(resampled, "", audio_ctx, params=p)

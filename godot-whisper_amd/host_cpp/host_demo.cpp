@@ -78,6 +78,7 @@ int main(int argc, char ** argv) {
     if (mode == "capture") {
         std::vector<float> xy((const float *) raw.data(), (const float *) raw.data() + raw.size() / 4);
         CaptureStreamToText node;
+        for (int i = 4; i < argc; ++i) if (std::string(argv[i]) == "--draft-reuse") node.draft_reuse = true;
         node.set_language_model(model.data(), model.size());
         const auto ups = node.stream_capture(xy, language, SpeechToText::SRC_SINC_FASTEST, audio_ctx > 0 ? audio_ctx : -1, prompt != "calls");
         printf("[");

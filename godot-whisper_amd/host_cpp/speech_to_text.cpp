@@ -50,6 +50,17 @@ int SpeechToText::set_token_dtw(bool on, const std::vector<int32_t> & layer_head
     return wmi_set_token_dtw(context_instance, on ? 1 : 0, token_dtw_pairs.data(), (int) token_dtw_pairs.size() / 2);
 }
 
+int SpeechToText::set_draft(const std::vector<int32_t> & tokens) {
+    if (!context_instance) return -1;
+    return wmi_set_draft(context_instance, tokens.empty() ? nullptr : tokens.data(), (int) tokens.size());
+}
+
+struct wmi_draft_status SpeechToText::draft_status() const {
+    struct wmi_draft_status s = { 0, 0, 0, 0, 1 };
+    if (context_instance) (void) wmi_draft_status(context_instance, &s);
+    return s;
+}
+
 int SpeechToText::set_no_speech(int mode) {
     const int prev = no_speech;
     no_speech = mode < 0 ? 0 : (mode > 3 ? 3 : mode);
@@ -372,6 +383,7 @@ std::vector<CaptureStreamToText::Update> CaptureStreamToText::stream_capture(con
     const size_t step = std::max<size_t>((size_t) std::lround(transcribe_interval * mix_rate), 1);
     wmi_capture * cap = use_session ? wmi_capture_init(context_instance, mix_rate, (int) interpolator_type, (int) (maximum_sentence_ms / 1000.0 * mix_rate)) : nullptr;
     if (use_session && !cap) { fprintf(stderr, "ERROR: wmi_capture_init failed\n"); return out; }
+    if (cap && draft_reuse) (void) wmi_capture_set_draft(cap, 1);   // every step offers the previous step's tokens as a draft
     size_t start = 0, pos = 0; int calls = 0, last_token_count = 0;
     std::vector<float> resampled;
     while (pos < n_frames) {

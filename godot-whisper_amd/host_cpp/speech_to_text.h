@@ -72,6 +72,11 @@ public:
     void set_grammar(const std::vector<std::vector<whisper_grammar_element>> & rules, float penalty = 100.0f);
     int  set_grammar_device(bool on);
     bool get_grammar_device() const { return grammar_device; }
+    // not in the reference: a draft for the NEXT transcription call (include/wmi_device.h wmi_set_draft): token ids the call verifies in one
+    // decoder pass and decodes on from where they stop being the greedy decode — the result is the undrafted call's.  An empty list clears
+    // it.  Returns what wmi_set_draft does (-1 without a context); draft_status(): what became of the last call's draft.
+    int  set_draft(const std::vector<int32_t> & tokens);
+    struct wmi_draft_status draft_status() const;
 
     // src/speech_to_text.h:151-156, :162 — resample(PackedVector2Array buffer, InterpolatorType): stereo capture frames at the mix rate
     // -> mono 16 kHz.  The reference folds on the CPU and calls libsamplerate's src_simple; here both steps run on the device
@@ -138,6 +143,7 @@ class CaptureStreamToText : public SpeechToText {
 public:
     using SpeechToText::SpeechToText;
     float transcribe_interval = 0.3f;
+    bool  draft_reuse = false;       // not in the reference: stream_capture on a session offers every step the previous step's tokens as a draft (wmi_capture_set_draft)
     int   minimum_sentence_ms = 3000, maximum_sentence_ms = 15000;
     int   hallucinating_count = 1;
     std::string punctuation_characters = ".!?;\xe3\x80\x82\xef\xbc\x9b\xef\xbc\x9f\xef\xbc\x81";

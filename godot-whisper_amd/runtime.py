@@ -145,6 +145,16 @@ DEVICE_API = [
     ("wmi_selftest_score_rows", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("wmi_selftest_score_plan", C.c_int, [C.c_void_p, abi.wmi_score_params, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                           C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_int]),
+    ("wmi_set_draft", C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    ("wmi_set_draft_with_state", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    ("wmi_draft_status", C.c_int, [C.c_void_p, C.POINTER(abi.wmi_draft_status)]),
+    ("wmi_draft_status_from_state", C.c_int, [C.c_void_p, C.POINTER(abi.wmi_draft_status)]),
+    ("wmi_capture_set_draft", C.c_int, [C.c_void_p, C.c_int]),
+    ("wmi_selftest_draft_plan", C.c_int, [C.c_void_p, abi.whisper_full_params, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int32),
+                                          C.c_void_p, C.c_void_p]),
+    ("wmi_selftest_draft_rows", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.POINTER(C.c_int32)]),
+    ("wmi_selftest_draft_logits", C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     ("wmi_long_default_params", abi.wmi_long_params, []),
     ("wmi_full_long", C.c_int, [C.c_void_p, abi.whisper_full_params, C.c_void_p, C.c_int, C.c_int, C.POINTER(abi.wmi_long_params)]),
     ("wmi_long_n_pieces", C.c_int, [C.c_void_p]),

@@ -814,6 +814,56 @@ WHISPER_API int  wmi_selftest_score_plan(struct whisper_context * ctx, struct wm
                                          const int32_t * n_tokens, int n_texts, int32_t * prefix, int cap_prefix, int * n_prefix, int32_t * first,
                                          int32_t * prefix_target, int32_t * rows, int cap_rows, int * n_rows, int32_t * pass_text0, int cap_passes);
 
+/* Verify a draft transcript in one decoder pass and decode only what differs.  The caller often has a good guess of a window's tokens — the
+ * streaming node's previous result, a smaller model's output, a transcript re-checked after a parameter change.  An armed draft is fed
+ * teacher-forced behind the prompt as ONE decoder batch; the filtered greedy pick of every row is taken on the device where its logits lie;
+ * the longest prefix of the draft that IS the greedy decode is accepted together with the one token the pass gives for free behind it, and
+ * the ordinary one-row step goes on from there.  The result is a greedy decode, never an approximation of one: a wrong draft costs one
+ * batch.  DESIGN.md section 5 has the rule; the short form:
+ *   honoured only in the first window of a call, at the first temperature, on whisper_full's device greedy path (greedy, temperature 0,
+ *   best_of 1 there, no logits_filter_callback, no grammar, weights loaded); P = the window's prompt length, n_max = n_text_ctx / 2 - 4,
+ *   n = min(n_offered, n_max - 1, max_tokens > 0 ? max_tokens + 1 : inf, n_text_ctx - P - 1); n <= 0: clipped to nothing.
+ *   wmi_set_draft         arms the state's NEXT transcription call (whisper_full*, wmi_full_device_pcm, wmi_capture_full, wmi_full_wav); the
+ *                         tokens are copied; the call consumes the draft whether it could use it or not; n = 0 clears it.  Returns 0; -1 for
+ *                         n < 0, a NULL list with n > 0, or an id < 0 or >= n_vocab — nothing is armed (an earlier draft stays), no device
+ *                         is touched.  Calls that cannot carry a draft (wmi_full_batch*, wmi_full_long*, wmi_pool_full,
+ *                         whisper_full_parallel, wmi_capture_full_batch) clear it and report reason 2, whatever they return (an
+ *                         argument error included; only a NULL context or a context without a state touches nothing).  A call that
+ *                         can carry one takes it where its transcription starts: one that returns before that (wmi_full_wav on a
+ *                         clip it cannot plan, wmi_capture_full on a failed resample) leaves the draft armed.
+ *   wmi_draft_status      what became of the last transcription call's draft: n_offered tokens were armed, n_rows draft tokens were fed
+ *                         (n above), n_accepted of them were the greedy decode, n_emitted_from_draft window tokens were taken from the
+ *                         pass (at most n_accepted + 1; fewer where one of them completed or failed the decoder); reason 0 used,
+ *                         1 nothing armed, 2 call not eligible, 3 clipped to nothing.
+ *   wmi_capture_set_draft mode 1: every wmi_capture_full arms the token ids of the session's previous successful result (all tokens of all
+ *                         its segments, in order) before it runs; wmi_capture_keep_last and a failed call forget them.  Mode 0 (default):
+ *                         off.  Returns the previous mode, -1 for a NULL session.
+ * wmi_get_timings of a drafted call shows fewer n_decode steps and more n_prompt (or n_batchd) rows: the draft's rows are batch rows.
+ * Off unless armed: a context that never arms a draft allocates and launches nothing for it. */
+struct wmi_draft_status { int32_t n_offered, n_rows, n_accepted, n_emitted_from_draft, reason; };
+WHISPER_API int wmi_set_draft(struct whisper_context * ctx, const whisper_token * tokens, int n);
+WHISPER_API int wmi_set_draft_with_state(struct whisper_context * ctx, struct whisper_state * state, const whisper_token * tokens, int n);
+WHISPER_API int wmi_draft_status(struct whisper_context * ctx, struct wmi_draft_status * out);
+WHISPER_API int wmi_draft_status_from_state(struct whisper_state * state, struct wmi_draft_status * out);
+WHISPER_API int wmi_capture_set_draft(struct wmi_capture * cap, int mode);
+/* Test hooks.
+ *   wmi_selftest_draft_plan   the plan of the rule with no device (works on a wmi_init_host_only context): the window at
+ *                             seek = offset_ms / 10 that ends at seek + (duration_ms > 0 ? duration_ms / 10 : 3000), a prompt of n_prompt
+ *                             tokens.  *n_rows = n + 1 logits rows (1: clipped to nothing), logit_rows [n + 1] their batch rows
+ *                             (n_prompt - 1 + j), steps [n + 1][16]: the DecStep words of every row (flags, space_id, eot, beg, n_vocab,
+ *                             ts_floor_end, ts_initial_start filled; the rest 0).  The arrays hold n_max rows.  Returns 0, -1 bad argument.
+ *   wmi_selftest_draft_rows   crafted logits [n_rows][n_vocab] through filter_stats + k_draft_pick per group of 8 + k_draft_finish on
+ *                             `device` (no context; host pointers): ban [n_vocab] bytes, steps [n_rows][16] DecStep words, targets
+ *                             [n_rows - 1]; out [n_rows][8] the records' words, *accepted.  Returns 0; -1 bad argument before the device
+ *                             is touched; -2 / -3 device errors.
+ *   wmi_selftest_draft_logits the next drafted call of the context's state also hands back the logits rows the verifier saw:
+ *                             buf [cap_rows][n_vocab] (rows beyond cap_rows are not copied); taken with the draft.  NULL: off. */
+WHISPER_API int wmi_selftest_draft_plan(struct whisper_context * ctx, struct whisper_full_params params, const whisper_token * prompt, int n_prompt,
+                                        const whisper_token * draft, int n_draft, int32_t * n_rows, int32_t * logit_rows, int32_t * steps);
+WHISPER_API int wmi_selftest_draft_rows(int device, int n_rows, int n_vocab, const float * logits, const uint8_t * ban, const int32_t * steps,
+                                        const int32_t * targets, int32_t * out, int32_t * accepted);
+WHISPER_API int wmi_selftest_draft_logits(struct whisper_context * ctx, float * buf, int cap_rows);
+
 /* Transcribe what an AudioStreamWAV holds: its `data` bytes as they are — 8 or 16 bit, mono or stereo, at the asset's own mix rate.
  *   replaces: the per-sample loop of AudioStreamToText.get_text (bin/addons/godot_whisper/audio_stream_to_text.gd:31-48), which turns
  *             the bytes into floats one `append` at a time and transcribes them as 16 kHz mono whatever the asset is (INTEGRATION.md,
