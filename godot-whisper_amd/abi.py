@@ -209,6 +209,10 @@ class wmi_wav(C.Structure):  # include/wmi_device.h: the data bytes of an AudioS
                 ("on_device", C.c_int)]
 
 
+class wmi_speaker(C.Structure):  # include/wmi_device.h: the channel energies of a time range of a stereo clip and the speaker they name (wmi_set_speaker)
+    _fields_ = [("speaker", C.c_int), ("reserved", C.c_int), ("is0", C.c_longlong), ("is1", C.c_longlong), ("e0", C.c_double), ("e1", C.c_double)]
+
+
 class wmi_grammar_status(C.Structure):  # include/wmi_device.h: the counters and capacities of the grammar's device route (wmi_set_grammar_device)
     _fields_ = [("steps_device", C.c_int32), ("rows_host", C.c_int32), ("cap_stacks", C.c_int32), ("cap_depth", C.c_int32),
                 ("cap_words", C.c_int32), ("reject_us", C.c_float)]
@@ -234,6 +238,7 @@ NO_SPEECH_OFF, NO_SPEECH_REPORT, NO_SPEECH_DROP, NO_SPEECH_GATE = range(4)      
 WINDOW_EMITTED, WINDOW_DROPPED, WINDOW_GATED = range(3)                          # wmi_window.outcome
 TOKEN_DTW_OFF, TOKEN_DTW_ON = range(2)                                           # wmi_set_token_dtw modes
 GRAMMAR_HOST, GRAMMAR_DEVICE = range(2)                                          # wmi_set_grammar_device modes
+SPEAKER_OFF, SPEAKER_SEGMENTS, SPEAKER_TOKENS = range(3)                         # wmi_set_speaker modes
 
 
 class whisper_model_loader(C.Structure):  # W/whisper.h:108-114

@@ -120,6 +120,7 @@ void whisper_free(struct whisper_context * ctx) {
     if (ctx->vad_res) (void) hipHostFree(ctx->vad_res);
     if (ctx->dsp_scratch) (void) hipFree(ctx->dsp_scratch);
     free_wav(*ctx);
+    free_speaker(*ctx);
     delete ctx;
 }
 
@@ -808,6 +809,7 @@ int wmi_batch_select(struct whisper_context * ctx, int chunk) {
     ctx->state->result_all = ctx->batch->results[chunk];
     if (chunk < (int) ctx->batch->windows.size()) ctx->state->windows = ctx->batch->windows[chunk]; else ctx->state->windows.clear();
     if (chunk < (int) ctx->batch->lang_id.size() && ctx->batch->lang_id[chunk] >= 0) ctx->state->lang_id = ctx->batch->lang_id[chunk];
+    speaker_select(*ctx, chunk);
     return (int) ctx->state->result_all.size();
 }
 

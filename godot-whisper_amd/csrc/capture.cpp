@@ -283,7 +283,13 @@ int wmi_capture_full(struct wmi_capture * c, struct whisper_full_params params) 
         if (n < 0) { c->draft_last.clear(); return n; }
         State * st = c->ctx->state.get();
         if (c->draft_mode == 1 && st && !c->draft_last.empty()) st->draft = c->draft_last;
+        // wmi_set_speaker: the channel energies of the accumulation as it lies in d_frames, one launch and one copy in front of the call's own
+        // work on its stream (full() waits for its results behind them)
+        const bool labels = n > 0 && st && speaker_begin(*c->ctx, 1);
+        if (labels && (!speaker_reserve(*c->ctx, 0, k::SRC_F32_STEREO, c->count, c->mix_rate) ||
+                       !speaker_queue(*c->ctx, 0, c->d_frames + 2 * c->off, st->dev.stream))) { c->draft_last.clear(); return -3; }
         const int ret = wmi_full_device_pcm(c->ctx, params, c->d_pcm, n, nullptr);
+        if (labels && ret == 0) speaker_commit(*c->ctx, 1, params.token_timestamps);
         c->draft_last.clear();                                          // (a failed call forgets them)
         if (c->draft_mode == 1 && ret == 0 && st)
             for (const Segment & seg : st->result_all) for (const whisper_token_data & t : seg.tokens) c->draft_last.push_back(t.id);

@@ -190,6 +190,13 @@ void resample_launch_kind(const ResamplePlan & pl, int kind, const void * d_src,
 // group of eight one per thread — or every frame so when no frame starts on such a boundary (a stereo source one sample off its frame grid).
 // d_src: sample-aligned; out: any f32 pointer.  false: bad kind / launch error.  n_frames = 0 launches nothing.
 bool wav_decode(int kind, const void * d_src, long long n_frames, float * out, hipStream_t st);
+// Channel energies per centisecond of a STEREO source (k_speaker.hip; speaker_ranges.h has the definition): one launch over n frames of
+// `kind` (SRC_F32_STEREO, SRC_S16_STEREO, SRC_S8_STEREO) at `rate` Hz writes nb = channel_bins_count(n, rate) pairs {left, right} of 8-byte
+// sums over frames [B(b), min(B(b + 1), n - 1)), B(b) = (b * rate) / 100, and behind them the two magnitudes of frame n - 1: (nb + 1) * 16
+// bytes at d_bins (8-byte aligned) — unsigned 64-bit sums of |v| for the integer kinds, doubles for f32.  d_src: sample-aligned.
+// n = 0 launches nothing.  false: bad kind / size / launch error.
+long long channel_bins_count(long long n, long long rate);
+bool channel_bins(int kind, const void * d_src, long long n, long long rate, void * d_bins, hipStream_t st);
 
 // ---------------------------------------------------------------- GEMM (k_gemm.hip)
 enum Epi : int {

@@ -45,6 +45,7 @@ void select_merged(whisper_context & ctx) {
     ctx.state->result_all = l.merged;
     ctx.state->windows = l.windows;
     if (l.lang_id >= 0) ctx.state->lang_id = l.lang_id;
+    speaker_select(ctx, -1);
 }
 
 int full_long(whisper_context * ctx, whisper_full_params params, const float * pcm, int n, bool on_device, const wmi_long_params & lp) {

@@ -33,6 +33,7 @@ struct WavJob {
     size_t bytes_off = 0, tab_off = 0;    // the clip's place in the byte buffer / the position tables (batch: one after the other)
     bool mark_begin = true, mark_end = true;   // record the events of wmi_wav_stats' timer around this job
     bool used = false;
+    int spk_slot = -1;                    // >= 0: the clip's table of channel energies (speaker.cpp) is queued behind its conversion
 };
 
 struct WavWork {
@@ -132,6 +133,18 @@ bool reserve_jobs(WavWork & w, WavJob * jobs, int n) {
     return reserve(w.d_bytes, w.bytes_cap, bytes, 4096) && reserve_tables(w, tab);
 }
 
+// the tables of a call that takes a speaker mode (wmi_set_speaker): one per stereo clip that is converted; false: out of memory
+bool reserve_speaker(whisper_context & ctx, WavJob * jobs, int n) {
+    if (!speaker_begin(ctx, n)) return true;
+    for (int i = 0; i < n; ++i) {
+        const WavPlan & p = jobs[i].plan;
+        const bool table = p.frames > 0 && p.n_out > 0 && jobs[i].wav->stereo == 1;
+        if (!speaker_reserve(ctx, i, p.kind, table ? p.frames : -1, jobs[i].wav->mix_rate)) return false;
+        if (table) jobs[i].spk_slot = i;
+    }
+    return true;
+}
+
 hipStream_t mel_stream_of(State & st) { return st.dev.mel_stream ? st.dev.mel_stream : st.dev.stream; }   // pcm_to_mel's choice
 
 }  // namespace
@@ -178,6 +191,7 @@ bool wav_job_run(whisper_context & ctx, WavJob & job, float * d_dst, hipStream_t
             HIP_TRY(hipGetLastError());
         }
         w->stats[3] += 1;
+        if (job.spk_slot >= 0 && !speaker_queue(ctx, job.spk_slot, src, s)) return false;       // the frames once more, where they lie
     }
     w->stats[1] += p.frames; w->stats[2] += p.n_out;
     if (job.mark_end) { HIP_TRY(hipEventRecord(w->ev[1], s)); w->ev_pending = true; }
@@ -243,12 +257,13 @@ int wmi_full_wav(struct whisper_context * ctx, struct whisper_full_params params
         if (!compute_ready(*ctx, __func__)) return -102;
         if (!HIP_OK(hipSetDevice(ctx->device))) return -102;
         WavWork * w = work(*ctx);
-        if (!w || !reserve_jobs(*w, &job, 1)) return -103;
+        if (!w || !reserve_jobs(*w, &job, 1) || !reserve_speaker(*ctx, &job, 1)) return -103;
         DeviceState & d = ctx->state->dev;
         struct Hook { DeviceState & d; ~Hook() { d.pcm_job = nullptr; } } hook{d};
         d.pcm_job = &job;                                                  // the one pcm_to_mel of full() runs the job instead of copying host samples
         const int r = full(*ctx, params, nullptr, nullptr, (int) job.plan.n_out);
         if (job.used) (void) hipStreamSynchronize(mel_stream_of(*ctx->state));   // full() has waited for its results; an early error return may not have
+        if (r == 0 && job.used && job.spk_slot >= 0) speaker_commit(*ctx, 1, params.token_timestamps);
         return r;
     } catch (...) { WMI_ERR("%s: out of memory\n", __func__); return -103; }
 }
@@ -266,12 +281,14 @@ int wmi_full_long_wav(struct whisper_context * ctx, struct whisper_full_params p
         if (!HIP_OK(hipSetDevice(ctx->device))) return -102;
         WavWork * w = work(*ctx);
         const size_t n = (size_t) job.plan.n_out;
-        if (!w || !reserve_jobs(*w, &job, 1) || !reserve(w->d_pcm, w->pcm_cap, std::max<size_t>(n, 1), 4096)) return -103;
+        if (!w || !reserve_jobs(*w, &job, 1) || !reserve(w->d_pcm, w->pcm_cap, std::max<size_t>(n, 1), 4096) || !reserve_speaker(*ctx, &job, 1)) return -103;
         hipStream_t s = mel_stream_of(*ctx->state);
         bool ok = wav_job_run(*ctx, job, w->d_pcm, s);
         ok = HIP_OK(hipStreamSynchronize(s)) && ok;                        // wmi_full_long takes device samples as ready, on whichever stream it reads them
         if (!ok) return -103;
-        return wmi_full_long(ctx, params, w->d_pcm, (int) n, 1, long_params);
+        const int r = wmi_full_long(ctx, params, w->d_pcm, (int) n, 1, long_params);
+        if (r == 0 && job.spk_slot >= 0) speaker_commit(*ctx, 3, params.token_timestamps);
+        return r;
     } catch (...) { WMI_ERR("%s: out of memory\n", __func__); return -103; }
 }
 
@@ -294,7 +311,8 @@ int wmi_full_batch_wav(struct whisper_context * ctx, struct whisper_full_params 
         if (!compute_ready(*ctx, __func__)) return -102;
         if (!HIP_OK(hipSetDevice(ctx->device))) return -102;
         WavWork * w = work(*ctx);
-        if (!w || !reserve_jobs(*w, jobs.data(), n) || !reserve(w->d_pcm, w->pcm_cap, std::max<size_t>(total, 1), 4096)) return -103;
+        if (!w || !reserve_jobs(*w, jobs.data(), n) || !reserve(w->d_pcm, w->pcm_cap, std::max<size_t>(total, 1), 4096) ||
+            !reserve_speaker(*ctx, jobs.data(), n)) return -103;
         hipStream_t s = mel_stream_of(*ctx->state);
         bool ok = true;
         for (int i = 0; i < n && ok; ++i) ok = wav_job_run(*ctx, jobs[i], w->d_pcm + off[i], s);      // every conversion is queued ...
@@ -302,7 +320,9 @@ int wmi_full_batch_wav(struct whisper_context * ctx, struct whisper_full_params 
         if (!ok) return -103;
         std::vector<const float *> pcm((size_t) n); std::vector<int> ns((size_t) n);
         for (int i = 0; i < n; ++i) { pcm[i] = w->d_pcm + off[i]; ns[i] = (int) jobs[i].plan.n_out; }
-        return wmi_full_batch(ctx, params, pcm.data(), ns.data(), n, 1);
+        const int r = wmi_full_batch(ctx, params, pcm.data(), ns.data(), n, 1);
+        if (r == 0) speaker_commit(*ctx, 2, params.token_timestamps);
+        return r;
     } catch (...) { WMI_ERR("%s: out of memory\n", __func__); return -103; }
 }
 

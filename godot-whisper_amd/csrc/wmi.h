@@ -436,6 +436,22 @@ struct WavJob;
 // queue the job's upload, position table and its one conversion launch on `s`; the mono 16 kHz samples land at d_dst (room for the job's count)
 bool wav_job_run(whisper_context & ctx, WavJob & job, float * d_dst, hipStream_t s);
 void free_wav(whisper_context & ctx);
+// Speaker labels from the two channels (speaker.cpp; wmi_set_speaker): the context's tables of channel energies, one per stereo clip of the
+// last wmi_full_wav / wmi_full_long_wav / wmi_full_batch_wav / wmi_capture_full call made with a mode.
+//   speaker_begin      a call with `n_clips` clips starts: the mode and ratio in effect are taken (false: mode 0, nothing is touched)
+//   speaker_reserve    room for clip `slot`'s table (device + pinned host); a mono clip (or n_frames < 0) gets none.  false: out of memory
+//   speaker_queue      k::channel_bins over the clip's frames and the table's copy to the host, on `s`: no wait
+//   speaker_commit     the call returned 0: its result carries the tables (family 1 one clip, 2 per chunk of wmi_batch_select, 3 wmi_full_long)
+//   speaker_invalidate every transcription call starts with it (full(), full_batch()): the result to come carries none until committed
+//   speaker_select     wmi_batch_select / the merged view of wmi_long_select: which clip's table and which time shift the accessors use
+struct SpeakerWork;
+bool speaker_begin(whisper_context & ctx, int n_clips);
+bool speaker_reserve(whisper_context & ctx, int slot, int kind, long long n_frames, int rate);
+bool speaker_queue(whisper_context & ctx, int slot, const void * d_src, hipStream_t s);
+void speaker_commit(whisper_context & ctx, int family, bool token_times);
+void speaker_invalidate(whisper_context & ctx);
+void speaker_select(whisper_context & ctx, int chunk);
+void free_speaker(whisper_context & ctx);
 }
 
 struct whisper_context {
@@ -461,6 +477,9 @@ struct whisper_context {
     float * vad_res = nullptr;          // pinned host memory the VAD kernel writes {decision, energy_all, energy_last} into (wmi_vad)
     float * dsp_scratch = nullptr; size_t dsp_scratch_bytes = 0;   // grow-only device staging of the host-pointer forms of wmi_vad / wmi_downmix_stereo / wmi_resample
     wmi::WavWork * wav = nullptr;       // wmi_wav_* / wmi_full_*_wav (wav.cpp): made by the first such call, null in a context that never makes one
+    // wmi_set_speaker: 0 off, 1 a label per segment, 2 per token too; read at the start of every transcription call that serves it (speaker.cpp)
+    int            speaker_mode = 0; double speaker_ratio = 1.1;
+    wmi::SpeakerWork * spk = nullptr;   // made by the first call with a mode (or wmi_wav_speaker), null in a context that never makes one
     // guards what belongs to the CONTEXT: the lock-step work set (wmi_full_batch), the DSP scratch, state creation, the probes.  Compute
     // on a state takes the state's own lock (wmi::State::mu), not this one.
     std::recursive_mutex mu;

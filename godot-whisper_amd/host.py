@@ -38,7 +38,7 @@ class SpeechToText:
     """One `whisper_context` per node (src/speech_to_text.h:135); not re-entrant."""
 
     def __init__(self, lib: C.CDLL, settings: dict | None = None, no_speech: int = 0, token_dtw=False, grammar=None,
-                 grammar_penalty: float = 100.0, grammar_device: bool = False):
+                 grammar_penalty: float = 100.0, grammar_device: bool = False, speaker_labels=False, speaker_ratio: float = 1.1):
         """grammar: rules in the format of abi.make_grammar (a list of rules, each a list of (type, value) without the closing END; rule 0
         is the start rule) — every full_params() then carries them with grammar_penalty; None: no grammar.
         grammar_device (product library only, include/wmi_device.h wmi_set_grammar_device): True — the grammar's reject masks and the
@@ -47,12 +47,19 @@ class SpeechToText:
         heads — or a list of (layer, head) pairs; every token dictionary then gains "t_dtw" (10 ms units, -1 for a token that is no text).
         "t0" / "t1" stay the reference's.
         no_speech (product library only, include/wmi_device.h wmi_set_no_speech): 0 off — the reference's behaviour —, 1 report the
-        windows' no-speech probability, 2 drop (OpenAI's rule), 3 gate.  The windows of a call are in last_windows after collect()."""
+        windows' no-speech probability, 2 drop (OpenAI's rule), 3 gate.  The windows of a call are in last_windows after collect().
+        speaker_labels (product library only, include/wmi_device.h wmi_set_speaker): True — the stereo clips of transcribe_wav*, and a
+        capture session's steps, leave a dictionary per segment in last_speakers (t0, t1, text, "speaker" 0 / 1 / None, "channel_energy"
+        (left, right)); "tokens" — with params.token_timestamps every token dictionary gains "speaker" as well.  speaker_ratio: how much
+        louder a channel must be (whisper.cpp --diarize: 1.1)."""
         self.lib = lib
         self.ctx = None
         self.no_speech = int(no_speech)
         self.token_dtw = token_dtw
         self.grammar_device = bool(grammar_device)
+        self.speaker_labels, self.speaker_ratio = speaker_labels, float(speaker_ratio)
+        self.last_speakers = []
+        self._speaker_called = False
         self.grammar_penalty = float(grammar_penalty)
         self._grammar = None
         self.set_grammar(grammar, grammar_penalty)
@@ -77,6 +84,32 @@ class SpeechToText:
         self.set_no_speech(self.no_speech)
         self.set_token_dtw(self.token_dtw)
         self.set_grammar_device(self.grammar_device)
+        self.set_speaker_labels(self.speaker_labels, self.speaker_ratio)
+
+    def set_speaker_labels(self, labels, ratio: float = 1.1) -> int:
+        """The context's speaker mode from the next transcription call on (False, True or "tokens"); returns the previous mode (0
+        without a context)."""
+        self.speaker_labels, self.speaker_ratio = labels, float(ratio)
+        if not self.ctx or not (labels or self._speaker_called):          # (a node that never asks for labels never makes the call)
+            return 0
+        self._speaker_called = True
+        mode = abi.SPEAKER_TOKENS if labels == "tokens" else abi.SPEAKER_SEGMENTS if labels else abi.SPEAKER_OFF
+        return self.lib.wmi_set_speaker(self.ctx, mode, self.speaker_ratio)
+
+    def speakers(self) -> list:
+        """A dictionary per segment the accessors show now: t0, t1, text, "speaker" (0, 1, None for the reference's "?") and
+        "channel_energy" (left, right), "samples" (is0, is1).  Empty where the result carries no table (wmi_full_get_segment_speaker -2)."""
+        lib, ctx, out = self.lib, self.ctx, []
+        if not ctx or not self.speaker_labels:
+            return out
+        rec = abi.wmi_speaker()
+        for i in range(lib.whisper_full_n_segments(ctx)):
+            if lib.wmi_full_get_segment_speaker(ctx, i, C.byref(rec)) != 0:
+                return []
+            out.append({"t0": lib.whisper_full_get_segment_t0(ctx, i), "t1": lib.whisper_full_get_segment_t1(ctx, i),
+                        "text": lib.whisper_full_get_segment_text(ctx, i), "speaker": rec.speaker if rec.speaker >= 0 else None,
+                        "channel_energy": (rec.e0, rec.e1), "samples": (rec.is0, rec.is1)})
+        return out
 
     def set_grammar(self, rules, penalty: float = 100.0):
         """The grammar of every later full_params() (None: none).  The element arrays stay referenced by this node."""
@@ -222,8 +255,13 @@ class SpeechToText:
                 })
                 if self.token_dtw:
                     out[-1]["t_dtw"] = lib.wmi_full_get_token_dtw(ctx, i, j)
+                if self.speaker_labels == "tokens":
+                    rec = abi.wmi_speaker()
+                    if lib.wmi_full_get_token_speaker(ctx, i, j, C.byref(rec)) == 0:
+                        out[-1]["speaker"] = rec.speaker if rec.speaker >= 0 else None
         out.insert(0, full_text)
         self.last_windows = self.windows()
+        self.last_speakers = self.speakers()
         return out
 
     def windows(self) -> list:
@@ -274,12 +312,14 @@ class SpeechToText:
         self.last_batch_windows = []
         self.last_modes = []
         self.last_langs = []                                          # per chunk: the language id whisper_full would report (detected with "auto")
+        self.last_batch_speakers = []                                 # per chunk: speakers() ([] for a mono clip)
         for c in range(n):
             assert self.lib.wmi_batch_select(self.ctx, c) >= 0
             self.last_modes.append(self.lib.wmi_batch_chunk_mode(self.ctx, c))
             self.last_langs.append(self.lib.wmi_batch_lang_id(self.ctx, c))
             out.append(self.collect())
             self.last_batch_windows.append(self.last_windows)
+            self.last_batch_speakers.append(self.last_speakers)
         return out
 
     # -- a whole recording (product library only: include/wmi_device.h wmi_full_long): cut at its silences on the device, the pieces
@@ -523,15 +563,20 @@ class AudioStreamToText(SpeechToText):
         return remove_special_characters(text)
 
     def get_text_wav(self, data: bytes, format: int, stereo, mix_rate: int, initial_prompt: str = "", interpolator_type: int = 2,
-                     long_form: bool = False) -> str:
+                     long_form: bool = False, speaker_prefix: bool = False) -> str:
         """get_text on audio_stream.data / .format / .stereo / .mix_rate themselves: every sample is decoded, a stereo asset is folded
-        and another rate resampled on the device — what the node's own loop (audio_stream_to_text.gd:40-46) gets wrong."""
+        and another rate resampled on the device — what the node's own loop (audio_stream_to_text.gd:40-46) gets wrong.
+        speaker_prefix (a node made with speaker_labels, a stereo asset): "(speaker 0) " / "(speaker 1) " / "(speaker ?) " in front of
+        every segment's text, as whisper.cpp's --diarize prints it (examples/main/main.cpp:262-265)."""
         if long_form:
             tokens = self.transcribe_wav_long(data, format, stereo, mix_rate, interpolator_type, self.full_params(initial_prompt, 0))
         else:
             tokens = self.transcribe_wav(data, format, stereo, mix_rate, initial_prompt, 0, interpolator_type)
         if not tokens:
             return ""
+        if speaker_prefix and self.last_speakers:
+            return "".join("(speaker %s) " % ("?" if s["speaker"] is None else s["speaker"]) +
+                           remove_special_characters(s["text"].decode("utf-8", errors="replace")) for s in self.last_speakers)
         return remove_special_characters(tokens.pop(0).decode("utf-8", errors="replace"))
 
 
@@ -557,12 +602,14 @@ class CaptureStreamToText(SpeechToText):
 
     def __init__(self, lib, settings=None, transcribe_interval: float = 0.3, minimum_sentence_ms: int = 3000,
                  maximum_sentence_ms: int = 15000, punctuation_characters: str = ".!?;。；？！", no_speech_gate: bool = False,
-                 draft_reuse: bool = False):
+                 draft_reuse: bool = False, speaker_labels=False):
         """no_speech_gate: transcribe in the no-speech mode "gate" (wmi_set_no_speech 3).  A step whose window was gated is treated like
         "no activity": nothing is emitted for it and the loop goes on.
         draft_reuse (stream_capture on a session; wmi_capture_set_draft 1): every step offers the previous step's tokens as a draft —
-        the messages are the same, the steps shorter; draft_statuses collects every step's wmi_draft_status."""
-        super().__init__(lib, settings, no_speech=abi.NO_SPEECH_GATE if no_speech_gate else 0)
+        the messages are the same, the steps shorter; draft_statuses collects every step's wmi_draft_status.
+        speaker_labels (stream_capture on a session; wmi_set_speaker): every step's collect() leaves last_speakers, from the session's
+        resident stereo frames."""
+        super().__init__(lib, settings, no_speech=abi.NO_SPEECH_GATE if no_speech_gate else 0, speaker_labels=speaker_labels)
         self.no_speech_gate = bool(no_speech_gate)
         self.draft_reuse = bool(draft_reuse)
         self.draft_statuses = []

@@ -123,8 +123,18 @@ int main(int argc, char ** argv) {
         int stereo = 0, mix_rate = 16000, interp = SpeechToText::SRC_SINC_FASTEST;
         sscanf(prompt.c_str(), "%d,%d,%d", &stereo, &mix_rate, &interp);
         node.set_language(SpeechToText::English);
+        const bool diarize = argc > 7 && std::string(argv[7]) == "--diarize";       // speaker labels from the two channels of a stereo asset
+        if (diarize) node.set_speaker_labels(1);
         printf("{\"transcription\": ");
         json_transcription(node.transcribe_wav(raw, language, stereo != 0, mix_rate, "", audio_ctx, (SpeechToText::InterpolatorType) interp));
+        if (diarize) {
+            printf(", \"speakers\": [");
+            const auto sp = node.speakers();
+            for (size_t i = 0; i < sp.size(); ++i)
+                printf("%s{\"t0\": %lld, \"t1\": %lld, \"speaker\": %d, \"e0\": %.17g, \"e1\": %.17g}", i ? ", " : "", (long long) sp[i].t0, (long long) sp[i].t1,
+                       sp[i].speaker, sp[i].e0, sp[i].e1);
+            printf("], \"diarized\": "); json_string(node.diarized_text());
+        }
         printf(", \"ret\": %d}\n", node.last_return);
         return 0;
     }

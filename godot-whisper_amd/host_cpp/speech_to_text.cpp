@@ -31,6 +31,37 @@ void SpeechToText::set_language_model(const uint8_t * data, size_t size) {   // 
     if (context_instance && no_speech != 0) (void) wmi_set_no_speech(context_instance, no_speech);
     if (context_instance && token_dtw) (void) wmi_set_token_dtw(context_instance, 1, token_dtw_pairs.data(), (int) token_dtw_pairs.size() / 2);
     if (context_instance && grammar_device) (void) wmi_set_grammar_device(context_instance, 1);
+    if (context_instance && speaker_mode) (void) wmi_set_speaker(context_instance, speaker_mode, speaker_ratio);
+}
+
+int SpeechToText::set_speaker_labels(int mode, double ratio) {
+    const int prev = speaker_mode;
+    speaker_mode = mode < 0 ? 0 : (mode > 2 ? 2 : mode); speaker_ratio = ratio;
+    if (context_instance) (void) wmi_set_speaker(context_instance, speaker_mode, speaker_ratio);
+    return prev;
+}
+
+std::vector<SegmentSpeaker> SpeechToText::speakers() const {
+    std::vector<SegmentSpeaker> out;
+    if (!context_instance || !speaker_mode) return out;
+    const int n_segments = whisper_full_n_segments(context_instance);
+    for (int i = 0; i < n_segments; ++i) {
+        struct wmi_speaker rec;
+        if (wmi_full_get_segment_speaker(context_instance, i, &rec) != 0) return std::vector<SegmentSpeaker>();
+        SegmentSpeaker s;
+        s.t0 = whisper_full_get_segment_t0(context_instance, i); s.t1 = whisper_full_get_segment_t1(context_instance, i);
+        s.text = whisper_full_get_segment_text(context_instance, i);
+        s.speaker = rec.speaker; s.e0 = rec.e0; s.e1 = rec.e1;
+        out.push_back(std::move(s));
+    }
+    return out;
+}
+
+std::string SpeechToText::diarized_text() const {                    // examples/main/main.cpp:262-265 in front of every segment
+    std::string out;
+    for (const SegmentSpeaker & s : speakers())
+        out += std::string("(speaker ") + (s.speaker < 0 ? "?" : s.speaker == 0 ? "0" : "1") + ") " + s.text;
+    return out;
 }
 
 void SpeechToText::set_grammar(const std::vector<std::vector<whisper_grammar_element>> & rules, float penalty) {

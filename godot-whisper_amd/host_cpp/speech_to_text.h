@@ -36,6 +36,14 @@ struct Token {
     float   no_speech_prob = -1.0f;   // not in the reference: of the token's segment (wmi_full_get_segment_no_speech_prob; -1 with set_no_speech(0))
     int64_t t_dtw = -1;               // not in the reference: the token's DTW time in 10 ms units (wmi_full_get_token_dtw; -1 without set_token_dtw, or for a token that is no text)
 };
+// not in the reference node: one segment's speaker from the two channels of a stereo asset (include/wmi_device.h wmi_speaker; whisper.cpp's
+// --diarize, examples/main/main.cpp:237-268).  speaker: 0 left, 1 right, -1 the reference's "?"
+struct SegmentSpeaker {
+    int64_t t0 = 0, t1 = 0;
+    std::string text;
+    int speaker = -1;
+    double e0 = 0.0, e1 = 0.0;
+};
 // the Array itself: element 0 is the full text, the rest are the token dictionaries (:447)
 struct Transcription {
     bool ok = false;              // false <=> the reference returns an empty Array
@@ -65,6 +73,12 @@ public:
     // given {layer, head, layer, head, ..} list; kept across set_language_model.  Returns what wmi_set_token_dtw does (0 without a context).
     int  set_token_dtw(bool on, const std::vector<int32_t> & layer_head = {});
     bool get_token_dtw() const { return token_dtw; }
+    // not in the reference: speaker labels for the stereo assets of transcribe_wav (include/wmi_device.h wmi_set_speaker: 0 off, 1 per
+    // segment, 2 per token too); kept across set_language_model.  Returns the previous mode.  speakers(): a record per segment of the last
+    // result, empty where it carries none (mode 0, a mono asset, another call); diarized_text(): main.cpp's "(speaker 0) text" lines joined.
+    int  set_speaker_labels(int mode, double ratio = 1.1);
+    std::vector<SegmentSpeaker> speakers() const;
+    std::string diarized_text() const;
     // not in the reference: a grammar for every later transcription (whisper_full_params.grammar_rules: rule 0 is the start rule, each rule
     // without its closing END element; an empty list: none), and where it is evaluated (include/wmi_device.h wmi_set_grammar_device:
     // true — reject masks and penalised sampling on the device); both kept across set_language_model.  set_grammar_device returns the
@@ -123,6 +137,7 @@ protected:
     int language = English;
     int no_speech = 0;
     bool token_dtw = false; std::vector<int32_t> token_dtw_pairs;
+    int speaker_mode = 0; double speaker_ratio = 1.1;
     bool grammar_device = false; float grammar_penalty = 100.0f;
     std::vector<std::vector<whisper_grammar_element>> grammar_rules;     // each closed by an END element
     std::vector<const whisper_grammar_element *> grammar_ptrs;

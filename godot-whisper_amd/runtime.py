@@ -172,6 +172,15 @@ DEVICE_API = [
     ("wmi_full_batch_wav", C.c_int, [C.c_void_p, abi.whisper_full_params, C.POINTER(abi.wmi_wav), C.c_int, C.c_int]),
     ("wmi_selftest_wav_plan", C.c_int, [C.POINTER(abi.wmi_wav), C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     ("wmi_wav_stats", C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    ("wmi_set_speaker", C.c_int, [C.c_void_p, C.c_int, C.c_double]),
+    ("wmi_full_get_segment_speaker", C.c_int, [C.c_void_p, C.c_int, C.POINTER(abi.wmi_speaker)]),
+    ("wmi_full_get_token_speaker", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(abi.wmi_speaker)]),
+    ("wmi_wav_speaker", C.c_int, [C.c_void_p, C.POINTER(abi.wmi_wav), C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.POINTER(abi.wmi_speaker)]),
+    ("wmi_speaker_stats", C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    ("wmi_selftest_channel_bins", C.c_int, [C.c_int, C.POINTER(abi.wmi_wav), C.c_void_p, C.c_longlong, C.POINTER(C.c_longlong), C.c_void_p]),
+    ("wmi_bench_channel_bins", C.c_int, [C.c_int, C.POINTER(abi.wmi_wav), C.c_int, C.POINTER(C.c_float)]),
+    ("wmi_selftest_speaker_ranges", C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_longlong, C.c_int, C.c_double, C.c_void_p,
+                                              C.c_void_p, C.c_int, C.POINTER(abi.wmi_speaker)]),
 ]
 
 _lib = None

@@ -921,6 +921,60 @@ WHISPER_API int wmi_full_batch_wav(struct whisper_context * ctx, struct whisper_
 WHISPER_API int wmi_selftest_wav_plan(const struct wmi_wav * wav, int converter, long long * frames, long long * n_out);
 WHISPER_API int wmi_wav_stats(struct whisper_context * ctx, int64_t * out5);
 
+/* Stereo clips: a speaker per segment and token from the channel energies (one voice per channel: two local microphones, a dialogue
+ * recorded left and right).
+ *   replaces: whisper.cpp's --diarize (examples/main/main.cpp:41-43 timestamp_to_sample, :237-268 estimate_diarization_speaker; the same in
+ *             examples/server/server.cpp): per segment a host loop over an f32 copy of both channels — a copy the WAV calls never make.
+ * The definition (tests/speaker_ref.py), for a stereo clip of n frames at `rate` Hz (frames as the WAV calls count them) and times in
+ * centiseconds:
+ *   is(t)    = max(0, min(n - 1, (t * rate) / 100)), 64-bit, truncating: the reference's clamp, at the asset's own rate, on the asset's own
+ *              frames (before any fold, before any resampling).  The clamp makes a range that reaches the end exclude the last frame.
+ *   e_c      = the sum of |x_c| over frames [is(t0), is(t1)), c = 0 left, 1 right, in double; s16 as v / 32768, s8 as v / 128
+ *   speaker  = 0 if e0 > ratio * e1, else 1 if e1 > ratio * e0, else -1 (the reference's "?"); an empty range or clip: -1, energies 0
+ * For s16 and s8 clips e0 / e1 equal the reference's sequential double loop bit for bit (ties included); for f32 clips they are within
+ * 2 (is1 - is0) 2^-53 of it, relatively, in an order that is the same from run to run.
+ * On the device this is ONE launch per stereo clip (csrc/k_speaker.hip): the packed frames are read where they lie (the uploaded bytes, a
+ * device-resident clip, a capture session's frames) into a table of channel sums per centisecond, which one copy brings to pinned host
+ * memory — queued behind the conversion, complete at a wait the call makes anyway; no wait is added.  Segment and token records are
+ * formed from the table when they are asked for; no sample is read on the host.
+ *   wmi_set_speaker   the context's mode, read at the START of wmi_full_wav / wmi_full_long_wav / wmi_full_batch_wav / wmi_capture_full:
+ *                     0 (default) nothing is allocated, launched or stored and every result is byte for byte what it is without this
+ *                     interface; 1 every segment of the result has a record over its [t0, t1); 2 every token too, over its own t0 / t1
+ *                     (with params.token_timestamps; without it the token accessor answers -2).  ratio <= 0 (or NaN) selects 1.1.
+ *                     Returns the previous mode, -2 for a NULL context, -1 for a mode outside 0 - 2.  Modes 1 and 2 change no token,
+ *                     segment, time or counter of a result; the no-speech, token-DTW, grammar and draft modes pass through unchanged.
+ *   wmi_full_get_segment_speaker / wmi_full_get_token_speaker   of the selected result: they follow wmi_batch_select (a table per stereo
+ *                     clip) and wmi_long_select (the merged view's times are absolute; a selected piece shows the same records for its
+ *                     segments, its piece-relative times shifted back).  0 ok; -1 a bad index or NULL; -2 the result carries no table:
+ *                     mode 0, a mono clip, token records outside mode 2, or the result of any other call family (whisper_full*,
+ *                     wmi_full_device_pcm, wmi_full_batch*, wmi_full_long on caller-made mono, wmi_pool_full, whisper_full_parallel,
+ *                     wmi_capture_full_batch: out of scope — there is no stereo source, or no table per lane yet).  Every transcription
+ *                     call on the context drops the tables of the one before it.
+ *   wmi_wav_speaker   ranges of the caller's own (words built from wmi_full_get_token_dtw, say), no transcription: uploads, launches,
+ *                     copies, waits once, and fills out[n].  Its argument errors are the WAV conversion errors, decided before the device
+ *                     is touched (-1 also for n < 0 or NULL t0 / t1 / out with n > 0); -12 a mono clip; -2 / -3 as there.  Any positive rate.
+ *   wmi_speaker_stats out4 = { tables made by the last call that took a mode, bins, bytes copied device -> host, kernel launches }
+ *   wmi_selftest_channel_bins   the kernel alone on `device`: bins [cap_bins][2] and last2 [2] of 8 bytes each (uint64 sums of |v| for the
+ *                     integer formats, doubles for WMI_WAV_F32); bin b covers frames [B(b), min(B(b + 1), n - 1)), B(b) = (b * rate) / 100,
+ *                     *n_bins = the smallest b with B(b) >= n; last2 = the magnitudes of frame n - 1, which no range counts.  What lies
+ *                     behind the n_bins pairs in `bins` is left as it was.  -4: cap_bins below the count (n_bins is still written); -5: the
+ *                     launch wrote into the guard the hook keeps behind the device table.
+ *   wmi_bench_channel_bins   the launch alone, `iters` times on a stream of its own, each between two device events: ms[iters]
+ *   wmi_selftest_speaker_ranges   host only: csrc/speaker_ranges.h on a caller-made table.  kind = the format (WMI_WAV_*).  last2 is
+ *                     not read (see above).  Returns 0, -1 for a bad argument. */
+struct wmi_speaker { int speaker; int reserved; long long is0, is1; double e0, e1; };   /* speaker: 0, 1, -1 undecided */
+WHISPER_API int wmi_set_speaker(struct whisper_context * ctx, int mode, double ratio);
+WHISPER_API int wmi_full_get_segment_speaker(struct whisper_context * ctx, int i_segment, struct wmi_speaker * out);
+WHISPER_API int wmi_full_get_token_speaker(struct whisper_context * ctx, int i_segment, int i_token, struct wmi_speaker * out);
+WHISPER_API int wmi_wav_speaker(struct whisper_context * ctx, const struct wmi_wav * wav, const int64_t * t0, const int64_t * t1, int n,
+                                double ratio, struct wmi_speaker * out);
+WHISPER_API int wmi_speaker_stats(struct whisper_context * ctx, int64_t * out4);
+WHISPER_API int wmi_selftest_channel_bins(int device, const struct wmi_wav * wav, void * bins, long long cap_bins, long long * n_bins,
+                                          void * last2);
+WHISPER_API int wmi_bench_channel_bins(int device, const struct wmi_wav * wav, int iters, float * ms);
+WHISPER_API int wmi_selftest_speaker_ranges(const void * bins, long long n_bins, const void * last2, int kind, long long n_frames, int rate,
+                                            double ratio, const int64_t * t0, const int64_t * t1, int n_ranges, struct wmi_speaker * out);
+
 /* Host worker pool self-test (no device needed): `reps` jobs of `n_tasks` tasks; returns reps * n_tasks * (n_tasks + 1) / 2
  * when every task of every job ran exactly once. */
 WHISPER_API int64_t wmi_selftest_pool(int n_tasks, int reps);
