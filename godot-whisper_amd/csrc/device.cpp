@@ -156,8 +156,10 @@ static bool init_state_into(whisper_context & ctx, State * st, bool replica_stat
         unsigned char * hand = nullptr;
         // (+ 2 S granules behind the words for the one-launch front of a layer, k::front: 3 S / 2 of q|k|v, S / 2 of the attention row)
         // (+ 40 KB behind those for the one-launch back of the cross-attention, k::xback: 8 heads x 8 slices x 66 granules of partials, S / 2 of the row)
-        ok = ok && dalloc(hand, (size_t) 32 * S + 64 + 40960);
-        if (ok) { d.mlp_hand = hand; d.mlp_arrive = (unsigned long long *) (hand + (size_t) 16 * S); k::fill_zero(hand, (size_t) 32 * S + 64 + 40960, d.stream); }
+        // (+ S granules behind those for the residual row between the two roles of the joined launch, k::attn_join)
+        const size_t hand_bytes = (size_t) 32 * S + 64 + 40960 + (size_t) 8 * S;
+        ok = ok && dalloc(hand, hand_bytes);
+        if (ok) { d.mlp_hand = hand; d.mlp_arrive = (unsigned long long *) (hand + (size_t) 16 * S); k::fill_zero(hand, hand_bytes, d.stream); }
     }
     if (!ok) { WMI_ERR("%s: device allocation failed\n", __func__); return false; }
     // buffers that are read before being fully written must hold finite values
@@ -1238,7 +1240,7 @@ struct StepTicket {
 };
 }
 
-// which launches enqueue_greedy_step takes for the f16 step (STEP_FORM_PAIRED / _FRONTED / _BACKED; wmi.h)
+// which launches enqueue_greedy_step takes for the f16 step (STEP_FORM_PAIRED / _FRONTED / _BACKED / _JOINED; wmi.h)
 static unsigned greedy_step_forms(whisper_context & ctx, int Tc, bool long_kv, bool chained, bool solo) {
     const DeviceState & d = ctx.state->dev; const HParams & hp = ctx.model.hp;
     const int S = hp.n_text_state, H = hp.n_text_head, Lt = hp.n_text_layer;
@@ -1251,10 +1253,12 @@ static unsigned greedy_step_forms(whisper_context & ctx, int Tc, bool long_kv, b
     // pair's word, so it runs where that pair does (the pick kernel reports the word, a fault re-runs the step without either)
     const bool fronted = paired && (M & 2) && (M & 4) && !kn.no_front && k::front_usable(S, 1, long_kv ? hp.n_text_ctx : 0);
     const bool backed = paired && (M & 8) && (M & 16) && !kn.no_xback && k::xback_usable(S, H, Tc);
-    return (paired ? STEP_FORM_PAIRED : 0u) | (fronted ? STEP_FORM_FRONTED : 0u) | (backed ? STEP_FORM_BACKED : 0u);
+    // the two as one launch (k::attn_join): the short-cache front only (the long-cache form keeps its launch), and the joined grid resident
+    const bool joined = fronted && backed && !long_kv && !kn.no_join && k::attn_join_usable(S, H, Tc);
+    return (paired ? STEP_FORM_PAIRED : 0u) | (fronted ? STEP_FORM_FRONTED : 0u) | (backed ? STEP_FORM_BACKED : 0u) | (joined ? STEP_FORM_JOINED : 0u);
 }
 
-constexpr int PAIR_FAULT_WORD = 4;           // d.mlp_arrive as 32-bit words: [0], [1] the MLP launches' tags, [2], [3] the front launches', [6], [7] the cross-attention back's, [4] the hand-offs' status (k::MlpPairArgs::fault)
+constexpr int PAIR_FAULT_WORD = 4;           // d.mlp_arrive as 32-bit words: [0], [1] the MLP launches' tags, [2], [3] the front launches', [6], [7] the cross-attention back's, [8], [9] the joined launch's hop, [4] the hand-offs' status (k::MlpPairArgs::fault)
 static void enqueue_greedy_step(whisper_context & ctx, int Tc, bool long_kv = false, bool chained = false, bool solo = true) {
     if (ctx.model.quantised) { enqueue_greedy_step_q(ctx, Tc); return; }
     State & st = *ctx.state; DeviceState & d = st.dev; const Weights & w = ctx.w; const HParams & hp = ctx.model.hp;
@@ -1283,18 +1287,19 @@ static void enqueue_greedy_step(whisper_context & ctx, int Tc, bool long_kv = fa
     };
     const k::Knobs & kn = k::knobs();
     const unsigned forms = greedy_step_forms(ctx, Tc, long_kv, chained, solo);
-    const bool paired = forms & STEP_FORM_PAIRED, fronted = forms & STEP_FORM_FRONTED, backed = forms & STEP_FORM_BACKED;
+    const bool paired = forms & STEP_FORM_PAIRED, fronted = forms & STEP_FORM_FRONTED, backed = forms & STEP_FORM_BACKED, joined = forms & STEP_FORM_JOINED;
     for (int il = 0; il < Lt; ++il) {
         const DecLayerW & l = w.dec[il];
         __half * ck = kv.k + ((size_t) il * n_ctx) * S, * cv = kv.v + ((size_t) il * n_ctx) * S;
+        k::JoinArgs jn{};
         if (fronted) {     // LN + q|k|v, the self-attention (once per head) and the out projection as ONE launch with two hand-offs (k::front)
-            k::FrontArgs f{};
+            k::FrontArgs & f = jn.f;
             f.x = d.dx; f.xout = d.dx; f.ln_g = l.ln1_g; f.ln_b = l.ln1_b; f.eps = hp.eps; f.S = S; f.Wqkv = l.w_qkv; f.bqkv = l.b_qkv; f.scale = kq_scale;
             f.q16 = d.dq; f.ck = ck; f.cv = cv; f.kv_head = &stp->kv_head; f.n_kv = &stp->n_kv; f.cap = hp.n_text_ctx; f.Wo = l.w_o; f.bo = l.b_o;
             f.gq = (unsigned long long *) ((unsigned char *) d.mlp_hand + (size_t) 16 * S + 64); f.ga = f.gq + 3 * S / 2;
             f.epoch = (uint32_t *) d.mlp_arrive + 2; f.par = il & 1; f.fault = (uint32_t *) d.mlp_arrive + PAIR_FAULT_WORD;
             f.spin_cap = kn.pair_spin_cap; f.withhold = kn.front_withhold;
-            k::front(f, s, long_kv); chk("front", il);
+            if (!joined) { k::front(f, s, long_kv); chk("front", il); }      // (joined: launched with the cross-attention back below)
         } else {
         if (M & 2) gv(k::EPI_QKV_DEC, l.ln1_g, l.ln1_b, nullptr, S, 3 * S, l.w_qkv, l.b_qkv, d.dq, S, nullptr, ck, cv, kq_scale, &stp->kv_head); chk("qkv", il);
         if ((M & 4) && long_kv) {
@@ -1313,13 +1318,18 @@ static void enqueue_greedy_step(whisper_context & ctx, int Tc, bool long_kv = fa
             const float * po = nullptr, * pl = nullptr, * pm = nullptr; int ns = 0;
             if (!(M & 8)) { k::attn_cross_partials_layout(1, H, Tc, d.xattn, &po, &pl, &pm, &ns); }
             else if (backed) {   // LN + cross query + key slices, the combine (once per head) and the out projection as ONE launch (k::xback)
-                k::XbackArgs xb{};
+                k::XbackArgs & xb = jn.x;
                 xb.x = d.dx; xb.xout = d.dx; xb.ln_g = l.ln2_g; xb.ln_b = l.ln2_b; xb.eps = hp.eps; xb.S = S; xb.wq = l.w_cq; xb.bq = l.b_cq; xb.qscale = kq_scale;
                 xb.kc = d.kvc_k + (size_t) il * Tc * S; xb.vc = d.kvc_v + (size_t) il * Tc * S; xb.T = Tc; xb.Wo = l.w_co; xb.bo = l.b_co;
                 xb.gp = (unsigned long long *) ((unsigned char *) d.mlp_hand + (size_t) 32 * S + 64); xb.ga = xb.gp + 8 * 8 * 66;
                 xb.epoch = (uint32_t *) d.mlp_arrive + 6; xb.par = il & 1; xb.fault = (uint32_t *) d.mlp_arrive + PAIR_FAULT_WORD;
                 xb.spin_cap = kn.pair_spin_cap; xb.withhold = kn.xback_withhold;
-                k::xback(xb, H, d.xattn, s); chk("cross-attn + out", il);
+                if (joined) {   // ... and the front above in the same launch, the residual row handed over inside it (k::attn_join)
+                    jn.gx = (unsigned long long *) ((unsigned char *) d.mlp_hand + (size_t) 32 * S + 64 + 40960);
+                    jn.epoch = (uint32_t *) d.mlp_arrive + 8; jn.withhold = kn.join_withhold;
+                    k::attn_join(jn, H, d.xattn, s);
+                } else k::xback(xb, H, d.xattn, s);
+                chk("cross-attn + out", il);
                 goto mlp;
             }
             else if (S > 1536) {                  // the fused kernel keeps a whole row per wavefront in registers: S <= 1536

@@ -16,6 +16,7 @@
 #include "kernels.h"
 #include "wave_ops.h"
 #include "ln_row.h"
+#include "xback_body.h"
 #include <type_traits>
 
 #include <cassert>
@@ -1986,29 +1987,25 @@ __global__ __launch_bounds__(64 * WPB) void k_mlp_pair(float * __restrict__ xio,
 // contiguous quarters — what the three launches (k_gemv1, k_self_attn_rows_long, k_gemv1) compute for such a cache.  The cell at the
 // step's slot is never taken from the cache (other workgroups of this launch write it): its k / v are the granules'.  Dynamic LDS:
 // front_long_lds(cap) bytes.  Phases 1 and 3 are the short form's.
-template <int NCH, int WPB, bool LONG = false>
-__global__ __launch_bounds__(64 * WPB) void k_front(const float * x, const float * ln_g, const float * ln_b, const __half * Wqkv, __half * ck, __half * cv,
-                                                    const uint32_t dims, const int cap, const FrontArgs cold, const Stamp sp) {
+// The body is a function: k_front runs it on every workgroup, k_attn_join (below) on its first 3 S / 16 workgroups, with the cross-attention
+// back's (xback_body.h) on the workgroups behind them.  JOIN: phase 3 publishes the residual row as granules {f32, tag} (hop) to the
+// launch's other role instead of storing it — nobody else reads it, and that role's own store of x is the launch's only one.
+template <int NCH> struct FrontLds {
+    __attribute__((aligned(16))) __half act[512 * NCH];     // the attention row (phase 3)
+    __attribute__((aligned(16))) __half hq[3 * 64];         // q, k, v of this workgroup's head (phase 2)
+    __attribute__((aligned(16))) __half hatt[64];
+    __attribute__((aligned(16))) float wscr[64];
+};
+// wg = workgroup of the role, y = lock-step row (0: the one-row step) of grid_x workgroups each; `a` with its leading fields rebuilt from
+// the preloaded dwords and row y's shifts applied
+template <int NCH, int WPB, bool LONG, bool JOIN>
+__device__ __forceinline__ void front_body(const FrontArgs & a, FrontLds<NCH> & lds, const JoinHop hop, const bool stamp_on, const Stamp sp,
+                                           const int wg, const int y, const int grid_x) {
     static_assert(!LONG || WPB == 4, "the long form's quarters are four wavefronts");
-    // the leading dwords arrive in SGPRs with the wavefront (kernarg preload): the row, gain / bias, the q|k|v weights, the self cache,
-    // dims = S | par << 15 | STAMP_ON_BIT and the cache's cells — the addresses of the first loads below; `cold` is read from the argument segment where
-    // it is used (its copies of the leading fields are not read)
-    FrontArgs a = cold;
-    a.x = x; a.ln_g = ln_g; a.ln_b = ln_b; a.Wqkv = Wqkv; a.ck = ck; a.cv = cv; a.cap = cap;
-    a.S = (int) (dims & 0x7fffu); a.par = (int) ((dims >> 15) & 1u);
-    // lock-step rows: row y is a one-row problem of its own (k_gemv1's convention): shift the per-row operands, everything below is the one-row kernel
-    if (const int y = blockIdx.y) {                         // (row 0 — the one-row step — waits for no stride of `cold` in front of its loads)
-        a.x += (size_t) y * a.S; a.xout += (size_t) y * a.S; a.q16 += (size_t) y * a.S;
-        a.ck += (int64_t) y * a.cache_row_stride; a.cv += (int64_t) y * a.cache_row_stride;
-        a.kv_head += (size_t) y * a.step_stride; a.n_kv += (size_t) y * a.step_stride;
-        a.gq += (size_t) y * 2 * a.S; a.ga += (size_t) y * 2 * a.S;
-    }
-    __shared__ __attribute__((aligned(16))) __half act[512 * NCH];          // the attention row (phase 3)
-    __shared__ __attribute__((aligned(16))) __half hq[3 * 64];        // q, k, v of this workgroup's head (phase 2)
-    __shared__ __attribute__((aligned(16))) __half hatt[64];
-    __shared__ __attribute__((aligned(16))) float wscr[64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), wg = blockIdx.x;
-    const unsigned long long ts0 = stamp_t0_if(dims & STAMP_ON_BIT);
+    static_assert(!JOIN || (!LONG && WPB == 4), "the joined launch runs the one-row short-cache form");
+    __half * act = lds.act, * hq = lds.hq, * hatt = lds.hatt; float * wscr = lds.wscr;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const unsigned long long ts0 = stamp_t0_if(stamp_on);
     const int S = a.S, K = S, H = S >> 6, N1 = 3 * S;
     const int gw = wg * WPB + wave;
     constexpr int R3 = WPB == 8 ? 2 : 4;                    // rows of the out projection per wavefront
@@ -2073,6 +2070,8 @@ __global__ __launch_bounds__(64 * WPB) void k_front(const float * x, const float
     // offset the compiler cannot fold: as a uniform load at the kernel's top it was load -> vmcnt(0) -> readfirstlane, a memory round trip
     // in front of the row's loads (LayerNorm done at + 2.4 us instead of + 1.5)
     const uint32_t tag_v = a.epoch[a.par + zl] + 1u, other_v = a.epoch[(a.par ^ 1) + zl];
+    uint32_t jtag_v = 0u;                                   // JOIN: the hop's tag (its own epoch pair; the other role's first workgroup keeps the words)
+    if constexpr (JOIN) jtag_v = hop.epoch[a.par + zl] + 1u;
     __builtin_amdgcn_sched_barrier(0);
 
     // ---- phase 1
@@ -2103,7 +2102,7 @@ __global__ __launch_bounds__(64 * WPB) void k_front(const float * x, const float
         v += WMI_SHX(v, 8); v += WMI_SHX(v, 4); v += WMI_SHX(v, 2); v += WMI_SHX(v, 1);
         // lanes 0 / 16 / 32 / 48 hold rows 4 gw + 0 .. 3
         tag = __builtin_amdgcn_readfirstlane(tag_v);
-        if (wg == 0 && blockIdx.y == 0 && tid == 0) {
+        if (wg == 0 && y == 0 && tid == 0) {
             if (other_v >= tag) __hip_atomic_fetch_or(a.fault, PAIR_FAULT_PARITY, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             a.epoch[a.par ^ 1] = tag;
         }
@@ -2336,10 +2335,61 @@ __global__ __launch_bounds__(64 * WPB) void k_front(const float * x, const float
         }
         if ((lane % LPR3) == 0) {
             const float bias = a.bo ? bias3 : 0.0f;
-            a.xout[orow + wrow3] = (v + bias) + resid3;
+            const float r = (v + bias) + resid3;
+            if constexpr (JOIN) {
+                const unsigned long long gr = ((unsigned long long) __builtin_amdgcn_readfirstlane(jtag_v) << 32) | (unsigned long long) __float_as_uint(r);
+                if (gw + 1 != hop.withhold) __hip_atomic_store(hop.gx + (orow + wrow3), gr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            } else a.xout[orow + wrow3] = r;
         }
     }
-    stamp_end(sp.base, sp.slot, (int) blockIdx.y * (int) gridDim.x * WPB + gw, ts0, tm1, tm2);
+    stamp_end(sp.base, sp.slot, y * grid_x * WPB + gw, ts0, tm1, tm2);
+}
+
+template <int NCH, int WPB, bool LONG = false>
+__global__ __launch_bounds__(64 * WPB) void k_front(const float * x, const float * ln_g, const float * ln_b, const __half * Wqkv, __half * ck, __half * cv,
+                                                    const uint32_t dims, const int cap, const FrontArgs cold, const Stamp sp) {
+    // the leading dwords arrive in SGPRs with the wavefront (kernarg preload): the row, gain / bias, the q|k|v weights, the self cache,
+    // dims = S | par << 15 | STAMP_ON_BIT and the cache's cells — the addresses of the first loads below; `cold` is read from the argument segment where
+    // it is used (its copies of the leading fields are not read)
+    FrontArgs a = cold;
+    a.x = x; a.ln_g = ln_g; a.ln_b = ln_b; a.Wqkv = Wqkv; a.ck = ck; a.cv = cv; a.cap = cap;
+    a.S = (int) (dims & 0x7fffu); a.par = (int) ((dims >> 15) & 1u);
+    // lock-step rows: row y is a one-row problem of its own (k_gemv1's convention): shift the per-row operands, everything below is the one-row kernel
+    if (const int y = blockIdx.y) {                         // (row 0 — the one-row step — waits for no stride of `cold` in front of its loads)
+        a.x += (size_t) y * a.S; a.xout += (size_t) y * a.S; a.q16 += (size_t) y * a.S;
+        a.ck += (int64_t) y * a.cache_row_stride; a.cv += (int64_t) y * a.cache_row_stride;
+        a.kv_head += (size_t) y * a.step_stride; a.n_kv += (size_t) y * a.step_stride;
+        a.gq += (size_t) y * 2 * a.S; a.ga += (size_t) y * 2 * a.S;
+    }
+    __shared__ __attribute__((aligned(16))) unsigned char smem[sizeof(FrontLds<NCH>)];
+    front_body<NCH, WPB, LONG, false>(a, *reinterpret_cast<FrontLds<NCH> *>(smem), JoinHop{}, dims & STAMP_ON_BIT, sp, (int) blockIdx.x, (int) blockIdx.y, (int) gridDim.x);
+}
+
+// ------------------------------------------------------------------------------------------------ front + cross-attention back, one launch
+// k_front's body on workgroups [0, F), F = 3 S / 16, and k_xback's on the H x ns workgroups behind them (head-major, as k_xback's grid):
+// the launch boundary between the two — and the second kernel's start-up, argument fetch and every load of it that does not depend on
+// the row (gain / bias, the query weights, its K and V slices) — overlaps the front's phases; the residual row x crosses as S granules
+// {f32, tag} from the S / 16 phase-3 workgroups to the H x ns readers (front_body / xback_body, JOIN).  One row, caches of <= 64 cells,
+// S <= 512; every workgroup resident at once (attn_join_usable).  The preloaded dwords are the front role's — it is on the critical path at
+// wavefront start; the other role reads its arguments from `cold` behind them.  dims = k_front's | ns << 16.  Each role leaves its own
+// stamp record (sp: the front's, cold.spx: the back's); the two overlap in time.
+__global__ __launch_bounds__(256) void k_attn_join(const float * x, const float * ln_g, const float * ln_b, const __half * Wqkv, __half * ck, __half * cv,
+                                                   const uint32_t dims, const int cap, const JoinArgs cold, const Stamp sp) {
+    constexpr size_t LDS_BYTES = sizeof(FrontLds<1>) > sizeof(XbackLds) ? sizeof(FrontLds<1>) : sizeof(XbackLds);      // the larger role's, not the sum
+    __shared__ __attribute__((aligned(16))) unsigned char smem[LDS_BYTES];
+    const int S = (int) (dims & 0x7fffu), F = 3 * S >> 4;
+    const JoinHop hop{ cold.gx, cold.epoch, cold.withhold };
+    if ((int) blockIdx.x < F) {
+        FrontArgs a = cold.f;
+        a.x = x; a.ln_g = ln_g; a.ln_b = ln_b; a.Wqkv = Wqkv; a.ck = ck; a.cv = cv; a.cap = cap;
+        a.S = S; a.par = (int) ((dims >> 15) & 1u);
+        front_body<1, 4, false, true>(a, *reinterpret_cast<FrontLds<1> *>(smem), hop, dims & STAMP_ON_BIT, sp, (int) blockIdx.x, 0, F);
+    } else {
+        XbackArgs a = cold.x;
+        a.S = S; a.par = (int) ((dims >> 15) & 1u); a.ns = (int) ((dims >> 16) & 0x7fffu);
+        const int H = S >> 6, lin = (int) blockIdx.x - F;
+        xback_body<true>(a, *reinterpret_cast<XbackLds *>(smem), hop, dims & STAMP_ON_BIT, cold.spx, lin % H, lin / H, H, 0);
+    }
 }
 
 // -- the A/B switches of the launch paths: one read of the environment per process (an embedding application may call setenv on its own threads)
@@ -2357,6 +2407,8 @@ static Knobs read_knobs() {
     kn.front_wpb = getenv("WMI_FRONT_WPB") ? atoi(getenv("WMI_FRONT_WPB")) : 4;      // wavefronts per workgroup of the one-row k_front (8: A/B)
     kn.no_xback = getenv("WMI_NO_XBACK") != nullptr;           // cross-attention, combine + out projection as two launches (k_xback off)
     kn.xback_withhold = getenv("WMI_XBACK_WITHHOLD") ? atoi(getenv("WMI_XBACK_WITHHOLD")) : 0;      // tests: see XbackArgs::withhold
+    kn.no_join = getenv("WMI_NO_JOIN") != nullptr;             // the front and the cross-attention back as two launches (k_attn_join off)
+    kn.join_withhold = getenv("WMI_JOIN_WITHHOLD") ? atoi(getenv("WMI_JOIN_WITHHOLD")) : 0;        // tests: see JoinArgs::withhold
     return kn;
 }
 static std::atomic<const Knobs *> g_knobs{nullptr};
@@ -2488,6 +2540,34 @@ void front(const FrontArgs & a, hipStream_t st, bool long_kv) {
         if (a.S <= 512) hipLaunchKernelGGL((k_front<1, 8>), grid, dim3(512), 0, st, FRONT_FLAT(a), a, sp);
         else            hipLaunchKernelGGL((k_front<2, 8>), grid, dim3(512), 0, st, FRONT_FLAT(a), a, sp);
     }
+}
+
+bool attn_join_usable(int S, int H, int T) {
+    // the one-row short-cache front on four-wavefront workgroups (LayerNorm rows of <= 512 columns: k_xback's limit) and the back's
+    // shapes; every workgroup of the joined grid resident at once — the back's wait for the front's, the front's for each other
+    if (S > 512 || front_wpb(1) != 4 || !front_usable(S, 1, 0) || !xback_usable(S, H, T, 1)) return false;
+    XbackArgs xa{}; xa.T = T; xback_plan(xa, H, nullptr);
+    static std::atomic<int> cache[64];
+    int dev = 0; (void) hipGetDevice(&dev);
+    int v = cache[dev & 63].load(std::memory_order_relaxed);
+    if (v == 0) {                                           // (asked once per device, outside any capture: greedy_step_forms runs before one)
+        int cus = 0, nb = 0;
+        (void) hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *) k_attn_join, 256, 0) != hipSuccess) nb = 0;
+        v = 1 + std::max(0, (cus - 1) * std::min(nb, 1));   // ONE workgroup per CU counted, one CU left to others: no role waits behind the other on a CU
+        cache[dev & 63].store(v, std::memory_order_relaxed);
+    }
+    return 3 * S / 16 + H * xa.ns <= v - 1;
+}
+void attn_join(JoinArgs a, int H, float * scratch, hipStream_t st) {
+    xback_plan(a.x, H, scratch);
+    const Stamp sp = stamp_next();                          // the front role's record first, then the back's: three records per layer as before
+    a.spx = stamp_next();
+    const FrontArgs & f = a.f;
+    const int grid = 3 * f.S / 16 + H * a.x.ns;             // (S <= 512, 4 <= ns <= 8: attn_join_usable)
+    a.x.par = f.par;
+    hipLaunchKernelGGL(k_attn_join, dim3(grid), dim3(256), 0, st, f.x, f.ln_g, f.ln_b, f.Wqkv, f.ck, f.cv,
+                       (uint32_t) f.S | (uint32_t) (f.par & 1) << 15 | (uint32_t) a.x.ns << 16 | (sp.base ? STAMP_ON_BIT : 0u), f.cap, a, sp);
 }
 #undef FRONT_FLAT
 

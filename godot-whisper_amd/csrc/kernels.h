@@ -553,9 +553,21 @@ void xback(XbackArgs a, int H, float * scratch, hipStream_t st);
 // long_cap > 0: the long-cache form (caches of more than 64 cells, one row) for a cache of long_cap cells; front(): long_kv launches it
 bool front_usable(int S, int rows = 1, int long_cap = 0);
 void front(const FrontArgs & a, hipStream_t st, bool long_kv = false);
+// front() and xback() of one layer as ONE launch (k_dec.hip: k_attn_join): workgroups [0, 3 S / 16) run k_front's body, the H x ns behind
+// them k_xback's, and the residual row crosses from the first role's out projection to the second's LayerNorm as S granules {f32, tag}
+// (gx, 8 bytes each, zeroed once) instead of through memory and a launch boundary.  f / x: the two launches' arguments, each with its own
+// granules, epoch words and `withhold` (x.x is not read: the row arrives through gx; f.xout is not written: x.xout is the launch's only
+// store of the row).  epoch: the hop's own pair of words, tags by MlpPairArgs' rules with f.par; time-outs and slow polls go to x.fault,
+// the polls are bounded by x.spin_cap.  withhold: tests, front-role wavefront `withhold - 1` never publishes its granules of the row.
+// One row, caches of <= 64 cells (the long-cache form of the front keeps its own launch), S <= 512.  Both roles are stamped: two slots
+// of stamp_next(), the front's first, whose records overlap in time.
+struct JoinArgs { FrontArgs f; XbackArgs x; unsigned long long * gx; uint32_t * epoch; int withhold; Stamp spx; };
+bool attn_join_usable(int S, int H, int T);                 // front_usable(S) and xback_usable(S, H, T) hold, and the joined grid is resident at once
+void attn_join(JoinArgs a, int H, float * scratch, hipStream_t st);
+void xback_plan(XbackArgs & a, int H, float * scratch);     // fills ks / ns / pmax / part_o / part_l from the cross-attention's scratch layout
 // A/B switches of the launch paths that are read from the environment: once per process (reload_knobs(): lab scripts that flip them between
 // probe calls of one process, exported as wmi_reload_knobs — not while a transcription runs on another thread)
-struct Knobs { bool no_mlp_pair; int sa_wpb; bool gemv1_wide_generic; bool host_draws; bool debug_sync; int pair_withhold; uint32_t pair_spin_cap; bool no_front; int front_withhold; bool no_xback; int xback_withhold; int front_wpb; };
+struct Knobs { bool no_mlp_pair; int sa_wpb; bool gemv1_wide_generic; bool host_draws; bool debug_sync; int pair_withhold; uint32_t pair_spin_cap; bool no_front; int front_withhold; bool no_xback; int xback_withhold; int front_wpb; bool no_join; int join_withhold; };
 const Knobs & knobs();
 void reload_knobs();
 void set_attn_one_group(bool on);              // encoder attention: never split the keys over two wave groups (bit-identical for any batch)

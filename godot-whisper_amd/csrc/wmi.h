@@ -591,7 +591,8 @@ bool draft_verify(whisper_context & ctx, const std::vector<int32_t> & prompt, co
                   float * logits_out, std::vector<whisper_token_data> & picks, int & accepted);
 // forms: when given, the launch form the step took (STEP_FORM_* bits; the test hook wmi_selftest_greedy_step reports them)
 enum : unsigned { STEP_FORM_LONG_KV = 1, STEP_FORM_CHAINED = 2, STEP_FORM_GRAPH = 4, STEP_FORM_PAIRED = 8, STEP_FORM_FRONTED = 16,
-                  STEP_FORM_BACKED = 32, STEP_FORM_RERUN = 64, STEP_FORM_SLOW = 128, STEP_FORM_QUANTISED = 256 };
+                  STEP_FORM_BACKED = 32, STEP_FORM_RERUN = 64, STEP_FORM_SLOW = 128, STEP_FORM_QUANTISED = 256,
+                  STEP_FORM_JOINED = 512 };      // JOINED: the front and the cross-attention back of a layer as one launch (with FRONTED and BACKED)
 bool decode_greedy_step(whisper_context & ctx, int32_t token, int32_t pos, const StepFilter & f, whisper_token_data & out, unsigned * forms = nullptr);
 bool upload_static_ban(whisper_context & ctx, const whisper_full_params & params);
 // The no-speech probability of a window (kernels.h: no_speech_*).  A launch is tagged; no_speech_read waits for the record

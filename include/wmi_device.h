@@ -345,7 +345,9 @@ WHISPER_API double wmi_selftest_proj(struct whisper_context * ctx, int op, int n
  * the device picked (id, tid, p, plog, pt, ptsum); forms (optional): the launch form the step took, a bit set —
  *   1 cache longer than 64 cells, 2 chained onto the previous step's pick, 4 replayed from a captured graph, 8 both MLP projections as
  *   one launch, 16 the front of each layer as one launch (together with 1: that launch's long-cache form), 32 the cross-attention back
- *   as one launch, 64 re-run after a failed in-launch hand-off, 128 a slow hand-off was reported, 256 the block-quantised step.
+ *   as one launch, 64 re-run after a failed in-launch hand-off, 128 a slow hand-off was reported, 256 the block-quantised step,
+ *   512 the front and the cross-attention back of each layer as ONE launch (only with 16 and 32, caches of <= 64 cells; WMI_NO_JOIN=1,
+ *   WMI_NO_FRONT=1 or WMI_NO_XBACK=1 turns it off).
  * Returns 0, or a negative value on error. */
 WHISPER_API int wmi_selftest_greedy_step(struct whisper_context * ctx, whisper_token token, int pos, float * logits, whisper_token_data * out,
                                          int * forms);
