@@ -213,6 +213,10 @@ class wmi_speaker(C.Structure):  # include/wmi_device.h: the channel energies of
     _fields_ = [("speaker", C.c_int), ("reserved", C.c_int), ("is0", C.c_longlong), ("is1", C.c_longlong), ("e0", C.c_double), ("e1", C.c_double)]
 
 
+class wmi_channel_segment(C.Structure):  # include/wmi_device.h: where a segment of the dialogue view comes from (wmi_channels_get_segment)
+    _fields_ = [("channel", C.c_int), ("index", C.c_int)]
+
+
 class wmi_grammar_status(C.Structure):  # include/wmi_device.h: the counters and capacities of the grammar's device route (wmi_set_grammar_device)
     _fields_ = [("steps_device", C.c_int32), ("rows_host", C.c_int32), ("cap_stacks", C.c_int32), ("cap_depth", C.c_int32),
                 ("cap_words", C.c_int32), ("reject_us", C.c_float)]

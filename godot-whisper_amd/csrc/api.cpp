@@ -810,6 +810,7 @@ int wmi_batch_select(struct whisper_context * ctx, int chunk) {
     if (chunk < (int) ctx->batch->windows.size()) ctx->state->windows = ctx->batch->windows[chunk]; else ctx->state->windows.clear();
     if (chunk < (int) ctx->batch->lang_id.size() && ctx->batch->lang_id[chunk] >= 0) ctx->state->lang_id = ctx->batch->lang_id[chunk];
     speaker_select(*ctx, chunk);
+    channels_deselect(*ctx);
     return (int) ctx->state->result_all.size();
 }
 

@@ -759,6 +759,7 @@ int full_batch(whisper_context & ctx, whisper_full_params params, const float * 
     State * primary = ctx.state;
     if (!ctx.batch) ctx.batch = new BatchWork();
     speaker_invalidate(ctx);                                       // (as full(): no channel table until the caller commits one per chunk)
+    channels_invalidate(ctx);
     // chunk c's own audio_ctx, and the parameters whisper_full would get for it
     auto actx = [&](int c) { return audio_ctx ? audio_ctx[c] : params.audio_ctx; };
     auto params_of = [&](int c) { whisper_full_params p = params; p.audio_ctx = actx(c); return p; };

@@ -111,6 +111,7 @@ int full(whisper_context & ctx, whisper_full_params params, const float * sample
     const HParams & hp = ctx.model.hp;
     st.result_all.clear();
     speaker_invalidate(ctx);                                         // (the result to come carries no channel table until its caller says so)
+    channels_invalidate(ctx);
     st.ts_failed = false;
     st.lang_probs.clear();
     // the draft armed for this call (wmi_set_draft): taken here whatever becomes of it; honoured in the first window's first attempt only

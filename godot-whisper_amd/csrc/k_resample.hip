@@ -27,6 +27,8 @@
 // What an input frame is read from is a template parameter (kernels.h SrcKind, in_frame<KIND>): a mono f32 buffer, the capture session's
 // f32 stereo frames, or the packed s16 / s8 frames of an AudioStreamWAV, mono or stereo (wav_frame.h: decode and fold per tap).  Plan,
 // positions, tap order and accumulators do not depend on it: the output equals that of a mono f32 buffer decoded first, bit for bit.
+// k_resample_split / k_resample_simple_split keep the two channels of a stereo kind apart instead of folding them: one thread, one tap
+// walk, two results.
 
 #include "kernels.h"
 #include "wav_frame.h"
@@ -153,6 +155,89 @@ __global__ __launch_bounds__(256) void k_resample_simple(const ResampleArgs a) {
     const long long i1 = pos <= 0 ? 0 : (pos > last ? last : pos);
     const float d = in_frame<KIND>(a, i1) - v0;                                               // float difference, then double multiply and add
     a.out[n] = (float) ((double) v0 + frac * (double) d);
+}
+
+// The two channels of a stereo kind resampled apart in one launch (kernels.h resample_launch_split): k_resample's thread with two
+// accumulator pairs.  What does not depend on the channel is computed once — the position, start_index, the tap walk and every tap's
+// interpolated coefficient ic —; each channel's sums then receive exactly the operations k_resample applies to a mono buffer holding that
+// channel (the same taps in the same order, the zero history and tail, left half then right half, out_scale * (left + right)), so
+// out0 / out1 equal two single-channel launches bit for bit.  A frame's two samples come from one load where the source lies on its frame
+// grid (WHOLE, wav_frame.h wav_channel).  a.raw holds the frames of every kind, a.out is out0; a.n0 is not served.
+template <int KIND, bool WHOLE>
+__global__ __launch_bounds__(256) void k_resample_split(const ResampleArgs a, float * __restrict__ out1) {
+    const long long n = (long long) blockIdx.x * 256 + threadIdx.x;
+    if (n >= a.n_out) return;
+    long long pos; double frac;
+    out_position(a, n, &pos, &frac);
+    const int increment = a.increment;
+    const int start_index = (int) __builtin_rint(frac * a.float_inc * 4096.0);
+    const int max_index = a.half_len << 12;
+    const long long last = a.n_in - 1;
+    const float * __restrict__ c = a.coeffs;
+
+    int fi = start_index;
+    int cnt = (max_index - fi) / increment;
+    fi += cnt * increment;
+    long long di = pos - cnt;
+    double left0 = 0.0, left1 = 0.0;
+    do {
+        const double fraction = (double) (fi & 4095) * (1.0 / 4096.0);
+        const int ix = fi >> 12;
+        const float c0 = c[ix], c1 = c[ix + 1];
+        const double ic = (double) c0 + fraction * (double) (c1 - c0);
+        const long long dc = di < 0 ? 0 : (di > last ? last : di);
+        float v0, v1;
+        wav_channel<KIND, WHOLE>(a.raw, dc, &v0, &v1);
+        const bool off = di < 0 || di > last;
+        v0 = off ? 0.0f : v0; v1 = off ? 0.0f : v1;
+        left0 += ic * (double) v0;
+        left1 += ic * (double) v1;
+        fi -= increment;
+        di += 1;
+    } while (fi >= 0);
+
+    fi = increment - start_index;
+    cnt = (max_index - fi) / increment;
+    fi += cnt * increment;
+    di = pos + 1 + cnt;
+    double right0 = 0.0, right1 = 0.0;
+    do {
+        const double fraction = (double) (fi & 4095) * (1.0 / 4096.0);
+        const int ix = fi >> 12;
+        const float c0 = c[ix], c1 = c[ix + 1];
+        const double ic = (double) c0 + fraction * (double) (c1 - c0);
+        const long long dc = di > last ? last : di;
+        float v0, v1;
+        wav_channel<KIND, WHOLE>(a.raw, dc, &v0, &v1);
+        v0 = di > last ? 0.0f : v0; v1 = di > last ? 0.0f : v1;
+        right0 += ic * (double) v0;
+        right1 += ic * (double) v1;
+        fi -= increment;
+        di -= 1;
+    } while (fi > 0);
+
+    a.out[n] = (float) (a.out_scale * (left0 + right0));
+    out1[n] = (float) (a.out_scale * (left1 + right1));
+}
+
+// k_resample_simple for the two channels: the two frames are read once, each channel gets the hold or the interpolation of its own samples
+template <bool LINEAR, int KIND, bool WHOLE>
+__global__ __launch_bounds__(256) void k_resample_simple_split(const ResampleArgs a, float * __restrict__ out1) {
+    const long long n = (long long) blockIdx.x * 256 + threadIdx.x;
+    if (n >= a.n_out) return;
+    long long pos; double frac;
+    out_position(a, n, &pos, &frac);
+    const long long last = a.n_in - 1;
+    const long long i0 = pos <= 0 ? 0 : (pos - 1 > last ? last : pos - 1);
+    float l0, r0;
+    wav_channel<KIND, WHOLE>(a.raw, i0, &l0, &r0);
+    if (!LINEAR) { a.out[n] = l0; out1[n] = r0; return; }
+    const long long i1 = pos <= 0 ? 0 : (pos > last ? last : pos);
+    float l1, r1;
+    wav_channel<KIND, WHOLE>(a.raw, i1, &l1, &r1);
+    const float dl = l1 - l0, dr = r1 - r0;
+    a.out[n] = (float) ((double) l0 + frac * (double) dl);
+    out1[n] = (float) ((double) r0 + frac * (double) dr);
 }
 
 double frac_one(double x) {                                   // thirdparty/libsamplerate/src/common.h:149-158
@@ -394,6 +479,32 @@ void resample_launch_kind(const ResamplePlan & pl, int kind, const void * d_src,
                           const int * d_pos, const double * d_frac, long long first, hipStream_t st) {
     if (kind < SRC_F32_MONO || kind > SRC_S8_STEREO) return;
     launch(pl, kind, d_src, n_in, d_out, d_coeffs, d_pos, d_frac, first, st);
+}
+
+template <int KIND, bool WHOLE>
+static void launch_split_as(const ResamplePlan & pl, const dim3 grid, const ResampleArgs & a, float * out1, hipStream_t st) {
+    if (pl.converter == 3) hipLaunchKernelGGL((k_resample_simple_split<false, KIND, WHOLE>), grid, dim3(256), 0, st, a, out1);
+    else if (pl.converter == 4) hipLaunchKernelGGL((k_resample_simple_split<true, KIND, WHOLE>), grid, dim3(256), 0, st, a, out1);
+    else hipLaunchKernelGGL((k_resample_split<KIND, WHOLE>), grid, dim3(256), 0, st, a, out1);
+}
+
+void resample_launch_split(const ResamplePlan & pl, int kind, const void * d_src, long long n_in, float * out0, float * out1,
+                           const float * d_coeffs, const int * d_pos, const double * d_frac, hipStream_t st) {
+    if ((kind != SRC_F32_STEREO && kind != SRC_S16_STEREO && kind != SRC_S8_STEREO) || pl.n_out <= 0) return;
+    ResampleArgs a;
+    a.in = nullptr; a.in2 = nullptr; a.raw = d_src;
+    a.n_in = n_in; a.out = out0; a.n_out = pl.n_out; a.n0 = 0;
+    a.coeffs = d_coeffs; a.half_len = pl.half_len;
+    a.float_inc = pl.float_inc; a.out_scale = pl.out_scale; a.increment = pl.increment;
+    a.m = pl.stepper->m; a.sh = pl.stepper->sh; a.frac_scale = ldexp(1.0, -pl.stepper->sh);
+    a.pos_tab = pl.need_table ? d_pos : nullptr; a.frac_tab = pl.need_table ? d_frac : nullptr;
+    const dim3 grid((unsigned) ((pl.n_out + 255) / 256));
+    const bool whole = ((uintptr_t) d_src % (uintptr_t) wav_frame_bytes(kind)) == 0;      // on the frame grid: a frame is one load
+    switch (kind) {
+        case SRC_F32_STEREO: if (whole) launch_split_as<SRC_F32_STEREO, true>(pl, grid, a, out1, st); else launch_split_as<SRC_F32_STEREO, false>(pl, grid, a, out1, st); break;
+        case SRC_S16_STEREO: if (whole) launch_split_as<SRC_S16_STEREO, true>(pl, grid, a, out1, st); else launch_split_as<SRC_S16_STEREO, false>(pl, grid, a, out1, st); break;
+        default:             if (whole) launch_split_as<SRC_S8_STEREO, true>(pl, grid, a, out1, st); else launch_split_as<SRC_S8_STEREO, false>(pl, grid, a, out1, st); break;
+    }
 }
 
 // Output k of a plan does not depend on the input length as long as every frame it reads exists: its position comes from k alone and the

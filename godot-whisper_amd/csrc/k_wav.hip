@@ -66,7 +66,69 @@ __global__ __launch_bounds__(256) void k_wav_decode(const unsigned char * __rest
     if (f < n_frames) out[f] = wav_frame<KIND>(src, f);
 }
 
+// k_wav_decode's scheme for the two channels of a stereo kind kept apart (kernels.h wav_split): the same head / body / tail, every frame
+// read once, no fold — out0[f] the left sample, out1[f] the right.  A group's eight pairs leave as two 16-byte stores per destination
+// where that destination allows (out0 and out1 are aligned independently), else as eight scalar stores.
+__device__ __forceinline__ void store_group(float * o, const float * r) {
+    if (((uintptr_t) o & 15) == 0) {
+        ((float4 *) o)[0] = make_float4(r[0], r[1], r[2], r[3]);
+        ((float4 *) o)[1] = make_float4(r[4], r[5], r[6], r[7]);
+    } else {
+#pragma unroll
+        for (int j = 0; j < WAV_GROUP; ++j) o[j] = r[j];
+    }
+}
+
+template <int KIND>
+__global__ __launch_bounds__(256) void k_wav_split(const unsigned char * __restrict__ src, long long n_frames, long long head, long long body,
+                                                   float * __restrict__ out0, float * __restrict__ out1) {
+    constexpr int FB = wav_frame_bytes(KIND);
+    constexpr int WORDS = WAV_GROUP * FB / 4;                                    // 4 (8-bit) .. 16 (f32): whole 16-byte pieces
+    const long long t = (long long) blockIdx.x * 256 + threadIdx.x;
+    if (t < body) {
+        const long long f0 = head + t * WAV_GROUP;
+        uint32_t w[WORDS];
+        const unsigned char * p = src + f0 * FB;
+#pragma unroll
+        for (int q = 0; q < WORDS / 4; ++q) { const uint4 v = ((const uint4 *) p)[q]; w[4 * q] = v.x; w[4 * q + 1] = v.y; w[4 * q + 2] = v.z; w[4 * q + 3] = v.w; }
+        float l[WAV_GROUP], r[WAV_GROUP];
+#pragma unroll
+        for (int j = 0; j < WAV_GROUP; ++j) { l[j] = group_sample<KIND>(w, 2 * j); r[j] = group_sample<KIND>(w, 2 * j + 1); }
+        store_group(out0 + f0, l);
+        store_group(out1 + f0, r);
+        return;
+    }
+    // the frames around the groups, as in k_wav_decode; sample-sized loads (the source may be one sample off its frame grid)
+    const long long i = t - body;
+    const long long f = i < head ? i : head + body * WAV_GROUP + (i - head);
+    if (f < n_frames) {
+        float l, r;
+        wav_channel<KIND>(src, f, &l, &r);
+        out0[f] = l; out1[f] = r;
+    }
+}
+
 }  // namespace
+
+bool wav_split(int kind, const void * d_src, long long n_frames, float * out0, float * out1, hipStream_t st) {
+    if ((kind != SRC_F32_STEREO && kind != SRC_S16_STEREO && kind != SRC_S8_STEREO) || n_frames < 0 || (n_frames > 0 && (!d_src || !out0 || !out1))) return false;
+    if (n_frames == 0) return true;
+    const int fb = wav_frame_bytes(kind);
+    long long head = -1;                                                         // as wav_decode: the first frame on a 16-byte boundary
+    for (int h = 0; h < 16; ++h) if ((((uintptr_t) d_src + (uintptr_t) h * fb) & 15) == 0) { head = h; break; }
+    long long body = 0;
+    if (head < 0 || head > n_frames) head = n_frames;
+    else body = (n_frames - head) / WAV_GROUP;
+    const long long threads = body + (n_frames - body * WAV_GROUP);
+    const dim3 grid((unsigned) ((threads + 255) / 256));
+    const unsigned char * s = (const unsigned char *) d_src;
+    switch (kind) {
+        case SRC_F32_STEREO: hipLaunchKernelGGL((k_wav_split<SRC_F32_STEREO>), grid, dim3(256), 0, st, s, n_frames, head, body, out0, out1); break;
+        case SRC_S16_STEREO: hipLaunchKernelGGL((k_wav_split<SRC_S16_STEREO>), grid, dim3(256), 0, st, s, n_frames, head, body, out0, out1); break;
+        default:             hipLaunchKernelGGL((k_wav_split<SRC_S8_STEREO>), grid, dim3(256), 0, st, s, n_frames, head, body, out0, out1); break;
+    }
+    return hipGetLastError() == hipSuccess;
+}
 
 bool wav_decode(int kind, const void * d_src, long long n_frames, float * out, hipStream_t st) {
     if (kind < SRC_F32_MONO || kind > SRC_S8_STEREO || n_frames < 0 || (n_frames > 0 && (!d_src || !out))) return false;

@@ -190,6 +190,14 @@ void resample_launch_kind(const ResamplePlan & pl, int kind, const void * d_src,
 // group of eight one per thread — or every frame so when no frame starts on such a boundary (a stereo source one sample off its frame grid).
 // d_src: sample-aligned; out: any f32 pointer.  false: bad kind / launch error.  n_frames = 0 launches nothing.
 bool wav_decode(int kind, const void * d_src, long long n_frames, float * out, hipStream_t st);
+// The two channels of a STEREO kind kept apart, one launch each (wmi_full_wav_channels): every frame is read once, out0 gets the left and
+// out1 the right samples — no fold.  wav_split is wav_decode's scheme at the source's own rate; resample_launch_split is
+// resample_launch_kind's thread with the channel-independent work (position, tap walk, interpolated coefficients) shared, and each of its
+// outputs equals resample_launch on a mono buffer of that channel bit for bit.  d_src: sample-aligned; out0 / out1: any f32 pointers, room
+// for n_frames / pl.n_out each.  A mono kind: false / nothing is launched.
+bool wav_split(int kind, const void * d_src, long long n_frames, float * out0, float * out1, hipStream_t st);
+void resample_launch_split(const ResamplePlan & pl, int kind, const void * d_src, long long n_in, float * out0, float * out1,
+                           const float * d_coeffs, const int * d_pos, const double * d_frac, hipStream_t st);
 // Channel energies per centisecond of a STEREO source (k_speaker.hip; speaker_ranges.h has the definition): one launch over n frames of
 // `kind` (SRC_F32_STEREO, SRC_S16_STEREO, SRC_S8_STEREO) at `rate` Hz writes nb = channel_bins_count(n, rate) pairs {left, right} of 8-byte
 // sums over frames [B(b), min(B(b + 1), n - 1)), B(b) = (b * rate) / 100, and behind them the two magnitudes of frame n - 1: (nb + 1) * 16

@@ -46,6 +46,7 @@ void select_merged(whisper_context & ctx) {
     ctx.state->windows = l.windows;
     if (l.lang_id >= 0) ctx.state->lang_id = l.lang_id;
     speaker_select(ctx, -1);
+    channels_deselect(ctx);
 }
 
 int full_long(whisper_context * ctx, whisper_full_params params, const float * pcm, int n, bool on_device, const wmi_long_params & lp) {

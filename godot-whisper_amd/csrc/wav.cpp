@@ -17,6 +17,7 @@
 #include <vector>
 #include "wmi.h"
 #include "kernels.h"
+#include "channel_merge.h"
 
 namespace wmi {
 
@@ -43,6 +44,9 @@ struct WavWork {
     float * d_pcm = nullptr; size_t pcm_cap = 0;                   // the samples of the long and the batch form
     hipEvent_t ev[2] = {nullptr, nullptr}; bool ev_pending = false;
     int64_t stats[5] = {0, 0, 0, 0, 0};
+    // wmi_full_wav_channels: the dialogue view of the last call (copies of the two channels' segments in channel_merge.h's order) and where
+    // each came from; valid until the next transcription call, shown: the dialogue is what the accessors read now
+    struct Channels { std::vector<Segment> merged; std::vector<wmi_channel_segment> from; int lang_id = -1; bool valid = false, shown = false; } ch;
 };
 
 namespace {
@@ -149,7 +153,7 @@ hipStream_t mel_stream_of(State & st) { return st.dev.mel_stream ? st.dev.mel_st
 
 }  // namespace
 
-bool wav_job_run(whisper_context & ctx, WavJob & job, float * d_dst, hipStream_t s) {
+bool wav_job_run(whisper_context & ctx, WavJob & job, float * d_dst, hipStream_t s, float * d_dst1) {
     WavWork * w = ctx.wav;
     if (!w) return false;
     const WavPlan & p = job.plan;
@@ -164,7 +168,7 @@ bool wav_job_run(whisper_context & ctx, WavJob & job, float * d_dst, hipStream_t
             src = d;
         }
         if (!p.resample) {
-            if (!k::wav_decode(p.kind, src, p.frames, d_dst, s)) return false;
+            if (!(d_dst1 ? k::wav_split(p.kind, src, p.frames, d_dst, d_dst1, s) : k::wav_decode(p.kind, src, p.frames, d_dst, s))) return false;
         } else {
             const float * d_tab = nullptr;
             if (job.converter <= 2) {                                      // the converter's table, shared with wmi_resample
@@ -187,13 +191,14 @@ bool wav_job_run(whisper_context & ctx, WavJob & job, float * d_dst, hipStream_t
                 w->stats[0] += p.n_out * 12;
                 d_pos = w->d_pos + job.tab_off; d_frac = w->d_frac + job.tab_off;
             }
-            k::resample_launch_kind(p.pl, p.kind, src, p.frames, d_dst, d_tab, d_pos, d_frac, 0, s);
+            if (d_dst1) k::resample_launch_split(p.pl, p.kind, src, p.frames, d_dst, d_dst1, d_tab, d_pos, d_frac, s);
+            else k::resample_launch_kind(p.pl, p.kind, src, p.frames, d_dst, d_tab, d_pos, d_frac, 0, s);
             HIP_TRY(hipGetLastError());
         }
         w->stats[3] += 1;
         if (job.spk_slot >= 0 && !speaker_queue(ctx, job.spk_slot, src, s)) return false;       // the frames once more, where they lie
     }
-    w->stats[1] += p.frames; w->stats[2] += p.n_out;
+    w->stats[1] += p.frames; w->stats[2] += d_dst1 ? 2 * p.n_out : p.n_out;
     if (job.mark_end) { HIP_TRY(hipEventRecord(w->ev[1], s)); w->ev_pending = true; }
     return true;
 }
@@ -206,6 +211,50 @@ void free_wav(whisper_context & ctx) {
     delete w;
     ctx.wav = nullptr;
 }
+
+void channels_invalidate(whisper_context & ctx) { if (ctx.wav) ctx.wav->ch.valid = ctx.wav->ch.shown = false; }
+
+void channels_deselect(whisper_context & ctx) { if (ctx.wav) ctx.wav->ch.shown = false; }
+
+namespace {
+
+// a stereo clip's plan for the two-channel calls; a mono clip is -12 (wmi_wav_speaker's code), behind every other conversion error
+WavPlan channels_plan(const wmi_wav * w, int converter, const char * who) {
+    WavPlan p = wav_plan(w, converter, who);
+    if (!p.err && w->stereo != 1) p.err = -12;
+    return p;
+}
+
+// the dialogue view (as long.cpp's select_merged): copies of the segments, channel 0's language, no windows and no speaker table
+void select_dialogue(whisper_context & ctx) {
+    WavWork::Channels & c = ctx.wav->ch;
+    ctx.state->result_all = c.merged;
+    ctx.state->windows.clear();
+    if (c.lang_id >= 0) ctx.state->lang_id = c.lang_id;
+    speaker_select(ctx, -1);
+    c.shown = true;
+}
+
+// after wmi_full_batch returned 0 on the two channels: the dialogue view of its two results, left selected
+void build_dialogue(whisper_context & ctx) {
+    WavWork::Channels & c = ctx.wav->ch;
+    const BatchWork & bw = *ctx.batch;
+    std::vector<int64_t> t0[2];
+    for (int ch = 0; ch < 2; ++ch) for (const Segment & seg : bw.results[ch]) t0[ch].push_back(seg.t0);
+    const size_t n = t0[0].size() + t0[1].size();
+    std::vector<int> channel(n), index(n);
+    chm::merge(t0[0].data(), (int) t0[0].size(), t0[1].data(), (int) t0[1].size(), channel.data(), index.data());
+    c.merged.clear(); c.from.clear();
+    for (size_t i = 0; i < n; ++i) {
+        c.merged.push_back(bw.results[channel[i]][index[i]]);           // a copy: text, tokens, times and t_dtw as they are
+        c.from.push_back(wmi_channel_segment{ channel[i], index[i] });
+    }
+    c.lang_id = !bw.lang_id.empty() ? bw.lang_id[0] : -1;
+    c.valid = true;
+    select_dialogue(ctx);
+}
+
+}  // namespace
 
 }  // namespace wmi
 
@@ -324,6 +373,79 @@ int wmi_full_batch_wav(struct whisper_context * ctx, struct whisper_full_params 
         if (r == 0) speaker_commit(*ctx, 2, params.token_timestamps);
         return r;
     } catch (...) { WMI_ERR("%s: out of memory\n", __func__); return -103; }
+}
+
+int wmi_wav_to_pcm_channels(struct whisper_context * ctx, const struct wmi_wav * wav, int converter, float * dst0, float * dst1, int dst_capacity,
+                            int dst_on_device) {
+    if (!ctx || !ctx->state) return -1;
+    try {
+        WavJob job; job.wav = wav; job.converter = converter;
+        job.plan = channels_plan(wav, converter, __func__);
+        if (job.plan.err) return job.plan.err;
+        if (!dst0 || !dst1 || dst_capacity < 0) return -1;
+        if (job.plan.n_out > dst_capacity) return -4;
+        Scope lk(ctx);
+        if (!compute_ready(*ctx, __func__)) return -2;
+        if (!HIP_OK(hipSetDevice(ctx->device))) return -2;
+        WavWork * w = work(*ctx);
+        if (!w) return -3;
+        hipStream_t s = mel_stream_of(*ctx->state);
+        const size_t n = (size_t) job.plan.n_out, off1 = (n + 63) & ~(size_t) 63;
+        if (!reserve_jobs(*w, &job, 1) || (!dst_on_device && !reserve(w->d_out, w->out_cap, off1 + n, 1024))) return -3;
+        float * d0 = dst_on_device ? dst0 : w->d_out, * d1 = dst_on_device ? dst1 : w->d_out + off1;
+        bool ok = wav_job_run(*ctx, job, d0, s, d1);                       // the ONE launch writes both
+        if (ok && !dst_on_device && n > 0)
+            ok = HIP_OK(hipMemcpyAsync(dst0, d0, n * 4, hipMemcpyDeviceToHost, s)) && HIP_OK(hipMemcpyAsync(dst1, d1, n * 4, hipMemcpyDeviceToHost, s));
+        ok = HIP_OK(hipStreamSynchronize(s)) && ok;
+        return ok ? (int) n : -3;
+    } catch (...) { WMI_ERR("%s: out of memory\n", __func__); return -3; }
+}
+
+int wmi_full_wav_channels(struct whisper_context * ctx, struct whisper_full_params params, const struct wmi_wav * wav, int converter) {
+    if (!ctx || !ctx->state) return -101;
+    try {
+        { Scope lk(ctx); DraftRefuse no_draft(ctx->state.get()); }         // (no draft is carried: dropped whatever the call returns)
+        WavJob job; job.wav = wav; job.converter = converter;
+        job.plan = channels_plan(wav, converter, __func__);
+        if (job.plan.err) return -100 + job.plan.err;
+        Scope lk(ctx);                                                     // wmi_full_batch's locks
+        if (!compute_ready(*ctx, __func__)) return -102;
+        if (!HIP_OK(hipSetDevice(ctx->device))) return -102;
+        WavWork * w = work(*ctx);
+        const size_t n = (size_t) job.plan.n_out, off1 = (n + 63) & ~(size_t) 63;      // the slices as wmi_full_batch_wav places its clips
+        if (!w || !reserve_jobs(*w, &job, 1) || !reserve(w->d_pcm, w->pcm_cap, std::max<size_t>(2 * off1, 1), 4096)) return -103;
+        hipStream_t s = mel_stream_of(*ctx->state);
+        bool ok = wav_job_run(*ctx, job, w->d_pcm, s, w->d_pcm + off1);    // one upload, one launch, both channels ...
+        ok = HIP_OK(hipStreamSynchronize(s)) && ok;                        // ... one wait
+        if (!ok) return -103;
+        const float * pcm[2] = { w->d_pcm, w->d_pcm + off1 }; const int ns[2] = { (int) n, (int) n };
+        const int r = wmi_full_batch(ctx, params, pcm, ns, 2, 1);          // (a speaker mode is not served: the result carries no table)
+        if (r == 0 && ctx->batch && ctx->batch->results.size() == 2) build_dialogue(*ctx);
+        return r;
+    } catch (...) { WMI_ERR("%s: out of memory\n", __func__); return -103; }
+}
+
+int wmi_channels_select(struct whisper_context * ctx, int channel) {
+    if (!ctx) return -1;
+    Scope lk(ctx);
+    if (!ctx->state || !ctx->wav || !ctx->wav->ch.valid || !ctx->batch || ctx->batch->results.size() != 2 || channel < -1 || channel > 1) return -1;
+    if (channel >= 0) return wmi_batch_select(ctx, channel);
+    select_dialogue(*ctx);
+    return (int) ctx->state->result_all.size();
+}
+
+int wmi_channels_get_segment(struct whisper_context * ctx, int i, struct wmi_channel_segment * out) {
+    if (!ctx || !out) return -1;
+    Scope lk(ctx);
+    const WavWork * w = ctx->wav;
+    if (!w || !w->ch.valid || !w->ch.shown || i < 0 || i >= (int) w->ch.from.size()) return -1;
+    *out = w->ch.from[(size_t) i];
+    return 0;
+}
+
+int wmi_selftest_channels_merge(const int64_t * t0_a, int n_a, const int64_t * t0_b, int n_b, int * out_channel, int * out_index) {
+    if (n_a < 0 || n_b < 0 || (n_a > 0 && !t0_a) || (n_b > 0 && !t0_b) || (n_a + (long long) n_b > 0 && (!out_channel || !out_index))) return -1;
+    return chm::merge(t0_a, n_a, t0_b, n_b, out_channel, out_index);
 }
 
 int wmi_wav_stats(struct whisper_context * ctx, int64_t * out5) {

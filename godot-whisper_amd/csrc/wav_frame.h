@@ -24,6 +24,24 @@ __device__ __forceinline__ float wav_frame(const void * __restrict__ src, long l
     const int8_t * p = (const int8_t *) src + 2 * i;
     return wav_fold(wav_s8(p[0]), wav_s8(p[1]));
 }
+
+// Frame i of a STEREO kind as its two samples, no fold (k_wav.hip k_wav_split, k_resample.hip k_resample_split: the two channels of a
+// dialogue kept apart).  WHOLE: `src` lies on the frame grid (frame bytes: 8 / 4 / 2), so the frame is one load; otherwise the source is
+// only sample-aligned and each sample is a load of its own.  Either way the same divisions as wav_frame.
+template <int KIND, bool WHOLE = false>
+__device__ __forceinline__ void wav_channel(const void * __restrict__ src, long long i, float * l, float * r) {
+    static_assert(KIND == SRC_F32_STEREO || KIND == SRC_S16_STEREO || KIND == SRC_S8_STEREO, "a stereo kind");
+    if (KIND == SRC_F32_STEREO) {
+        if (WHOLE) { const float2 f = ((const float2 *) src)[i]; *l = f.x; *r = f.y; }
+        else { const float * p = (const float *) src + 2 * i; *l = p[0]; *r = p[1]; }
+    } else if (KIND == SRC_S16_STEREO) {
+        if (WHOLE) { const uint32_t w = ((const uint32_t *) src)[i]; *l = wav_s16((int16_t) (uint16_t) w); *r = wav_s16((int16_t) (uint16_t) (w >> 16)); }
+        else { const int16_t * p = (const int16_t *) src + 2 * i; *l = wav_s16(p[0]); *r = wav_s16(p[1]); }
+    } else {
+        if (WHOLE) { const uint16_t w = ((const uint16_t *) src)[i]; *l = wav_s8((int8_t) (uint8_t) w); *r = wav_s8((int8_t) (uint8_t) (w >> 8)); }
+        else { const int8_t * p = (const int8_t *) src + 2 * i; *l = wav_s8(p[0]); *r = wav_s8(p[1]); }
+    }
+}
 #endif
 
 constexpr int wav_frame_bytes(int kind) {

@@ -433,9 +433,14 @@ void state_installs_set(StateInstall * top);
 // AudioStreamWAV ingest (wav.cpp): the context's work set, and one planned conversion (DeviceState::pcm_job)
 struct WavWork;
 struct WavJob;
-// queue the job's upload, position table and its one conversion launch on `s`; the mono 16 kHz samples land at d_dst (room for the job's count)
-bool wav_job_run(whisper_context & ctx, WavJob & job, float * d_dst, hipStream_t s);
+// queue the job's upload, position table and its one conversion launch on `s`; the mono 16 kHz samples land at d_dst (room for the job's count).
+// d_dst1 (a stereo clip only): the launch is the split form — the left channel's samples land at d_dst, the right channel's at d_dst1
+bool wav_job_run(whisper_context & ctx, WavJob & job, float * d_dst, hipStream_t s, float * d_dst1 = nullptr);
 void free_wav(whisper_context & ctx);
+// the two-channel result of wmi_full_wav_channels (wav.cpp): every transcription call starts with channels_invalidate (full(), full_batch():
+// the result to come is no channels result until that call says so); channels_deselect: another view than the dialogue is being selected
+void channels_invalidate(whisper_context & ctx);
+void channels_deselect(whisper_context & ctx);
 // Speaker labels from the two channels (speaker.cpp; wmi_set_speaker): the context's tables of channel energies, one per stereo clip of the
 // last wmi_full_wav / wmi_full_long_wav / wmi_full_batch_wav / wmi_capture_full call made with a mode.
 //   speaker_begin      a call with `n_clips` clips starts: the mode and ratio in effect are taken (false: mode 0, nothing is touched)

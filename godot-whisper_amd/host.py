@@ -404,6 +404,29 @@ class SpeechToText:
             return []
         return self.collect_batch(len(made))
 
+    def transcribe_wav_channels(self, data: bytes, format: int, mix_rate: int, initial_prompt: str = "", audio_ctx: int = 0,
+                                interpolator_type: int = 2, params=None) -> list:
+        """A stereo asset with one voice per channel (wmi_full_wav_channels): both channels transcribed apart in one lock-step call.
+        -> the dialogue, a dictionary per segment in the order of the merged view: "channel" (0 left, 1 right), "index" (the segment's
+        place in that channel's result), t0, t1 (10 ms units), text.  Leaves last_channels (the two per-channel results in collect()'s
+        form), last_modes / last_langs / last_batch_windows per channel, and the dialogue view selected."""
+        self.last_channels = []
+        if not self.ctx:
+            return []
+        wav, _keep = self._wav(data, format, 1, mix_rate)
+        p = params if params is not None else self.full_params(initial_prompt, audio_ctx)
+        self.last_ret = self.lib.wmi_full_wav_channels(self.ctx, p, C.byref(wav), int(interpolator_type))
+        if self.last_ret != 0:
+            return []
+        self.last_channels = self.collect_batch(2)
+        n = self.lib.wmi_channels_select(self.ctx, -1)
+        assert n >= 0
+        rec, out = abi.wmi_channel_segment(), []
+        for i, (t0, t1, text) in enumerate(self.segments()):
+            assert self.lib.wmi_channels_get_segment(self.ctx, i, C.byref(rec)) == 0
+            out.append({"channel": rec.channel, "index": rec.index, "t0": t0, "t1": t1, "text": text})
+        return out
+
     def segments(self) -> list:
         """(t0, t1, text) of the segments the accessors show now (10 ms units)."""
         lib, ctx = self.lib, self.ctx
@@ -563,11 +586,16 @@ class AudioStreamToText(SpeechToText):
         return remove_special_characters(text)
 
     def get_text_wav(self, data: bytes, format: int, stereo, mix_rate: int, initial_prompt: str = "", interpolator_type: int = 2,
-                     long_form: bool = False, speaker_prefix: bool = False) -> str:
+                     long_form: bool = False, speaker_prefix: bool = False, channels: bool = False) -> str:
         """get_text on audio_stream.data / .format / .stereo / .mix_rate themselves: every sample is decoded, a stereo asset is folded
         and another rate resampled on the device — what the node's own loop (audio_stream_to_text.gd:40-46) gets wrong.
         speaker_prefix (a node made with speaker_labels, a stereo asset): "(speaker 0) " / "(speaker 1) " / "(speaker ?) " in front of
-        every segment's text, as whisper.cpp's --diarize prints it (examples/main/main.cpp:262-265)."""
+        every segment's text, as whisper.cpp's --diarize prints it (examples/main/main.cpp:262-265).
+        channels (a stereo asset with one voice per channel): the two channels are transcribed apart (transcribe_wav_channels) and the
+        dialogue joined with the same prefix per segment, the channel being the speaker."""
+        if channels:
+            return "".join("(speaker %d) " % s["channel"] + remove_special_characters(s["text"].decode("utf-8", errors="replace"))
+                           for s in self.transcribe_wav_channels(data, format, mix_rate, initial_prompt, 0, interpolator_type))
         if long_form:
             tokens = self.transcribe_wav_long(data, format, stereo, mix_rate, interpolator_type, self.full_params(initial_prompt, 0))
         else:

@@ -125,6 +125,20 @@ int main(int argc, char ** argv) {
         node.set_language(SpeechToText::English);
         const bool diarize = argc > 7 && std::string(argv[7]) == "--diarize";       // speaker labels from the two channels of a stereo asset
         if (diarize) node.set_speaker_labels(1);
+        if (argc > 7 && std::string(argv[7]) == "--channels") {                     // one voice per channel: the two channels transcribed apart
+            const auto dlg = node.transcribe_wav_channels(raw, language, mix_rate, "", audio_ctx, (SpeechToText::InterpolatorType) interp);
+            printf("{\"dialogue\": [");
+            for (size_t i = 0; i < dlg.size(); ++i) {
+                printf("%s{\"channel\": %d, \"index\": %d, \"t0\": %lld, \"t1\": %lld, \"text\": ", i ? ", " : "", dlg[i].channel, dlg[i].index,
+                       (long long) dlg[i].t0, (long long) dlg[i].t1);
+                json_string(dlg[i].text); printf("}");
+            }
+            printf("], \"channels\": [");
+            for (size_t c = 0; c < node.last_channels.size(); ++c) { if (c) printf(", "); json_transcription(node.last_channels[c]); }
+            printf("], \"text\": "); json_string(SpeechToText::dialogue_text(dlg));
+            printf(", \"ret\": %d}\n", node.last_return);
+            return 0;
+        }
         printf("{\"transcription\": ");
         json_transcription(node.transcribe_wav(raw, language, stereo != 0, mix_rate, "", audio_ctx, (SpeechToText::InterpolatorType) interp));
         if (diarize) {

@@ -246,6 +246,47 @@ Transcription SpeechToText::transcribe_wav(const std::vector<uint8_t> & data, in
     return collect();
 }
 
+std::vector<SpeechToText::DialogueSegment> SpeechToText::transcribe_wav_channels(const std::vector<uint8_t> & data, int format, int mix_rate,
+                                                                                const std::string & initial_prompt, int audio_ctx,
+                                                                                InterpolatorType interpolator_type) {
+    std::vector<DialogueSegment> out;
+    last_channels.clear();
+    const whisper_full_params whisper_params = make_params(initial_prompt, audio_ctx);
+    if (!context_instance) {
+        fprintf(stderr, "ERROR: Context instance is null\n");
+        return out;
+    }
+    static const uint8_t none = 0;
+    const wmi_wav wav = { data.empty() ? &none : data.data(), (long long) data.size(), format, 1, mix_rate, 0 };
+    const int ret = wmi_full_wav_channels(context_instance, whisper_params, &wav, (int) interpolator_type);
+    last_return = ret;
+    if (ret != 0) {
+        fprintf(stderr, "ERROR: Failed to process audio, returned %d\n", ret);
+        return out;
+    }
+    for (int c = 0; c < 2; ++c) {
+        if (wmi_channels_select(context_instance, c) < 0) return out;
+        last_channels.push_back(collect());
+    }
+    const int n = wmi_channels_select(context_instance, -1);         // the dialogue view stays selected
+    for (int i = 0; i < n; ++i) {
+        struct wmi_channel_segment rec;
+        if (wmi_channels_get_segment(context_instance, i, &rec) != 0) return std::vector<DialogueSegment>();
+        DialogueSegment s;
+        s.channel = rec.channel; s.index = rec.index;
+        s.t0 = whisper_full_get_segment_t0(context_instance, i); s.t1 = whisper_full_get_segment_t1(context_instance, i);
+        s.text = whisper_full_get_segment_text(context_instance, i);
+        out.push_back(std::move(s));
+    }
+    return out;
+}
+
+std::string SpeechToText::dialogue_text(const std::vector<DialogueSegment> & dialogue) {
+    std::string out;
+    for (const DialogueSegment & s : dialogue) out += std::string("(speaker ") + (s.channel == 0 ? "0" : "1") + ") " + s.text;
+    return out;
+}
+
 std::vector<Transcription> SpeechToText::transcribe_batch(const std::vector<std::vector<float>> & buffers,
                                                           const std::string & initial_prompt, int audio_ctx) {
     std::vector<Transcription> out;

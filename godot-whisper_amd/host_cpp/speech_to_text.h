@@ -106,6 +106,16 @@ public:
     // and another rate resampled to 16 kHz on the device; the node's own GDScript loop (addon/audio_stream_to_text.gd:40-46) does none of it.
     Transcription transcribe_wav(const std::vector<uint8_t> & data, int format, bool stereo, int mix_rate, const std::string & initial_prompt = "",
                                  int audio_ctx = 0, InterpolatorType interpolator_type = SRC_SINC_FASTEST);
+    // not in the reference: a STEREO AudioStreamWAV with one voice per channel (include/wmi_device.h: wmi_full_wav_channels) — the two
+    // channels transcribed apart in one lock-step call.  Returns the dialogue: a record per segment in the merged view's order (by start
+    // time, the left channel first on a tie), the channel being the speaker; last_channels has the two per-channel results.
+    // dialogue_text(): "(speaker 0) text" per segment joined, in diarized_text()'s format.
+    struct DialogueSegment { int channel = 0, index = 0; int64_t t0 = 0, t1 = 0; std::string text; };
+    std::vector<DialogueSegment> transcribe_wav_channels(const std::vector<uint8_t> & data, int format, int mix_rate,
+                                                         const std::string & initial_prompt = "", int audio_ctx = 0,
+                                                         InterpolatorType interpolator_type = SRC_SINC_FASTEST);
+    std::vector<Transcription> last_channels;
+    static std::string dialogue_text(const std::vector<DialogueSegment> & dialogue);
     // not in the reference: several buffers in lock-step on one GPU (include/wmi_device.h: wmi_full_batch); element c is
     // what transcribe(buffers[c], initial_prompt, audio_ctx) returns on a fresh context
     std::vector<Transcription> transcribe_batch(const std::vector<std::vector<float>> & buffers, const std::string & initial_prompt,

@@ -172,6 +172,11 @@ DEVICE_API = [
     ("wmi_full_batch_wav", C.c_int, [C.c_void_p, abi.whisper_full_params, C.POINTER(abi.wmi_wav), C.c_int, C.c_int]),
     ("wmi_selftest_wav_plan", C.c_int, [C.POINTER(abi.wmi_wav), C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     ("wmi_wav_stats", C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    ("wmi_wav_to_pcm_channels", C.c_int, [C.c_void_p, C.POINTER(abi.wmi_wav), C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+    ("wmi_full_wav_channels", C.c_int, [C.c_void_p, abi.whisper_full_params, C.POINTER(abi.wmi_wav), C.c_int]),
+    ("wmi_channels_select", C.c_int, [C.c_void_p, C.c_int]),
+    ("wmi_channels_get_segment", C.c_int, [C.c_void_p, C.c_int, C.POINTER(abi.wmi_channel_segment)]),
+    ("wmi_selftest_channels_merge", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     ("wmi_set_speaker", C.c_int, [C.c_void_p, C.c_int, C.c_double]),
     ("wmi_full_get_segment_speaker", C.c_int, [C.c_void_p, C.c_int, C.POINTER(abi.wmi_speaker)]),
     ("wmi_full_get_token_speaker", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(abi.wmi_speaker)]),

@@ -977,6 +977,50 @@ WHISPER_API int wmi_bench_channel_bins(int device, const struct wmi_wav * wav, i
 WHISPER_API int wmi_selftest_speaker_ranges(const void * bins, long long n_bins, const void * last2, int kind, long long n_frames, int rate,
                                             double ratio, const int64_t * t0, const int64_t * t1, int n_ranges, struct wmi_speaker * out);
 
+/* Stereo dialogues: the two channels of a stereo clip transcribed apart, in one lock-step call (one voice per channel — where both talk at
+ * once the fold of wmi_full_wav hands the decoder a mixture, and the energy rule above can only answer "?").
+ *   replaces: de-interleaving the asset on the host (in the node a GDScript loop per sample), two mono clips, wmi_full_batch_wav: two
+ *             conversion launches and no joint result.
+ * The definition, held bit for bit (tests/channels_ref.py), for a stereo clip of `frames` frames as the WAV calls count them:
+ *   ch[c][f]   the sample of channel c (0 left, 1 right) of frame f: s16 v / 32768, s8 signed v / 128, f32 as is — no fold
+ *   pcm[c]     mix_rate == 16000: ch[c].  Else wmi_resample(ch[c], mix_rate -> 16000, converter), bit for bit; both channels have the
+ *              count of that plan, the count wmi_wav_to_pcm reports for the clip
+ *   result     wmi_full_batch(ctx, params, { pcm[0], pcm[1] }, { n, n }, 2, on_device): chunk c is channel c
+ * On the device the bytes are uploaded once and ONE launch reads every frame once and writes both channels (csrc/k_wav.hip k_wav_split at
+ * 16 kHz; csrc/k_resample.hip k_resample_split otherwise: position, tap walk and interpolated coefficients computed once per output, two
+ * accumulator pairs).
+ *   wmi_wav_to_pcm_channels   the two channels' mono 16 kHz samples into dst0 / dst1 (host pointers, or device pointers with dst_on_device
+ *                       != 0; room for dst_capacity samples EACH); returns the count per channel.  Waits for the samples.  Errors as
+ *                       wmi_wav_to_pcm (also -1 for a NULL dst0 / dst1); -12 a mono clip (wmi_wav_speaker's code), decided behind the others.
+ *   wmi_full_wav_channels   the one split launch into two slices of a device buffer of the context, one wait, then wmi_full_batch on the
+ *                       two device pointers.  A conversion error e is returned as -100 + e (a mono clip: -112), otherwise exactly what
+ *                       wmi_full_batch returns for the definition's samples.  It takes the locks of wmi_full_batch_wav and, like it,
+ *                       carries no draft (an armed one is dropped).  The no-speech, token-DTW and grammar-device modes pass through as in
+ *                       wmi_full_batch.  wmi_set_speaker modes 1 and 2 are NOT served: the result carries no table, the speaker accessors
+ *                       answer -2 (each channel IS a speaker).  wmi_wav_stats afterwards: { n_bytes (+ the position table, once),
+ *                       frames, 2 n, 1 launch, microseconds }.  When the call returns 0 the dialogue view is selected.
+ *   wmi_channels_select   c = 0 / 1: the accessors read that channel, exactly as wmi_batch_select(ctx, c) (wmi_batch_chunk_mode,
+ *                       wmi_batch_lang_id and the windows per channel as there); c = -1: the dialogue view — copies of both channels'
+ *                       segments (text, tokens, times, DTW times untouched; nothing is shifted) in the order of a stable two-way merge by
+ *                       start time: while both channels have segments left, channel 0's next if its t0 <= channel 1's next's t0, else
+ *                       channel 1's; then the rest (csrc/channel_merge.h).  Its language id is channel 0's; it carries no window records
+ *                       (wmi_full_n_windows 0) and no speaker table.  Returns the segment count; -1 for another index, or when the last
+ *                       transcription call on the context was not wmi_full_wav_channels (every transcription call drops the view).
+ *   wmi_channels_get_segment   segment i of the dialogue view: { its channel, its index in that channel's result }.  0; -1 for a bad index
+ *                       or when the selected result is not the dialogue view.
+ *   wmi_selftest_channels_merge   host only, no context: the merge rule on two lists of start times; out_channel / out_index hold
+ *                       n_a + n_b entries, which is what it returns (-1: a negative count or a NULL pointer that is needed).
+ * Off unless called.  Not served: the capture session's frames, the long and the batch form per channel, more than two channels,
+ * suppressing what both microphones heard, energy tables on a channels result, interleaving below segment granularity. */
+struct wmi_channel_segment { int channel; int index; };
+WHISPER_API int wmi_wav_to_pcm_channels(struct whisper_context * ctx, const struct wmi_wav * wav, int converter, float * dst0, float * dst1,
+                                        int dst_capacity, int dst_on_device);
+WHISPER_API int wmi_full_wav_channels(struct whisper_context * ctx, struct whisper_full_params params, const struct wmi_wav * wav,
+                                      int converter);
+WHISPER_API int wmi_channels_select(struct whisper_context * ctx, int channel);
+WHISPER_API int wmi_channels_get_segment(struct whisper_context * ctx, int i, struct wmi_channel_segment * out);
+WHISPER_API int wmi_selftest_channels_merge(const int64_t * t0_a, int n_a, const int64_t * t0_b, int n_b, int * out_channel, int * out_index);
+
 /* Host worker pool self-test (no device needed): `reps` jobs of `n_tasks` tasks; returns reps * n_tasks * (n_tasks + 1) / 2
  * when every task of every job ran exactly once. */
 WHISPER_API int64_t wmi_selftest_pool(int n_tasks, int reps);
