@@ -202,6 +202,7 @@ class wmi_long_piece(C.Structure):  # include/wmi_device.h: one piece of the las
 
 
 WMI_WAV_S8, WMI_WAV_S16, WMI_WAV_F32 = 0, 1, 32  # include/wmi_device.h; 0 / 1 = AudioStreamWAV.FORMAT_8_BITS / FORMAT_16_BITS
+WMI_WAV_IMA_ADPCM = 2                            # AudioStreamWAV.FORMAT_IMA_ADPCM: served in mode 1 of wmi_set_wav_adpcm only
 
 
 class wmi_wav(C.Structure):  # include/wmi_device.h: the data bytes of an AudioStreamWAV and what they hold (wmi_wav_to_pcm, wmi_full_*_wav)
@@ -243,6 +244,7 @@ WINDOW_EMITTED, WINDOW_DROPPED, WINDOW_GATED = range(3)                         
 TOKEN_DTW_OFF, TOKEN_DTW_ON = range(2)                                           # wmi_set_token_dtw modes
 GRAMMAR_HOST, GRAMMAR_DEVICE = range(2)                                          # wmi_set_grammar_device modes
 SPEAKER_OFF, SPEAKER_SEGMENTS, SPEAKER_TOKENS = range(3)                         # wmi_set_speaker modes
+WAV_ADPCM_OFF, WAV_ADPCM_ON = range(2)                                           # wmi_set_wav_adpcm modes
 
 
 class whisper_model_loader(C.Structure):  # W/whisper.h:108-114

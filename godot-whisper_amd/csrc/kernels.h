@@ -198,6 +198,19 @@ bool wav_decode(int kind, const void * d_src, long long n_frames, float * out, h
 bool wav_split(int kind, const void * d_src, long long n_frames, float * out0, float * out1, hipStream_t st);
 void resample_launch_split(const ResamplePlan & pl, int kind, const void * d_src, long long n_in, float * out0, float * out1,
                            const float * d_coeffs, const int * d_pos, const double * d_frac, hipStream_t st);
+// IMA-ADPCM bytes of an AudioStreamWAV -> interleaved s16 (k_adpcm.hip; adpcm_map.h has the definition and the map algebra): two prefix
+// scans over chunks of ADPCM_CHUNK nibbles per channel, one chunk per thread, ADPCM_WG chunks per workgroup, the workgroups' partials walked
+// in tiles of ADPCM_PART_TILE — ADPCM_LAUNCHES launches on `st`, no workgroup waits for another.
+//   adpcm_plan          host only.  n_used: the bytes that hold frames (stereo: a trailing odd byte is ignored); frames = 2 * n_used / channels;
+//                       head: the bytes of chunk 0, in front of the source's first 16-byte boundary; out_skew: how many s16 the image should
+//                       start behind a 16-byte boundary for the full chunks to leave as 16-byte stores (any 2-byte aligned d_out is served)
+//   adpcm_scratch_bytes what d_scratch must hold for a source of n_bytes, wherever it lies (256-byte aligned)
+//   adpcm_decode        d_src: any byte address; d_out: room for frames * channels s16.  frames = 0 launches nothing.  false: launch error.
+constexpr int ADPCM_CHUNK = 32, ADPCM_WG = 256, ADPCM_PART_TILE = 256, ADPCM_LAUNCHES = 5;
+struct AdpcmPlan { long long n_used = 0, frames = 0, n_chunks = 0; int head = 0, out_skew = 0; };
+AdpcmPlan adpcm_plan(const void * d_src, long long n_bytes, bool stereo);
+size_t adpcm_scratch_bytes(long long n_bytes, bool stereo);
+bool adpcm_decode(const AdpcmPlan & p, const void * d_src, bool stereo, int16_t * d_out, void * d_scratch, hipStream_t st);
 // Channel energies per centisecond of a STEREO source (k_speaker.hip; speaker_ranges.h has the definition): one launch over n frames of
 // `kind` (SRC_F32_STEREO, SRC_S16_STEREO, SRC_S8_STEREO) at `rate` Hz writes nb = channel_bins_count(n, rate) pairs {left, right} of 8-byte
 // sums over frames [B(b), min(B(b + 1), n - 1)), B(b) = (b * rate) / 100, and behind them the two magnitudes of frame n - 1: (nb + 1) * 16

@@ -210,7 +210,10 @@ int wmi_wav_speaker(struct whisper_context * ctx, const struct wmi_wav * wav, co
     if (!ctx) return -1;
     try {
         int kind = 0; long long frames = 0;
-        if (const int e = clip_check(wav, &kind, &frames)) return e;
+        wmi_wav s16;                                                   // an IMA-ADPCM clip in mode 1 of wmi_set_wav_adpcm: the s16 clip its decode makes
+        const bool adpcm = wav && wav->format == 2 && ctx->wav_adpcm_mode;
+        if (adpcm) { if (const int e = adpcm_as_s16(wav, &s16)) return e; }
+        if (const int e = clip_check(adpcm ? &s16 : wav, &kind, &frames)) return e;
         if (n < 0 || (n > 0 && (!t0 || !t1 || !out))) return -1;
         Scope lk(ctx);
         if (!ctx->state || !compute_ready(*ctx, __func__)) return -2;
@@ -221,7 +224,8 @@ int wmi_wav_speaker(struct whisper_context * ctx, const struct wmi_wav * wav, co
         if (!table_reserve(t, kind, frames, wav->mix_rate)) return -3;
         const void * src = wav->data;
         const size_t fb = (size_t) (kind == spk::KIND_F32 ? 8 : kind == spk::KIND_S16 ? 4 : 2);
-        if (!wav->on_device && frames > 0) {
+        if (adpcm) { if (!adpcm_stage(*ctx, *wav, s, &src)) return -3; }
+        else if (!wav->on_device && frames > 0) {
             if (!HIP_OK(hipMalloc(&fr.d_bytes, (size_t) frames * fb)) ||
                 !HIP_OK(hipMemcpyAsync(fr.d_bytes, wav->data, (size_t) frames * fb, hipMemcpyHostToDevice, s))) return -3;
             src = fr.d_bytes;

@@ -9,6 +9,11 @@
 // form, and one launch — k_wav_decode at 16 kHz, else the resampler reading the packed frames (k_resample.hip in_frame<KIND>).  For
 // wmi_full_wav the launch writes into the staging area behind pcm_to_mel's padded image, on the log-mel's stream (DeviceState::pcm_job);
 // the long and the batch form convert into a buffer of the context and hand wmi_full_long / wmi_full_batch device pointers.
+//
+// IMA-ADPCM (format 2, wmi_set_wav_adpcm mode 1): the clip's bytes go up as they are, k::adpcm_decode (k_adpcm.hip: two prefix scans, five
+// launches) writes the interleaved s16 samples into a grow-only image of the context on the same stream, and the job goes on as the
+// device-resident WMI_WAV_S16 clip that image is — the conversion, the resampler's readers, the channel split and the speaker bins run as
+// they are.  Mode 0 refuses the format as before and allocates nothing.
 
 #include <algorithm>
 #include <climits>
@@ -18,6 +23,7 @@
 #include "wmi.h"
 #include "kernels.h"
 #include "channel_merge.h"
+#include "adpcm_map.h"
 
 namespace wmi {
 
@@ -26,6 +32,7 @@ struct WavPlan {
     int kind = 0, sample_bytes = 0;       // k::SrcKind
     long long frames = 0, n_out = 0;
     bool resample = false; k::ResamplePlan pl;
+    bool adpcm = false;                   // format 2 in mode 1: the bytes are decoded to s16 first; kind and frames are the decoded clip's
 };
 
 struct WavJob {
@@ -35,6 +42,7 @@ struct WavJob {
     bool mark_begin = true, mark_end = true;   // record the events of wmi_wav_stats' timer around this job
     bool used = false;
     int spk_slot = -1;                    // >= 0: the clip's table of channel energies (speaker.cpp) is queued behind its conversion
+    size_t s16_off = 0;                   // an ADPCM clip's place in the s16 image (in samples, a multiple of 8)
 };
 
 struct WavWork {
@@ -42,6 +50,9 @@ struct WavWork {
     int * d_pos = nullptr; double * d_frac = nullptr; size_t tab_cap = 0;
     float * d_out = nullptr; size_t out_cap = 0;                   // wmi_wav_to_pcm with a host dst
     float * d_pcm = nullptr; size_t pcm_cap = 0;                   // the samples of the long and the batch form
+    int16_t * d_s16 = nullptr; size_t s16_cap = 0;                 // ADPCM clips decoded: interleaved s16, one clip after the other (grow-only)
+    unsigned char * d_scan = nullptr; size_t scan_cap = 0;         // the scans' scratch (k::adpcm_scratch_bytes of the largest clip; the clips
+                                                                   // of a call decode one behind the other on one stream)
     hipEvent_t ev[2] = {nullptr, nullptr}; bool ev_pending = false;
     int64_t stats[5] = {0, 0, 0, 0, 0};
     // wmi_full_wav_channels: the dialogue view of the last call (copies of the two channels' segments in channel_merge.h's order) and where
@@ -59,7 +70,7 @@ struct Scope {                                                         // the co
 };
 
 // everything that can be said about a clip without a device
-WavPlan wav_plan(const wmi_wav * w, int converter, const char * who) {
+WavPlan wav_plan(const wmi_wav * w, int converter, const char * who, int adpcm_mode) {
     WavPlan p;
     if (!w || !w->data) { p.err = -1; return p; }
     bool stereo = w->stereo == 1;
@@ -67,14 +78,18 @@ WavPlan wav_plan(const wmi_wav * w, int converter, const char * who) {
         case WMI_WAV_S8:  p.kind = stereo ? k::SRC_S8_STEREO : k::SRC_S8_MONO; p.sample_bytes = 1; break;
         case WMI_WAV_S16: p.kind = stereo ? k::SRC_S16_STEREO : k::SRC_S16_MONO; p.sample_bytes = 2; break;
         case WMI_WAV_F32: p.kind = stereo ? k::SRC_F32_STEREO : k::SRC_F32_MONO; p.sample_bytes = 4; break;
-        case 2: case 3:
-            WMI_ERR("%s: format %d (%s) is not decoded here: its decoder is sequential and stays on the host\n", who, w->format,
-                    w->format == 2 ? "IMA-ADPCM" : "QOA");
+        case 2:
+            if (adpcm_mode) { p.adpcm = true; p.kind = stereo ? k::SRC_S16_STEREO : k::SRC_S16_MONO; p.sample_bytes = 1; break; }   // (no alignment asked)
+            [[fallthrough]];
+        case 3:
+            WMI_ERR("%s: format %d (%s) is not decoded here%s\n", who, w->format, w->format == 2 ? "IMA-ADPCM" : "QOA",
+                    w->format == 2 ? ": wmi_set_wav_adpcm turns its decode on" : "");
             p.err = -11; return p;
         default: p.err = -1; return p;
     }
     if (w->stereo < 0 || w->stereo > 1 || w->mix_rate <= 0 || w->n_bytes < 0) { p.err = -1; return p; }
-    p.frames = w->n_bytes / p.sample_bytes / (stereo ? 2 : 1);         // a trailing incomplete sample or frame is ignored
+    p.frames = p.adpcm ? adpcm::frames_of(w->n_bytes, stereo)          // two frames per byte (and channel)
+                       : w->n_bytes / p.sample_bytes / (stereo ? 2 : 1);   // a trailing incomplete sample or frame is ignored
     if (p.frames > INT_MAX) { p.err = -1; return p; }
     if (w->on_device && ((uintptr_t) w->data % (uintptr_t) p.sample_bytes)) { p.err = -1; return p; }
     if (w->mix_rate == RATE_16K) { p.n_out = p.frames; return p; }
@@ -126,15 +141,21 @@ size_t up16(size_t n) { return (n + 15) & ~(size_t) 15; }
 
 // room for the jobs' bytes and position tables, each job's place written into it; resets the counters of wmi_wav_stats
 bool reserve_jobs(WavWork & w, WavJob * jobs, int n) {
-    size_t bytes = 0, tab = 0;
+    size_t bytes = 0, tab = 0, s16 = 0, scan = 0;
     for (int i = 0; i < n; ++i) {
         WavJob & j = jobs[i];
         if (j.plan.frames <= 0 || j.plan.n_out <= 0) continue;
+        if (j.plan.adpcm) {                                                // (+ 8: the image may start up to 6 samples behind its place, adpcm_plan's out_skew)
+            const bool stereo = j.wav->stereo == 1;
+            j.s16_off = s16; s16 += ((size_t) j.plan.frames * (stereo ? 2 : 1) + 8 + 7) & ~(size_t) 7;
+            scan = std::max(scan, k::adpcm_scratch_bytes(j.wav->n_bytes, stereo));
+        }
         if (!j.wav->on_device) { j.bytes_off = bytes; bytes += up16((size_t) j.wav->n_bytes); }
         if (j.plan.resample && j.plan.pl.need_table) { j.tab_off = tab; tab += (size_t) j.plan.n_out; }
     }
     memset(w.stats, 0, sizeof(w.stats)); w.ev_pending = false;
-    return reserve(w.d_bytes, w.bytes_cap, bytes, 4096) && reserve_tables(w, tab);
+    return reserve(w.d_bytes, w.bytes_cap, bytes, 4096) && reserve_tables(w, tab) &&
+           reserve(w.d_s16, w.s16_cap, s16, 4096) && reserve(w.d_scan, w.scan_cap, scan, 4096);      // (nothing asked: nothing allocated)
 }
 
 // the tables of a call that takes a speaker mode (wmi_set_speaker): one per stereo clip that is converted; false: out of memory
@@ -166,6 +187,14 @@ bool wav_job_run(whisper_context & ctx, WavJob & job, float * d_dst, hipStream_t
             HIP_TRY(hipMemcpyAsync(d, job.wav->data, (size_t) job.wav->n_bytes, hipMemcpyHostToDevice, s));
             w->stats[0] += job.wav->n_bytes;
             src = d;
+        }
+        if (p.adpcm) {                                                     // bytes -> the s16 image; from here on the clip is that image
+            const bool stereo = job.wav->stereo == 1;
+            const k::AdpcmPlan ap = k::adpcm_plan(src, job.wav->n_bytes, stereo);
+            int16_t * img = w->d_s16 + job.s16_off + ap.out_skew;
+            if (!k::adpcm_decode(ap, src, stereo, img, w->d_scan, s)) return false;
+            w->stats[3] += k::ADPCM_LAUNCHES;
+            src = img;
         }
         if (!p.resample) {
             if (!(d_dst1 ? k::wav_split(p.kind, src, p.frames, d_dst, d_dst1, s) : k::wav_decode(p.kind, src, p.frames, d_dst, s))) return false;
@@ -206,10 +235,42 @@ bool wav_job_run(whisper_context & ctx, WavJob & job, float * d_dst, hipStream_t
 void free_wav(whisper_context & ctx) {
     WavWork * w = ctx.wav;
     if (!w) return;
-    for (void * p : { (void *) w->d_bytes, (void *) w->d_pos, (void *) w->d_frac, (void *) w->d_out, (void *) w->d_pcm }) if (p) (void) hipFree(p);
+    for (void * p : { (void *) w->d_bytes, (void *) w->d_pos, (void *) w->d_frac, (void *) w->d_out, (void *) w->d_pcm, (void *) w->d_s16, (void *) w->d_scan }) if (p) (void) hipFree(p);
     for (hipEvent_t e : w->ev) if (e) (void) hipEventDestroy(e);
     delete w;
     ctx.wav = nullptr;
+}
+
+int adpcm_as_s16(const wmi_wav * w, wmi_wav * s16) {
+    if (!w || !w->data || w->format != 2 || w->stereo < 0 || w->stereo > 1 || w->mix_rate <= 0 || w->n_bytes < 0) return -1;   // wav_plan's checks; any rate
+    const long long frames = adpcm::frames_of(w->n_bytes, w->stereo == 1);
+    if (frames > INT_MAX) return -1;
+    *s16 = wmi_wav{ w->data, frames * (w->stereo == 1 ? 4 : 2), WMI_WAV_S16, w->stereo, w->mix_rate, 0 };
+    return 0;
+}
+
+bool adpcm_stage(whisper_context & ctx, const wmi_wav & wav, hipStream_t s, const void ** d_s16) {
+    WavWork * w = work(ctx);
+    if (!w) return false;
+    WavJob job; job.wav = &wav;
+    job.plan.adpcm = true;
+    job.plan.frames = job.plan.n_out = adpcm::frames_of(wav.n_bytes, wav.stereo == 1);     // (n_out: reserve_jobs skips a clip without results)
+    if (!reserve_jobs(*w, &job, 1)) return false;
+    *d_s16 = nullptr;
+    if (job.plan.frames <= 0) return true;
+    const void * src = wav.data;
+    if (!wav.on_device) {
+        HIP_TRY(hipMemcpyAsync(w->d_bytes, wav.data, (size_t) wav.n_bytes, hipMemcpyHostToDevice, s));
+        w->stats[0] += wav.n_bytes;
+        src = w->d_bytes;
+    }
+    const bool stereo = wav.stereo == 1;
+    const k::AdpcmPlan ap = k::adpcm_plan(src, wav.n_bytes, stereo);
+    int16_t * img = w->d_s16 + ap.out_skew;
+    if (!k::adpcm_decode(ap, src, stereo, img, w->d_scan, s)) return false;
+    w->stats[1] += job.plan.frames; w->stats[3] += k::ADPCM_LAUNCHES;
+    *d_s16 = img;
+    return true;
 }
 
 void channels_invalidate(whisper_context & ctx) { if (ctx.wav) ctx.wav->ch.valid = ctx.wav->ch.shown = false; }
@@ -219,8 +280,8 @@ void channels_deselect(whisper_context & ctx) { if (ctx.wav) ctx.wav->ch.shown =
 namespace {
 
 // a stereo clip's plan for the two-channel calls; a mono clip is -12 (wmi_wav_speaker's code), behind every other conversion error
-WavPlan channels_plan(const wmi_wav * w, int converter, const char * who) {
-    WavPlan p = wav_plan(w, converter, who);
+WavPlan channels_plan(const wmi_wav * w, int converter, const char * who, int adpcm_mode) {
+    WavPlan p = wav_plan(w, converter, who, adpcm_mode);
     if (!p.err && w->stereo != 1) p.err = -12;
     return p;
 }
@@ -264,7 +325,7 @@ extern "C" {
 
 int wmi_selftest_wav_plan(const struct wmi_wav * wav, int converter, long long * frames, long long * n_out) {
     try {
-        const WavPlan p = wav_plan(wav, converter, __func__);
+        const WavPlan p = wav_plan(wav, converter, __func__, 0);          // (no context, no mode: format 2 is refused)
         if (p.err) return p.err;
         if (frames) *frames = p.frames;
         if (n_out) *n_out = p.n_out;
@@ -272,11 +333,144 @@ int wmi_selftest_wav_plan(const struct wmi_wav * wav, int converter, long long *
     } catch (...) { return -3; }
 }
 
+int wmi_set_wav_adpcm(struct whisper_context * ctx, int on) {
+    if (!ctx) return -2;
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    const int prev = ctx->wav_adpcm_mode;
+    ctx->wav_adpcm_mode = on ? 1 : 0;
+    return prev;
+}
+
+int wmi_selftest_adpcm_plan(const struct wmi_wav * wav, int converter, long long * frames, long long * n_out) {
+    try {
+        const WavPlan p = wav_plan(wav, converter, __func__, 1);
+        if (p.err) return p.err;
+        if (frames) *frames = p.frames;
+        if (n_out) *n_out = p.n_out;
+        return 0;
+    } catch (...) { return -3; }
+}
+
+int wmi_selftest_adpcm_shape(int * out5) {
+    if (!out5) return -1;
+    out5[0] = k::ADPCM_CHUNK; out5[1] = 64; out5[2] = k::ADPCM_WG; out5[3] = k::ADPCM_PART_TILE; out5[4] = k::ADPCM_LAUNCHES;
+    return 0;
+}
+
+int wmi_selftest_adpcm_host(const unsigned char * bytes, long long n_bytes, int stereo, int16_t * out_s16, long long cap_frames) {
+    if (n_bytes < 0 || stereo < 0 || stereo > 1 || (n_bytes > 0 && !bytes) || cap_frames < 0) return -1;
+    const int nch = stereo ? 2 : 1;
+    const long long frames = adpcm::frames_of(n_bytes, stereo == 1);
+    if (frames > INT_MAX) return -1;
+    if (frames > cap_frames) return -4;
+    if (frames > 0 && !out_s16) return -1;
+    for (int c = 0; c < nch; ++c) {                                        // the sequential loop: one stream per channel from (0, 0)
+        int predictor = 0, index = 0;
+        for (long long i = 0; i < frames; ++i) {
+            adpcm::decode_nibble(adpcm::nibble_at(bytes, nch, c, i), predictor, index);
+            out_s16[i * nch + c] = (int16_t) predictor;
+        }
+    }
+    return (int) frames;
+}
+
+int wmi_selftest_adpcm_maps(const unsigned char * nibbles, long long n, int chunk, int32_t * out_predictor, int32_t * out_index, long long cap) {
+    if (n < 0 || chunk < 1 || (n > 0 && !nibbles) || cap < 0) return -1;
+    try {
+        const long long chunks = (n + chunk - 1) / chunk;
+        if (chunks + 1 > cap) return -4;
+        if (!out_predictor || !out_index) return -1;
+        for (long long i = 0; i < n; ++i) if (nibbles[i] > 15) return -1;
+        // the plan of k_adpcm.hip with a sequential scan: the chunks' index maps, their prefix applied to 0 ...
+        std::vector<adpcm::IdxMap> im((size_t) chunks);
+        for (long long j = 0; j < chunks; ++j) {
+            adpcm::IdxMap m = adpcm::idx_identity();
+            for (long long i = j * chunk; i < std::min(n, (j + 1) * chunk); ++i) m = adpcm::compose(m, adpcm::idx_nibble(nibbles[i]));
+            im[(size_t) j] = m;
+        }
+        adpcm::IdxMap pi = adpcm::idx_identity();
+        for (long long j = 0; j <= chunks; ++j) { out_index[j] = adpcm::apply(pi, 0); if (j < chunks) pi = adpcm::compose(pi, im[(size_t) j]); }
+        // ... then, from every chunk's entry index, the chunks' predictor maps, and their prefix applied to 0
+        adpcm::PredMap pp = adpcm::pred_identity();
+        for (long long j = 0; j <= chunks; ++j) {
+            out_predictor[j] = adpcm::apply(pp, 0);
+            if (j == chunks) break;
+            adpcm::PredMap m = adpcm::pred_identity();
+            int index = out_index[j];
+            for (long long i = j * chunk; i < std::min(n, (j + 1) * chunk); ++i) {
+                m = adpcm::compose(m, adpcm::pred_nibble(index, nibbles[i]));
+                index = adpcm::apply(adpcm::idx_nibble(nibbles[i]), index);
+            }
+            pp = adpcm::compose(pp, m);
+        }
+        return (int) std::min<long long>(chunks, INT_MAX);
+    } catch (...) { return -3; }
+}
+
+namespace {
+
+// the kernels alone on `device`: source at `offset` bytes into an allocation, the image with a guard behind it; iters > 0: timed, no copy back
+int adpcm_run(int device, const unsigned char * bytes, long long n_bytes, int stereo, int offset, int16_t * out_s16, long long cap_frames,
+              long long * frames_out, int iters, float * ms) {
+    if (device < 0 || n_bytes < 0 || stereo < 0 || stereo > 1 || (n_bytes > 0 && !bytes) || offset < 0 || offset > 4096 || cap_frames < 0) return -1;
+    const bool st2 = stereo == 1;
+    const long long frames = adpcm::frames_of(n_bytes, st2);
+    if (frames > INT_MAX) return -1;
+    if (frames_out) *frames_out = frames;
+    if (!ms && frames > cap_frames) return -4;
+    if (frames == 0) return ms ? -1 : 0;
+    if (!ms && !out_s16) return -1;
+    if (!HIP_OK(hipSetDevice(device))) return -2;
+    constexpr size_t GUARD = 256;
+    const size_t n_s16 = (size_t) frames * (st2 ? 2 : 1), img_bytes = 16 + n_s16 * 2, total = img_bytes + GUARD;
+    void * d_src = nullptr, * d_img = nullptr, * d_scan = nullptr; hipStream_t s = nullptr; hipEvent_t ev[2] = {nullptr, nullptr};
+    struct Free { void *& a; void *& b; void *& c; hipStream_t & s; hipEvent_t * e;
+                  ~Free() { for (int i = 0; i < 2; ++i) if (e[i]) (void) hipEventDestroy(e[i]); if (s) (void) hipStreamDestroy(s);
+                            for (void * p : { a, b, c }) if (p) (void) hipFree(p); } } fr{d_src, d_img, d_scan, s, ev};
+    if (!HIP_OK(hipMalloc(&d_src, (size_t) n_bytes + (size_t) offset)) || !HIP_OK(hipMalloc(&d_img, total)) ||
+        !HIP_OK(hipMalloc(&d_scan, k::adpcm_scratch_bytes(n_bytes, st2))) || !HIP_OK(hipStreamCreate(&s))) return -3;
+    if (!HIP_OK(hipMemsetAsync(d_img, 0xA5, total, s)) ||
+        !HIP_OK(hipMemcpyAsync((unsigned char *) d_src + offset, bytes, (size_t) n_bytes, hipMemcpyHostToDevice, s))) return -3;
+    const unsigned char * src = (const unsigned char *) d_src + offset;
+    const k::AdpcmPlan ap = k::adpcm_plan(src, n_bytes, st2);
+    int16_t * img = (int16_t *) d_img + ap.out_skew;                       // (the guard starts right behind the last sample)
+    if (ms) {
+        if (!HIP_OK(hipEventCreate(&ev[0])) || !HIP_OK(hipEventCreate(&ev[1]))) return -3;
+        for (int i = 0; i < iters; ++i)
+            if (!HIP_OK(hipEventRecord(ev[0], s)) || !k::adpcm_decode(ap, src, st2, img, d_scan, s) || !HIP_OK(hipEventRecord(ev[1], s)) ||
+                !HIP_OK(hipEventSynchronize(ev[1])) || !HIP_OK(hipEventElapsedTime(ms + i, ev[0], ev[1]))) return -3;
+        return 0;
+    }
+    std::vector<unsigned char> host(total);
+    bool ok = k::adpcm_decode(ap, src, st2, img, d_scan, s);
+    ok = ok && HIP_OK(hipMemcpyAsync(host.data(), d_img, total, hipMemcpyDeviceToHost, s));
+    ok = HIP_OK(hipStreamSynchronize(s)) && ok;
+    if (!ok || !HIP_OK(hipGetLastError())) return -3;
+    const size_t first = (size_t) ap.out_skew * 2, last = first + n_s16 * 2;
+    for (size_t i = 0; i < total; ++i) if ((i < first || i >= last) && host[i] != 0xA5) return -5;       // written in front of or behind the image
+    memcpy(out_s16, host.data() + first, n_s16 * 2);
+    return 0;
+}
+
+}  // namespace
+
+int wmi_selftest_adpcm_decode(int device, const unsigned char * bytes, long long n_bytes, int stereo, int src_byte_offset, int16_t * out_s16,
+                              long long cap_frames, long long * frames) {
+    try { return adpcm_run(device, bytes, n_bytes, stereo, src_byte_offset, out_s16, cap_frames, frames, 0, nullptr); }
+    catch (...) { return -3; }
+}
+
+int wmi_bench_adpcm_decode(int device, const unsigned char * bytes, long long n_bytes, int stereo, int src_byte_offset, int iters, float * ms) {
+    if (iters < 1 || !ms) return -1;
+    try { return adpcm_run(device, bytes, n_bytes, stereo, src_byte_offset, nullptr, 0, nullptr, iters, ms); }
+    catch (...) { return -3; }
+}
+
 int wmi_wav_to_pcm(struct whisper_context * ctx, const struct wmi_wav * wav, int converter, float * dst, int dst_capacity, int dst_on_device) {
     if (!ctx || !ctx->state) return -1;
     try {
         WavJob job; job.wav = wav; job.converter = converter;
-        job.plan = wav_plan(wav, converter, __func__);
+        job.plan = wav_plan(wav, converter, __func__, ctx->wav_adpcm_mode);
         if (job.plan.err) return job.plan.err;
         if (!dst || dst_capacity < 0) return -1;
         if (job.plan.n_out > dst_capacity) return -4;
@@ -300,7 +494,7 @@ int wmi_full_wav(struct whisper_context * ctx, struct whisper_full_params params
     if (!ctx || !ctx->state) return -101;
     try {
         WavJob job; job.wav = wav; job.converter = converter;
-        job.plan = wav_plan(wav, converter, __func__);
+        job.plan = wav_plan(wav, converter, __func__, ctx->wav_adpcm_mode);
         if (job.plan.err) return -100 + job.plan.err;
         Scope lk(ctx);                                                     // wmi_full_device_pcm's locks
         if (!compute_ready(*ctx, __func__)) return -102;
@@ -323,7 +517,7 @@ int wmi_full_long_wav(struct whisper_context * ctx, struct whisper_full_params p
     try {
         { Scope lk(ctx); DraftRefuse no_draft(ctx->state.get()); }         // (no draft is carried: dropped whatever the call returns)
         WavJob job; job.wav = wav; job.converter = converter;
-        job.plan = wav_plan(wav, converter, __func__);
+        job.plan = wav_plan(wav, converter, __func__, ctx->wav_adpcm_mode);
         if (job.plan.err) return -100 + job.plan.err;
         Scope lk(ctx);                                                     // wmi_full_long's locks
         if (!compute_ready(*ctx, __func__)) return -102;
@@ -351,7 +545,7 @@ int wmi_full_batch_wav(struct whisper_context * ctx, struct whisper_full_params 
         size_t total = 0;
         for (int i = 0; i < n; ++i) {
             jobs[i].wav = wavs + i; jobs[i].converter = converter;
-            jobs[i].plan = wav_plan(wavs + i, converter, __func__);
+            jobs[i].plan = wav_plan(wavs + i, converter, __func__, ctx->wav_adpcm_mode);
             if (jobs[i].plan.err) return -100 + jobs[i].plan.err;
             jobs[i].mark_begin = i == 0; jobs[i].mark_end = i == n - 1;
             off[i] = total; total += ((size_t) jobs[i].plan.n_out + 63) & ~(size_t) 63;
@@ -380,7 +574,7 @@ int wmi_wav_to_pcm_channels(struct whisper_context * ctx, const struct wmi_wav *
     if (!ctx || !ctx->state) return -1;
     try {
         WavJob job; job.wav = wav; job.converter = converter;
-        job.plan = channels_plan(wav, converter, __func__);
+        job.plan = channels_plan(wav, converter, __func__, ctx->wav_adpcm_mode);
         if (job.plan.err) return job.plan.err;
         if (!dst0 || !dst1 || dst_capacity < 0) return -1;
         if (job.plan.n_out > dst_capacity) return -4;
@@ -406,7 +600,7 @@ int wmi_full_wav_channels(struct whisper_context * ctx, struct whisper_full_para
     try {
         { Scope lk(ctx); DraftRefuse no_draft(ctx->state.get()); }         // (no draft is carried: dropped whatever the call returns)
         WavJob job; job.wav = wav; job.converter = converter;
-        job.plan = channels_plan(wav, converter, __func__);
+        job.plan = channels_plan(wav, converter, __func__, ctx->wav_adpcm_mode);
         if (job.plan.err) return -100 + job.plan.err;
         Scope lk(ctx);                                                     // wmi_full_batch's locks
         if (!compute_ready(*ctx, __func__)) return -102;

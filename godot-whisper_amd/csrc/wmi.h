@@ -437,6 +437,11 @@ struct WavJob;
 // d_dst1 (a stereo clip only): the launch is the split form — the left channel's samples land at d_dst, the right channel's at d_dst1
 bool wav_job_run(whisper_context & ctx, WavJob & job, float * d_dst, hipStream_t s, float * d_dst1 = nullptr);
 void free_wav(whisper_context & ctx);
+// IMA-ADPCM clips (wmi_set_wav_adpcm mode 1) for a call outside wav.cpp (wmi_wav_speaker):
+//   adpcm_as_s16   host only: the clip's argument errors (-1), else *s16 = the WMI_WAV_S16 clip its decode makes (data: the ADPCM bytes still)
+//   adpcm_stage    upload (a host source) and decode on `s` into the context's image: *d_s16 = the interleaved samples (null: no frames).  No wait.
+int adpcm_as_s16(const wmi_wav * w, wmi_wav * s16);
+bool adpcm_stage(whisper_context & ctx, const wmi_wav & wav, hipStream_t s, const void ** d_s16);
 // the two-channel result of wmi_full_wav_channels (wav.cpp): every transcription call starts with channels_invalidate (full(), full_batch():
 // the result to come is no channels result until that call says so); channels_deselect: another view than the dialogue is being selected
 void channels_invalidate(whisper_context & ctx);
@@ -484,6 +489,7 @@ struct whisper_context {
     wmi::WavWork * wav = nullptr;       // wmi_wav_* / wmi_full_*_wav (wav.cpp): made by the first such call, null in a context that never makes one
     // wmi_set_speaker: 0 off, 1 a label per segment, 2 per token too; read at the start of every transcription call that serves it (speaker.cpp)
     int            speaker_mode = 0; double speaker_ratio = 1.1;
+    int            wav_adpcm_mode = 0;  // wmi_set_wav_adpcm: 0 format 2 is refused, 1 decoded on the device; read where a WAV call plans its clips
     wmi::SpeakerWork * spk = nullptr;   // made by the first call with a mode (or wmi_wav_speaker), null in a context that never makes one
     // guards what belongs to the CONTEXT: the lock-step work set (wmi_full_batch), the DSP scratch, state creation, the probes.  Compute
     // on a state takes the state's own lock (wmi::State::mu), not this one.

@@ -38,7 +38,8 @@ class SpeechToText:
     """One `whisper_context` per node (src/speech_to_text.h:135); not re-entrant."""
 
     def __init__(self, lib: C.CDLL, settings: dict | None = None, no_speech: int = 0, token_dtw=False, grammar=None,
-                 grammar_penalty: float = 100.0, grammar_device: bool = False, speaker_labels=False, speaker_ratio: float = 1.1):
+                 grammar_penalty: float = 100.0, grammar_device: bool = False, speaker_labels=False, speaker_ratio: float = 1.1,
+                 wav_adpcm: bool = False):
         """grammar: rules in the format of abi.make_grammar (a list of rules, each a list of (type, value) without the closing END; rule 0
         is the start rule) — every full_params() then carries them with grammar_penalty; None: no grammar.
         grammar_device (product library only, include/wmi_device.h wmi_set_grammar_device): True — the grammar's reject masks and the
@@ -51,7 +52,10 @@ class SpeechToText:
         speaker_labels (product library only, include/wmi_device.h wmi_set_speaker): True — the stereo clips of transcribe_wav*, and a
         capture session's steps, leave a dictionary per segment in last_speakers (t0, t1, text, "speaker" 0 / 1 / None, "channel_energy"
         (left, right)); "tokens" — with params.token_timestamps every token dictionary gains "speaker" as well.  speaker_ratio: how much
-        louder a channel must be (whisper.cpp --diarize: 1.1)."""
+        louder a channel must be (whisper.cpp --diarize: 1.1).
+        wav_adpcm (product library only, include/wmi_device.h wmi_set_wav_adpcm): True — transcribe_wav, transcribe_wav_long,
+        transcribe_wav_batch, transcribe_wav_channels and AudioStreamToText.get_text_wav accept format 2 (AudioStreamWAV.FORMAT_IMA_ADPCM):
+        the compressed bytes are decoded on the device.  False — format 2 is refused (last_ret -111), as ever."""
         self.lib = lib
         self.ctx = None
         self.no_speech = int(no_speech)
@@ -60,6 +64,8 @@ class SpeechToText:
         self.speaker_labels, self.speaker_ratio = speaker_labels, float(speaker_ratio)
         self.last_speakers = []
         self._speaker_called = False
+        self.wav_adpcm = bool(wav_adpcm)
+        self._adpcm_called = False
         self.grammar_penalty = float(grammar_penalty)
         self._grammar = None
         self.set_grammar(grammar, grammar_penalty)
@@ -85,6 +91,15 @@ class SpeechToText:
         self.set_token_dtw(self.token_dtw)
         self.set_grammar_device(self.grammar_device)
         self.set_speaker_labels(self.speaker_labels, self.speaker_ratio)
+        self.set_wav_adpcm(self.wav_adpcm)
+
+    def set_wav_adpcm(self, on: bool) -> int:
+        """The context's IMA-ADPCM mode from the next WAV call on; returns the previous mode (0 without a context)."""
+        self.wav_adpcm = bool(on)
+        if not self.ctx or not (on or self._adpcm_called):                # (a node that never asks for the mode never makes the call)
+            return 0
+        self._adpcm_called = True
+        return self.lib.wmi_set_wav_adpcm(self.ctx, abi.WAV_ADPCM_ON if on else abi.WAV_ADPCM_OFF)
 
     def set_speaker_labels(self, labels, ratio: float = 1.1) -> int:
         """The context's speaker mode from the next transcription call on (False, True or "tokens"); returns the previous mode (0
@@ -351,7 +366,8 @@ class SpeechToText:
         return out
 
     # -- an AudioStreamWAV as it is (product library only: include/wmi_device.h wmi_full_wav & co.): `data` are the asset's bytes, 8 or
-    #    16 bit (AudioStreamWAV.FORMAT_8_BITS = 0 / FORMAT_16_BITS = 1; abi.WMI_WAV_F32 for f32), mono or stereo, at its own mix rate.
+    #    16 bit (AudioStreamWAV.FORMAT_8_BITS = 0 / FORMAT_16_BITS = 1; abi.WMI_WAV_F32 for f32; FORMAT_IMA_ADPCM = 2 with wav_adpcm),
+    #    mono or stereo, at its own mix rate.
     #    The reference node decodes them in a GDScript loop as if they were 16 kHz mono (audio_stream_to_text.gd:40-46).
     @staticmethod
     def _wav(data, format: int, stereo, mix_rate: int):

@@ -123,9 +123,11 @@ int main(int argc, char ** argv) {
         int stereo = 0, mix_rate = 16000, interp = SpeechToText::SRC_SINC_FASTEST;
         sscanf(prompt.c_str(), "%d,%d,%d", &stereo, &mix_rate, &interp);
         node.set_language(SpeechToText::English);
-        const bool diarize = argc > 7 && std::string(argv[7]) == "--diarize";       // speaker labels from the two channels of a stereo asset
+        const auto has = [&](const char * flag) { for (int i = 7; i < argc; ++i) if (std::string(argv[i]) == flag) return true; return false; };
+        const bool diarize = has("--diarize");                                      // speaker labels from the two channels of a stereo asset
         if (diarize) node.set_speaker_labels(1);
-        if (argc > 7 && std::string(argv[7]) == "--channels") {                     // one voice per channel: the two channels transcribed apart
+        if (has("--adpcm")) node.set_wav_adpcm(true);                               // format 2 (FORMAT_IMA_ADPCM) is decoded on the device
+        if (has("--channels")) {                     // one voice per channel: the two channels transcribed apart
             const auto dlg = node.transcribe_wav_channels(raw, language, mix_rate, "", audio_ctx, (SpeechToText::InterpolatorType) interp);
             printf("{\"dialogue\": [");
             for (size_t i = 0; i < dlg.size(); ++i) {

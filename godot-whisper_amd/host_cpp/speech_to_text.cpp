@@ -32,6 +32,14 @@ void SpeechToText::set_language_model(const uint8_t * data, size_t size) {   // 
     if (context_instance && token_dtw) (void) wmi_set_token_dtw(context_instance, 1, token_dtw_pairs.data(), (int) token_dtw_pairs.size() / 2);
     if (context_instance && grammar_device) (void) wmi_set_grammar_device(context_instance, 1);
     if (context_instance && speaker_mode) (void) wmi_set_speaker(context_instance, speaker_mode, speaker_ratio);
+    if (context_instance && wav_adpcm) (void) wmi_set_wav_adpcm(context_instance, 1);
+}
+
+bool SpeechToText::set_wav_adpcm(bool on) {
+    const bool prev = wav_adpcm;
+    wav_adpcm = on;
+    if (context_instance) (void) wmi_set_wav_adpcm(context_instance, on ? 1 : 0);
+    return prev;
 }
 
 int SpeechToText::set_speaker_labels(int mode, double ratio) {

@@ -78,6 +78,10 @@ public:
     // result, empty where it carries none (mode 0, a mono asset, another call); diarized_text(): main.cpp's "(speaker 0) text" lines joined.
     int  set_speaker_labels(int mode, double ratio = 1.1);
     std::vector<SegmentSpeaker> speakers() const;
+    // not in the reference: AudioStreamWAV.FORMAT_IMA_ADPCM (format 2) for transcribe_wav / transcribe_wav_channels, decoded on the device
+    // (include/wmi_device.h wmi_set_wav_adpcm); off: format 2 is refused (last_return -111).  Kept across set_language_model.  Returns the
+    // previous setting.
+    bool set_wav_adpcm(bool on);
     std::string diarized_text() const;
     // not in the reference: a grammar for every later transcription (whisper_full_params.grammar_rules: rule 0 is the start rule, each rule
     // without its closing END element; an empty list: none), and where it is evaluated (include/wmi_device.h wmi_set_grammar_device:
@@ -148,6 +152,7 @@ protected:
     int no_speech = 0;
     bool token_dtw = false; std::vector<int32_t> token_dtw_pairs;
     int speaker_mode = 0; double speaker_ratio = 1.1;
+    bool wav_adpcm = false;
     bool grammar_device = false; float grammar_penalty = 100.0f;
     std::vector<std::vector<whisper_grammar_element>> grammar_rules;     // each closed by an END element
     std::vector<const whisper_grammar_element *> grammar_ptrs;

@@ -186,6 +186,14 @@ DEVICE_API = [
     ("wmi_bench_channel_bins", C.c_int, [C.c_int, C.POINTER(abi.wmi_wav), C.c_int, C.POINTER(C.c_float)]),
     ("wmi_selftest_speaker_ranges", C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_longlong, C.c_int, C.c_double, C.c_void_p,
                                               C.c_void_p, C.c_int, C.POINTER(abi.wmi_speaker)]),
+    ("wmi_set_wav_adpcm", C.c_int, [C.c_void_p, C.c_int]),
+    ("wmi_selftest_adpcm_plan", C.c_int, [C.POINTER(abi.wmi_wav), C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
+    ("wmi_selftest_adpcm_shape", C.c_int, [C.POINTER(C.c_int)]),
+    ("wmi_selftest_adpcm_decode", C.c_int, [C.c_int, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_longlong,
+                                            C.POINTER(C.c_longlong)]),
+    ("wmi_selftest_adpcm_host", C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_longlong]),
+    ("wmi_selftest_adpcm_maps", C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_longlong]),
+    ("wmi_bench_adpcm_decode", C.c_int, [C.c_int, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)]),
 ]
 
 _lib = None

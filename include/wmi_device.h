@@ -896,14 +896,14 @@ WHISPER_API int wmi_selftest_draft_logits(struct whisper_context * ctx, float * 
  *                       launch (by stream events; this call waits for them) }.  All zero on a context that never made such a call.
  * Conversion errors, every one decided before the device is touched: -1 a NULL pointer, an unknown format, stereo outside 0 / 1, a
  * non-positive rate, negative bytes, more frames than an int holds, a device pointer that is not sample-aligned, a converter outside
- * 0 - 4; -11 formats 2 and 3 (IMA-ADPCM, QOA: sequential decoders that stay on the host; logged); -10 converter 0; -2 the context cannot
+ * 0 - 4; -11 formats 2 and 3 (IMA-ADPCM unless wmi_set_wav_adpcm turns it on, QOA: decoded on the host; logged); -10 converter 0; -2 the context cannot
  * compute; -3 a device error; -4 dst_capacity below the result count.  A converter error of the plan (ratio outside [1/256, 256],
  * SRC_LINEAR upsampling one frame) gives 0 samples, as wmi_resample.  The wmi_full_*_wav calls return a conversion error e as -100 + e,
  * and otherwise exactly what whisper_full / wmi_full_long / wmi_full_batch return for the converted samples (an empty clip included).
  * The no-speech, token-DTW and grammar-device modes apply as in those calls; each call takes the locks the call it ends in takes;
  * wmi_get_timings gains nothing (the conversion's time is in wmi_wav_stats, and, being queued in front of the log-mel, inside the wall
  * time of the transcription).  Off unless called: a context that never makes one of these calls allocates and launches nothing for them.
- * Not served: IMA-ADPCM and QOA, RIFF headers (Godot hands over the data chunk), more than two channels, SRC_SINC_BEST_QUALITY. */
+ * Not served: QOA, IMA-ADPCM outside wmi_set_wav_adpcm's mode 1, RIFF headers (Godot hands over the data chunk), more than two channels, SRC_SINC_BEST_QUALITY. */
 enum { WMI_WAV_S8 = 0, WMI_WAV_S16 = 1, WMI_WAV_F32 = 32 };   /* 0 / 1 = AudioStreamWAV.FORMAT_8_BITS / FORMAT_16_BITS */
 struct wmi_wav {
     const void * data;
@@ -1020,6 +1020,59 @@ WHISPER_API int wmi_full_wav_channels(struct whisper_context * ctx, struct whisp
 WHISPER_API int wmi_channels_select(struct whisper_context * ctx, int channel);
 WHISPER_API int wmi_channels_get_segment(struct whisper_context * ctx, int i, struct wmi_channel_segment * out);
 WHISPER_API int wmi_selftest_channels_merge(const int64_t * t0_a, int n_a, const int64_t * t0_b, int n_b, int * out_channel, int * out_index);
+
+/* IMA-ADPCM clips (AudioStreamWAV.FORMAT_IMA_ADPCM, format value 2) decoded on the device: the compressed bytes go up as they are, half a
+ * byte per sample, and every WAV call above serves them.
+ *   replaces: decoding the clip on the host (in the node a GDScript loop per nibble) and handing over two or four bytes per sample.
+ * The definition, held bit for bit (tests/adpcm_ref.py; csrc/adpcm_map.h):
+ *   tables   the standard IMA ones: STEP[89] = 7, 8, 9, .. 29794, 32767; INDEX[16] = {-1, -1, -1, -1, 2, 4, 6, 8} twice
+ *   state    per channel (predictor, step_index), (0, 0) in front of the clip; there are no block headers: a channel is ONE stream
+ *   nibble n step = STEP[step_index]; step_index = clamp(step_index + INDEX[n], 0, 88);
+ *            diff = step >> 3 (+ step >> 2 if n & 1) (+ step >> 1 if n & 2) (+ step if n & 4), negated if n & 8 — in at least 32 bits;
+ *            predictor = clamp(predictor + diff, -32768, 32767); the sample is the predictor
+ *   layout   the low nibble of a byte first.  Mono: byte k = frames 2k, 2k + 1; frames = 2 * n_bytes.  Stereo: byte 2k + c = frames 2k,
+ *            2k + 1 of channel c; frames = 2 * (n_bytes / 2), a trailing odd byte is ignored
+ *   result   the decoded clip is interleaved s16; a format-2 clip gives exactly what the same call gives for WMI_WAV_S16 data equal to
+ *            the decoded samples, with the same stereo and mix_rate — nothing new is defined behind the decode
+ * NOT verified (Godot's source is not part of this repository): the layout and the initial state are written from knowledge of Godot
+ * 4.1's audio_stream_wav.cpp; and Godot may hold `diff` in an int16_t, which wraps where step >= 18500 meets n & 7 == 7 — an encoder
+ * corner.  Here diff has 32 bits, as Godot's own encoder assumes; a clip that reaches that corner may decode differently there.
+ * On the device (csrc/k_adpcm.hip): both recurrences are chains of clamped additions x -> min(max(x + a, lo), hi), which compose exactly
+ * (csrc/adpcm_map.h), so each is a prefix scan over chunks of 32 nibbles: five launches per clip (reduce, walk of the
+ * partials, apply — the index's apply is the predictor's reduce), queued on the conversion's stream between the upload and the existing
+ * conversion with no host wait; no workgroup waits for another.  The s16 image lands in a grow-only buffer of the context and the call goes
+ * on as for a device-resident WMI_WAV_S16 clip: the conversion, the resampler's readers, the channel split and the speaker bins are the
+ * existing launches.
+ *   wmi_set_wav_adpcm   the context's mode, read where a WAV call plans its clips.  0 (default): format 2 is -11 (-111) everywhere, as
+ *                       without this interface, and nothing is allocated or launched for it.  on != 0: format 2 is served by wmi_wav_to_pcm,
+ *                       wmi_wav_to_pcm_channels, wmi_full_wav, wmi_full_long_wav, wmi_full_batch_wav (clips of mixed formats in one call),
+ *                       wmi_full_wav_channels (a mono clip: -12 as ever), wmi_wav_speaker, with the speaker modes.  Returns the previous
+ *                       mode, -2 for a NULL context.  Format 3 (QOA) stays -11 in both modes.  Argument errors are decided on the host
+ *                       as before: more frames than an int holds (mono: 2 * n_bytes > INT_MAX) is -1; a device source (on_device) may lie
+ *                       at any byte address.  wmi_selftest_wav_plan has no context and keeps answering -11.  wmi_wav_stats: the bytes
+ *                       copied count the ADPCM bytes, the launches count the five decode launches too.
+ *   wmi_selftest_adpcm_plan    host only: wmi_selftest_wav_plan as mode 1 plans (format 2: the decoded clip's frames and result count)
+ *   wmi_selftest_adpcm_shape   out5 = { nibbles per chunk (one chunk per thread and channel), lanes per wavefront, chunks per workgroup,
+ *                       partials per tile of the cross-workgroup walk, launches per clip }
+ *   wmi_selftest_adpcm_decode  the kernels alone on `device`: the bytes are placed src_byte_offset (0 - 4096) bytes into a device
+ *                       allocation; out_s16 gets frames * channels interleaved samples.  *frames is written first; -4: cap_frames below
+ *                       it; -5: a byte outside the image (the guard the hook keeps around it) was written; -1 / -2 / -3 as above
+ *   wmi_selftest_adpcm_host    host only: the sequential loop in C++ — the definition, and the baseline for timing.  Returns the frames,
+ *                       -4: cap_frames below them
+ *   wmi_selftest_adpcm_maps    host only: csrc/adpcm_map.h's compose and apply over n caller-made nibbles (one per byte, 0 - 15) of one
+ *                       channel cut into chunks of `chunk`: the kernels' plan with sequential scans.  out_predictor / out_index [chunks + 1]:
+ *                       every chunk's entry state and, last, the state behind the stream.  Returns the chunk count; -4: cap below chunks + 1
+ *   wmi_bench_adpcm_decode     the decode launches alone, `iters` times, each between two device events: ms[iters] */
+WHISPER_API int wmi_set_wav_adpcm(struct whisper_context * ctx, int on);
+WHISPER_API int wmi_selftest_adpcm_plan(const struct wmi_wav * wav, int converter, long long * frames, long long * n_out);
+WHISPER_API int wmi_selftest_adpcm_shape(int * out5);
+WHISPER_API int wmi_selftest_adpcm_decode(int device, const unsigned char * bytes, long long n_bytes, int stereo, int src_byte_offset,
+                                          int16_t * out_s16, long long cap_frames, long long * frames);
+WHISPER_API int wmi_selftest_adpcm_host(const unsigned char * bytes, long long n_bytes, int stereo, int16_t * out_s16, long long cap_frames);
+WHISPER_API int wmi_selftest_adpcm_maps(const unsigned char * nibbles, long long n, int chunk, int32_t * out_predictor, int32_t * out_index,
+                                        long long cap);
+WHISPER_API int wmi_bench_adpcm_decode(int device, const unsigned char * bytes, long long n_bytes, int stereo, int src_byte_offset, int iters,
+                                       float * ms);
 
 /* Host worker pool self-test (no device needed): `reps` jobs of `n_tasks` tasks; returns reps * n_tasks * (n_tasks + 1) / 2
  * when every task of every job ran exactly once. */
